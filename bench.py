@@ -43,6 +43,9 @@ Printed JSON (rank 0, one line) carries, besides the contract fields:
   per_rank          - ms per step, kernel ms, fraction of rays marched for every rank (N > 1);
   parity            - max |error| of ONE image of this very workload rendered by the timed code path against the CPU
                       oracle (untimed; budget 1e-4 on rgb / depth / mask);
+  dump_outputs      - with --dump-outputs DIR: what the last timed step returned (rgb, depth, mask), written as DIR/<name>.npy
+                      (float32); the noise draws of the timed steps start from a fixed seed, so equal arguments give equal
+                      inputs from run to run and two builds can be compared array for array;
   cpu_baseline      - kind 'reference': run.py::render + the real Generator's sampler (oracle/_ref, staged by
                       oracle/make_ref.py) timed on this box's host cores on ONE image of the same workload; kind 'port' (the
                       oracle restatement) only where the staged sources are missing.
@@ -74,6 +77,7 @@ MFMA_F32_PEAK_TFLOPS = 157.3
 MFMA_F16_PEAK_TFLOPS = 2500.0
 MLP_FLOP_PER_RAY = 704512
 N_SIMD = 1024
+DUMP_BYTES_MAX = 64 << 20                            # --dump-outputs: cap on the bytes written
 PMC_PROFILES = ('profiles/r6/pmc_render_fwd.json', 'profiles/r5/pmc_render_fwd.json', 'profiles/r4/pmc_render_fwd.json', 'profiles/r3/pmc_render_fwd.json', 'profiles/r2/pmc_render_fwd.json', 'profiles/r1/pmc_render_fwd_derived.json')
 
 
@@ -257,6 +261,28 @@ def roofline(kernel_ms, marched, n_images, live_clock_hz=None, texels='fp32'):
     return r
 
 
+def dump_outputs(out, dir_):
+    """Writes the arrays of one render step's result as dir_/<name>.npy (float32).  Above DUMP_BYTES_MAX the same seeded
+    sample of whole images is taken from every array.  Returns {'dir', 'arrays': {name: shape}, 'images': indices or 'all'}."""
+    import numpy as np
+    names = ('rgb', 'depth', 'mask')
+    n_img = out['rgb'].shape[0]
+    per_image = sum(out[k][0].numel() * 4 for k in names)
+    keep = min(n_img, max(1, DUMP_BYTES_MAX // per_image))
+    idx = None
+    if keep < n_img:
+        idx = torch.randperm(n_img, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    os.makedirs(dir_, exist_ok=True)
+    shapes = {}
+    for k in names:
+        a = out[k].detach().float().cpu()
+        if idx is not None:
+            a = a[idx]
+        np.save(os.path.join(dir_, k + '.npy'), a.numpy())
+        shapes[k] = list(a.shape)
+    return {'dir': dir_, 'arrays': shapes, 'images': 'all' if idx is None else idx.tolist()}
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher (how the driver calls it): re-run this very command line under
     torch.distributed.run, one process per GPU on 127.0.0.1; rank 0 prints the JSON line, the exit code is passed on."""
@@ -304,7 +330,13 @@ def main():
                     help='render mode, two-stream schedule: consecutive render kernels alternate over this many streams '
                          '(default 1; 2 with fp16 texels)')
     ap.add_argument('--serial', action='store_true', help='render mode: one stream, every step after the previous one (the default)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='render mode: after the timed steps, write what the last timed step returned (rgb, depth, mask) as '
+                         'DIR/<name>.npy, float32, at most %d MB (a fixed, seeded sample of the images beyond that); rank 0'
+                         % (DUMP_BYTES_MAX >> 20))
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != 'render':
+        ap.error('--dump-outputs: render mode only')
 
     if 'WORLD_SIZE' not in os.environ and (args.gpus > 1 or args.force_dist):
         return self_launch(args.gpus)
@@ -373,6 +405,7 @@ def main():
         i + depth runs on a second HIP stream while step i renders (depth + 1 slots; a slot is refilled only after the
         render that read it has finished).  Every step does all of its work either way."""
         main = torch.cuda.current_stream(dev)
+        out = None                                          # (n = 0: --warmup 0)
         if not pipelined:
             for i in range(n):
                 pre = prepare(v, v.get('ws'))
@@ -421,10 +454,13 @@ def main():
         """W untimed + exactly K timed steps of variant v, barrier + synchronize on both sides, max over ranks."""
         run_steps(v, args.warmup, pipelined)
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        # the noise draws of the K timed steps start from a fixed state: with the same arguments the last step's inputs are
+        # the same from run to run, whatever the prewarm ran (host-side only, outside the timed region)
+        torch.cuda.manual_seed(4321 + rank)
         fence()
         t0 = time.perf_counter()
         marks[0].record()
-        run_steps(v, args.steps, pipelined, marks)
+        last = run_steps(v, args.steps, pipelined, marks)
         fence()
         local = time.perf_counter() - t0
         per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
@@ -433,7 +469,7 @@ def main():
             t = torch.tensor([local], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        return elapsed, per_step, local
+        return elapsed, per_step, local, last
 
     headline = {'d': d, 'tuning': 0}
     pipelined = bool(args.pipelined) and not args.serial
@@ -445,7 +481,9 @@ def main():
             run_steps(headline, 10, pipelined)
             torch.cuda.synchronize()
             prewarm_steps += 10
-    elapsed, per_step, local_elapsed = timed(headline, pipelined)
+    elapsed, per_step, local_elapsed, last = timed(headline, pipelined)
+    dumped = dump_outputs(last, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    del last
 
     variants = {}
     if not args.no_variants:
@@ -457,7 +495,7 @@ def main():
             # BASELINE cfg2 names bf16: the same whole step with the triplanes handed over as bf16 texels (arithmetic fp32)
             legs.append(('bf16_texels', {'d': d, 'tuning': 0, 'tdt': ops.TEXEL_BF16}, pipelined))
         for name, v, pl in legs:
-            e_v, per_v, _ = timed(v, pl)
+            e_v, per_v, _, _ = timed(v, pl)
             variants[name] = {'value': world * n_rays * args.steps / e_v, 'ms_per_step': e_v / args.steps * 1e3,
                               'ms_per_step_stats': stats(per_v)}
 
@@ -569,6 +607,8 @@ def main():
                 if r16:
                     res['config']['%s_vs_fp32_reference_rgb' % tx] = r16['max_abs']['rgb']
                     res['config']['%s_vs_fp32_reference_rgb_mean' % tx] = r16['mean_abs']['rgb']
+        if dumped is not None:
+            res['dump_outputs'] = dumped
         if world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'], res['parity'] = cpu_baseline_and_parity(1234, dev, ops, args.texels)
         else:

@@ -132,3 +132,23 @@ def test_bench_launches_itself_when_called_without_a_launcher(gpu_device, mode):
     r = subprocess.run([sys.executable, 'bench.py', '--gpus', '64', '--steps', '1', '--warmup', '0'], cwd=ROOT,
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode != 0 and 'GPU(s) are visible' in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_repeat_exactly(gpu_device, tmp_path):
+    """--dump-outputs DIR: the last timed step's rgb / depth / mask as float32 .npy; with equal arguments two runs write the
+    same arrays (the timed steps' noise starts from a fixed seed), and --steps is the number of timed steps."""
+    import numpy as np
+    runs = []
+    for name in ('a', 'b'):
+        r = subprocess.run([sys.executable, 'bench.py', '--steps', '4', '--warmup', '1', '--no-cpu-baseline', '--no-extras',
+                            '--no-variants', '--images-per-gpu', '2', '--dump-outputs', str(tmp_path / name)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _last_json(r.stdout)
+        assert j['steps'] == 4 and j['ms_per_step'] > 0
+        assert j['dump_outputs']['arrays'] == {'rgb': [2, 128, 128, 3], 'depth': [2, 128, 128], 'mask': [2, 128, 128]}
+        runs.append({k: np.load(str(tmp_path / name / (k + '.npy'))) for k in ('rgb', 'depth', 'mask')})
+    for k, a in runs[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), k
+        assert np.array_equal(a, runs[1][k]), k
+    assert runs[0]['mask'].max() > 0.5                            # the cameras see the scene

@@ -76,3 +76,27 @@ def test_design_md_stays_a_current_state_document():
     too_long = [(i + 1, len(l)) for i, l in enumerate(lines) if len(l) > 120]
     assert not too_long, too_long[:5]
     assert os.path.exists(os.path.join(ROOT, 'HISTORY.md'))
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_whole_images_above_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 .npy per returned array; above the byte cap the same seeded sample of whole
+    images from every array, the same sample every time."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(5)
+    out = {'rgb': torch.rand(6, 4, 4, 3, generator=g), 'depth': torch.rand(6, 4, 4, generator=g),
+           'mask': torch.rand(6, 4, 4, generator=g)}
+    info = bench.dump_outputs(out, str(tmp_path / 'all'))
+    assert info['images'] == 'all' and info['arrays']['rgb'] == [6, 4, 4, 3]
+    for k in ('rgb', 'depth', 'mask'):
+        a = np.load(str(tmp_path / 'all' / (k + '.npy')))
+        assert a.dtype == np.float32 and np.array_equal(a, out[k].numpy())
+    monkeypatch.setattr(bench, 'DUMP_BYTES_MAX', 3 * 4 * 4 * 5 * 4)          # room for three images
+    a = bench.dump_outputs(out, str(tmp_path / 'a'))
+    b = bench.dump_outputs(out, str(tmp_path / 'b'))
+    assert len(a['images']) == 3 and a['images'] == sorted(a['images']) and a['images'] == b['images']
+    assert sum(os.path.getsize(str(tmp_path / 'a' / (k + '.npy'))) - 128 for k in ('rgb', 'depth', 'mask')) <= bench.DUMP_BYTES_MAX
+    for k in ('rgb', 'depth', 'mask'):
+        assert np.array_equal(np.load(str(tmp_path / 'a' / (k + '.npy'))), out[k][a['images']].numpy())

@@ -11,9 +11,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import make_ref, reference  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not reference.available(), reason='reference sources not available (oracle/make_ref.py)')
+needs_reference = pytest.mark.skipif(not reference.available(), reason='reference sources not available (oracle/make_ref.py)')
 
 
+@needs_reference
 def test_staged_copy_is_complete_and_intact():
     root = make_ref.stage()
     assert root == make_ref.DST and make_ref.staged_ok()
@@ -26,6 +27,7 @@ def test_staged_copy_is_complete_and_intact():
             assert open(os.path.join(root, f), 'rb').read() == open(os.path.join(make_ref.REF, f), 'rb').read(), f
 
 
+@needs_reference
 def test_staged_copy_is_ignored_by_git_but_not_by_gpurun():
     assert 'oracle/_ref/' in open(os.path.join(ROOT, '.gitignore')).read().split()
     if os.path.isdir(os.path.join(ROOT, '.git')):          # (a checkout; an archive / GPU-box snapshot has no .git)
@@ -37,6 +39,7 @@ def test_staged_copy_is_ignored_by_git_but_not_by_gpurun():
     assert 'oracle' not in ignore and '_ref' not in ignore          # it has to travel to the GPU box with the snapshot
 
 
+@needs_reference
 def test_loader_falls_back_to_the_staged_copy():
     env = dict(os.environ, NFI_REFERENCE_CHECKOUT='/nonexistent')
     code = ('import sys; sys.path.insert(0, %r)\n'
