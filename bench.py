@@ -20,7 +20,14 @@ and the shader clock (2.30 GHz in the first steps after idle, 2.38 GHz settled) 
 the driver's `--steps 20 --warmup 5` - reads the same rate as a long one (141 M rays/s; 134 M without it).  Reported in
 `prewarm`.
 
-Printed JSON (rank 0, one line) carries, besides the contract fields:
+A plain run (no --full) does only what the headline needs: set-up, prewarm, the W warm-up and K timed steps, the
+--dump-outputs arrays and the result line; `roofline` and `cpu_baseline` are null there.  `--full` adds everything else
+below (the variant legs, the live kernel timing and roofline, the extras, the CPU baseline and parity figure), each leg
+after the headline's timed steps as before; --no-variants / --no-extras / --no-cpu-baseline leave single legs out of it.
+
+Printed JSON (rank 0, one line) carries, besides the contract fields (with --full only: the config.value_* / config.x_* /
+end-to-end scalars, variants, roofline, kernel_ms_stats, per_rank's kernel_ms and shader_clock_hz, extras, parity and
+cpu_baseline):
   config.value_mlp_exact_fp32 / .value_all_rays_hit / .value_pipelined - the same whole step, same K, same protocol, with
                       the decoder MLP on exact-fp32 MFMA (tuning bit 3) / with cameras at radius 1.3 (every ray crosses
                       the scene cube, nothing is skipped) / under the two-stream schedule (scalars inside `config`, where
@@ -308,8 +315,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--mode', choices=('render', 'train'), default='render')
     ap.add_argument('--images-per-gpu', type=int, default=None)
-    ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the CPU oracle leg (and the parity figure)')
-    ap.add_argument('--no-extras', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='render mode: after the headline, also run the variant legs, the live kernel timing and roofline, '
+                         'the extras and the CPU baseline with the parity figure (a plain run prints the headline alone)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU oracle leg (and the parity figure)')
+    ap.add_argument('--no-extras', action='store_true', help='--full: skip the extras')
     ap.add_argument('--no-skip', action='store_true', help='march rays that miss the scene cube too')
     ap.add_argument('--force-dist', action='store_true', help='initialise RCCL even with one rank (exercises the N>1 code path)')
     ap.add_argument('--bucket-mb', type=int, default=32, help='train mode: gradient bucket size')
@@ -323,7 +333,7 @@ def main():
                     help='render mode: untimed steps for this long before the W warm-up steps (allocator and shader clock '
                          'in steady state, HISTORY.md 4.3); 0 switches it off')
     ap.add_argument('--no-variants', action='store_true',
-                    help='render mode: skip the value_mlp_exact_fp32 / value_all_rays_hit / value_pipelined legs')
+                    help='--full: skip the value_mlp_exact_fp32 / value_all_rays_hit / value_pipelined legs')
     ap.add_argument('--prefetch-depth', type=int, default=2,
                     help='render mode, two-stream schedule: how many steps ahead the front of a step is prepared')
     ap.add_argument('--render-streams', type=int, default=None,
@@ -486,7 +496,7 @@ def main():
     del last
 
     variants = {}
-    if not args.no_variants:
+    if args.full and not args.no_variants:
         legs = [('all_rays_hit', {'d': d_hit, 'tuning': 0}, pipelined),
                 ('pipelined' if not pipelined else 'serial', {'d': d, 'tuning': 0}, not pipelined)]
         if args.texels == 'fp32':
@@ -499,17 +509,19 @@ def main():
             variants[name] = {'value': world * n_rays * args.steps / e_v, 'ms_per_step': e_v / args.steps * 1e3,
                               'ms_per_step_stats': stats(per_v)}
 
-    # ---- dominant kernel, timed live with HIP events on its own stream (untimed extra launches) ----
+    # ---- dominant kernel, timed live with HIP events on its own stream (untimed extra launches; --full) ----
     k_ms, k_clk = [], []
+    kernel_ms = live_clock = None
 
     def read_kernel_events():
         k_ms.append(ev.elapsed_ms())
         cyc, ticks = (int(v) for v in probe.tolist())
         if ticks > 0:
             k_clk.append(cyc / ticks * 1e8)                # s_memrealtime ticks at 100 MHz
-    run_steps(headline, min(50, max(5, args.steps)), pipelined, timed_kernel=True, after=read_kernel_events)    # same schedule as the timed steps
-    kernel_ms = sum(k_ms) / len(k_ms)
-    live_clock = sum(k_clk) / len(k_clk) if k_clk else None
+    if args.full:
+        run_steps(headline, min(50, max(5, args.steps)), pipelined, timed_kernel=True, after=read_kernel_events)    # same schedule as the timed steps
+        kernel_ms = sum(k_ms) / len(k_ms)
+        live_clock = sum(k_clk) / len(k_clk) if k_clk else None
     # rays the kernel marches = rays whose line meets the cube inflated by 1e-4 (the kernel's own skip test, fp32)
     import numpy as np
     wide = float(np.float32(SCENE_RANGE) * np.float32(1.0001))
@@ -540,7 +552,7 @@ def main():
             'schedule': two_stream if pipelined else 'one stream, serial steps: what a caller of the drop-in render() gets',
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': 'f32 (decoder MLP operands split-fp16 hi+lo, 22 bits; strict fp32: config.value_mlp_exact_fp32)',
-            'data': 'synthetic',
+            'data': 'synthetic', 'full': args.full,
             'config': {'workload': 'cfg2: shapenet_chairs-like forward render, %d images/GPU, 128x128 rays/image, '
                                    '64 coarse + 64 fine samples, 3x256x256x32 fp32 triplanes, SDF decoder, A=10; '
                                    'step = texel hand-off + decoder pack + 2 rand draws + ray set-up + fused render kernel'
@@ -571,10 +583,11 @@ def main():
                                    'rate; all_rays_hit = cameras at radius 1.3, every ray crosses the scene cube; bf16_texels = the triplanes handed over '
                                    'as bf16 texels (the storage type BASELINE cfg2 names; arithmetic fp32, parity against the rounded planes); %s = %s'
                                    % (other, two_stream if other == 'pipelined' else 'one stream'))
-        res['roofline'] = roofline(kernel_ms, marched, B, live_clock, args.texels)
-        res['kernel_ms_stats'] = stats(k_ms)
+        res['roofline'] = roofline(kernel_ms, marched, B, live_clock, args.texels) if args.full else None
+        if args.full:
+            res['kernel_ms_stats'] = stats(k_ms)
         res['per_rank'] = per_rank
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             res['extras'] = extras(dev, ops)      # before the CPU leg: its OpenMP workers keep spinning for a while
             ref_gpu = res['extras'].get('pytorch_rocm_reference_path') or {}
             if ref_gpu.get('value'):
@@ -609,7 +622,7 @@ def main():
                     res['config']['%s_vs_fp32_reference_rgb_mean' % tx] = r16['mean_abs']['rgb']
         if dumped is not None:
             res['dump_outputs'] = dumped
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'], res['parity'] = cpu_baseline_and_parity(1234, dev, ops, args.texels)
         else:
             res['cpu_baseline'] = None

@@ -5,6 +5,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -21,8 +22,8 @@ def _last_json(out):
 
 
 def test_bench_single_process(gpu_device):
-    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-extras',
-                        '--images-per-gpu', '2'], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline',
+                        '--no-extras', '--images-per-gpu', '2'], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)
     for k in REQUIRED:
@@ -52,10 +53,31 @@ def test_bench_single_process(gpu_device):
     assert lv['gather_stream_algorithmic']['x_hbm_peak'] > 0
 
 
+def test_bench_plain_run_is_the_headline_alone(gpu_device):
+    """Without --full the run sets up, warms up, times the K steps and prints the line: no variant legs, no live kernel
+    timing or roofline, no extras, no CPU baseline.  The whole process spends at most 30 s outside its W + K steps."""
+    steps, warmup = 20, 5
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup)], cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _last_json(r.stdout)
+    for k in REQUIRED:
+        assert k in j, k
+    assert j['full'] is False and j['steps'] == steps and j['value'] > 1e6 and j['ms_per_step'] > 0
+    assert j['roofline'] is None and j['cpu_baseline'] is None
+    for k in ('variants', 'extras', 'parity', 'kernel_ms_stats'):
+        assert k not in j, k
+    assert not [k for k in j['config'] if k.startswith(('value_', 'x_'))], j['config']
+    assert j['per_rank'][0]['kernel_ms'] is None and 0 < j['per_rank'][0]['rays_marched_fraction'] <= 1
+    assert wall - (steps + warmup) * j['ms_per_step'] * 1e-3 <= 30.0, wall
+
+
 def test_bench_16_bit_texel_storage(gpu_device):
     """--texels bf16 (the storage type BASELINE cfg2 names): the line comes out, the exact-fp32 leg (fp32 texels only) is left
     out, and the run's own parity figure is taken against the ROUNDED planes."""
-    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--no-extras', '--texels', 'bf16',
+    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--full', '--no-extras', '--texels', 'bf16',
                         '--images-per-gpu', '2'], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)
@@ -65,7 +87,7 @@ def test_bench_16_bit_texel_storage(gpu_device):
 
 def test_bench_parity_figure(gpu_device):
     """The bench line carries its own parity check: one image of the timed workload against the CPU oracle."""
-    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--no-extras'], cwd=ROOT,
+    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--full', '--no-extras'], cwd=ROOT,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)
@@ -105,7 +127,7 @@ def test_bench_distributed_code_path(gpu_device):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1',
                         '--master-addr', '127.0.0.1', '--master-port', '29517', 'bench.py', '--gpus', '1', '--steps', '3',
-                        '--warmup', '1', '--no-cpu-baseline', '--no-extras', '--images-per-gpu', '2', '--force-dist'],
+                        '--warmup', '1', '--full', '--no-cpu-baseline', '--no-extras', '--images-per-gpu', '2', '--force-dist'],
                        cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     j = _last_json(r.stdout)

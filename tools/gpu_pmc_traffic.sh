@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for C in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  timeout 120 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/p$i -o b -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/p$i.log 2>&1
+  timeout 120 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/p$i -o b -- python $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $OUT/p$i.log 2>&1
 done
 python - <<PY
 import csv, glob, collections, json

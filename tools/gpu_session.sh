@@ -29,16 +29,16 @@ for w in $WHAT; do
     refreport)
       timeout 1500 python tools/reference_report.py $REFREPORT_SECTIONS > $O/reference_parity.json 2> $O/reference_parity.err; echo "refreport rc=$?" >> $O/env.txt;;
     bench)
-      t0=$(date +%s); timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$? seconds=$(( $(date +%s) - t0 ))" >> $O/env.txt; tail -c 600 $O/bench.json;;
+      t0=$(date +%s); timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$? seconds=$(( $(date +%s) - t0 ))" >> $O/env.txt; tail -c 600 $O/bench.json;;
     train)
       timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 \
         bench.py --gpus 1 --mode train --steps 30 --warmup 5 --force-dist > $O/train.json 2> $O/train.err; echo "train rc=$?" >> $O/env.txt; tail -c 1500 $O/train.json;;
     pmc)
       timeout 1200 python tools/pmc_collect.py --workdir /tmp/pmc_fwd --kernel render_fwd_kernel --out $O/pmc_render_fwd.json --marched-from-bench -- \
-        python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-variants > $O/pmc.log 2>&1; echo "pmc rc=$?" >> $O/env.txt; tail -30 $O/pmc.log;;
+        python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras --no-variants > $O/pmc.log 2>&1; echo "pmc rc=$?" >> $O/env.txt; tail -30 $O/pmc.log;;
     pmc_bf16)
       timeout 1200 python tools/pmc_collect.py --workdir /tmp/pmc_bf16 --kernel render_fwd_kernel --out $O/pmc_render_fwd_bf16.json --marched-from-bench -- \
-        python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-variants --texels bf16 > $O/pmc_bf16.log 2>&1; echo "pmc_bf16 rc=$?" >> $O/env.txt; tail -12 $O/pmc_bf16.log;;
+        python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras --no-variants --texels bf16 > $O/pmc_bf16.log 2>&1; echo "pmc_bf16 rc=$?" >> $O/env.txt; tail -12 $O/pmc_bf16.log;;
     pmc_bwd)
       # the field backward kernel inside the training step (4 images x 128x128 rays x (64 + 64) samples: ONE launch since the one-node render)
       timeout 1200 python tools/pmc_collect.py --workdir /tmp/pmc_bwd --kernel field_query_bwd_kernel --out $O/pmc_backward.json --units 8388608 -- \

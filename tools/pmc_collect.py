@@ -2,7 +2,7 @@
 sys/hip/hsa tracing), plus the derived per-launch figures bench.py's roofline reads.
 
   python tools/pmc_collect.py --kernel render_fwd_kernel --out gpurun_out/pmc_render_fwd.json \
-         --marched-from-bench -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras
+         --marched-from-bench -- python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras
 
 Passes: (0) kernel trace + stats, (1) FETCH_SIZE, (2) WRITE_SIZE, (3) TCC_HIT_sum TCC_MISS_sum,
 (4) SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_VALU_MFMA_BUSY_CYCLES, (5) SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY
@@ -43,7 +43,7 @@ def main():
     ap.add_argument('--out', required=True)
     ap.add_argument('--workdir', default=None)
     ap.add_argument('--marched-from-bench', action='store_true',
-                    help='the command is bench.py: take rays_marched_per_launch from its JSON line')
+                    help='the command is bench.py --full: take rays_marched_per_launch from its JSON line')
     ap.add_argument('--units', type=float, default=None, help='units (rays / points) processed per launch, if known')
     ap.add_argument('--pick', choices=('mean', 'max'), default='mean',
                     help='how to combine the launches of the kernel (max: the launch with the largest counter value)')
@@ -63,7 +63,10 @@ def main():
     if a.marched_from_bench:
         for line in open(os.path.join(work, 'p0.log')):
             if line.startswith('{') and '"roofline"' in line:
-                units = json.loads(line)['roofline']['rays_marched_per_launch']
+                rf = json.loads(line)['roofline']
+                if rf is None:
+                    raise SystemExit('--marched-from-bench: the bench line has no roofline (run bench.py with --full)')
+                units = rf['rays_marched_per_launch']
     durs = []
     for f in glob.glob(os.path.join(d0, '**', '*kernel_trace.csv'), recursive=True):
         for r in csv.DictReader(open(f)):
