@@ -390,6 +390,8 @@ int nfi_sdf_gradient_bwd(const nfi_sdf_gradient_args* a, nfi_stream_t stream);
  * Fused forward render: run.py::render (176-350) from cameras + texels to pixels in one
  * persistent launch (plus the ray set-up launch), no per-sample HBM round trips.
  * ------------------------------------------------------------------------------------------ */
+/* bits of nfi_render_args.tuning that the library reads (described at the field; every other bit is ignored) */
+enum { NFI_TUNING_SCANLINE_ORDER = 4, NFI_TUNING_EXACT_FP32_MLP = 8, NFI_TUNING_SINGLE_WORK_COUNTER = 16 };
 typedef struct nfi_render_args {
   int n_scenes, height, width;
   int n_samples;                 /* S per pass, <= NFI_MAX_SAMPLES; without fine_sampling a single pass of up to
@@ -427,10 +429,10 @@ typedef struct nfi_render_args {
   /* optional hipEvent_t pair recorded on the stream immediately before / after the render kernel
    * (excludes the ray set-up launch): live per-launch kernel timing for bench.py.  NULL = off. */
   void* event_start; void* event_stop;
-  /* tuning knob, 0 = default.  bit 2: hand rays out in scanline order instead of 8x8 pixel tiles
-   * (results identical).  bit 3: evaluate the decoder MLP with exact-fp32 MFMA instead of the
+  /* tuning knob, 0 = default, an OR of NFI_TUNING_*.  bit 2 (SCANLINE_ORDER): hand rays out in scanline order instead
+   * of 8x8 pixel tiles (results identical).  bit 3 (EXACT_FP32_MLP): evaluate the decoder MLP with exact-fp32 MFMA instead of the
    * split-fp16 (hi+lo, 22 significand bits) MFMA; both meet the 1e-4 parity budget (fp32 texels only: with 16-bit texel
-   * storage the texels, not the MLP operands, set the precision - the call is refused).  bit 4: ONE device-wide work
+   * storage the texels, not the MLP operands, set the precision - the call is refused).  bit 4 (SINGLE_WORK_COUNTER): ONE device-wide work
    * counter instead of the per-XCD queues over square pixel blocks (results identical; the per-XCD queues take the
    * largest of 32 / 16 / 8 pixels that divides both image sides, two positions per atomic, and fall back to the single
    * counter when not even 8 does). */

@@ -1324,6 +1324,16 @@ extern "C" size_t nfi_field_bwd_workspace_bytes(const nfi_field_bwd_args* a) {
 extern "C" size_t nfi_decoder_bwd_image_floats(void) { return (size_t)kBwdImageFloats; }
 extern "C" size_t nfi_decoder_bwd_image_floats_viewdir(void) { return (size_t)kVbImageFloats; }
 
+template <bool ATT, bool COORD, bool VD, int TEX>
+static int launch_field_bwd(dim3 grid, size_t shmem, hipStream_t s, const FieldBwdParams& k) {
+  constexpr auto kernel = &field_query_bwd_kernel<ATT, COORD, VD, TEX>;
+  // shmem depends on VD only, a template argument: one constant per instantiation
+  const int rc = ensure_dynamic_lds<kernel>(shmem, "field_query_bwd");
+  if (rc) return rc;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), shmem, s, k);
+  return NFI_OK;
+}
+
 extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t stream) {
   REQUIRE(a && a->points && a->texels && a->decoder_image && a->w1 && a->w2 && a->workspace && a->g_sigma && a->g_rgb,
           "field_query_bwd: null pointer");
@@ -1417,27 +1427,15 @@ extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t str
   const size_t shmem = vd ? (size_t)(kVdFieldLdsFloats + kVbImageFloats + 4 * kStFloatsVd) * sizeof(float)
                           : (size_t)(kBwdFwdFloats + kBwdImageFloats + 4 * kStFloats) * sizeof(float);
   const bool att = a->n_attention > 0, coord = a->g_points != nullptr;
-#define NFI_LAUNCH_FBWD_T(ATT, COORD, VD, TEX)                                                                    \
-  do {                                                                                                            \
-    /* shmem depends on VD only, a template argument: one constant per instantiation */                            \
-    NFI_ENSURE_DYNAMIC_LDS((&field_query_bwd_kernel<ATT, COORD, VD, TEX>), shmem, "field_query_bwd");               \
-    hipLaunchKernelGGL((field_query_bwd_kernel<ATT, COORD, VD, TEX>), grid, dim3(256), shmem, s, k);               \
-  } while (0)
-#define NFI_LAUNCH_FBWD(ATT, COORD, VD)                                                                           \
-  do {                                                                                                            \
-    if (VD || a->texel_dtype == NFI_TEXEL_F32) NFI_LAUNCH_FBWD_T(ATT, COORD, VD, 0);                               \
-    else if (a->texel_dtype == NFI_TEXEL_BF16) NFI_LAUNCH_FBWD_T(ATT, COORD, false, 1);                            \
-    else NFI_LAUNCH_FBWD_T(ATT, COORD, false, 2);                                                                 \
-  } while (0)
-  if (vd) {
-    if (att) { if (coord) NFI_LAUNCH_FBWD(true, true, true); else NFI_LAUNCH_FBWD(true, false, true); }
-    else { if (coord) NFI_LAUNCH_FBWD(false, true, true); else NFI_LAUNCH_FBWD(false, false, true); }
-  } else {
-    if (att) { if (coord) NFI_LAUNCH_FBWD(true, true, false); else NFI_LAUNCH_FBWD(true, false, false); }
-    else { if (coord) NFI_LAUNCH_FBWD(false, true, false); else NFI_LAUNCH_FBWD(false, false, false); }
-  }
-#undef NFI_LAUNCH_FBWD
-#undef NFI_LAUNCH_FBWD_T
+  rc = dispatch_texel_att(a->texel_dtype, att, [&](auto tex, auto att_c) {
+    constexpr int TEX = decltype(tex)::value;
+    constexpr bool ATT = decltype(att_c)::value;
+    if constexpr (TEX == 0) {     // the view-direction decoder: fp32 texels (checked above)
+      if (vd) return coord ? launch_field_bwd<ATT, true, true, 0>(grid, shmem, s, k) : launch_field_bwd<ATT, false, true, 0>(grid, shmem, s, k);
+    }
+    return coord ? launch_field_bwd<ATT, true, false, TEX>(grid, shmem, s, k) : launch_field_bwd<ATT, false, false, TEX>(grid, shmem, s, k);
+  });
+  if (rc) return rc;
   if (binned) {
     const dim3 pgrid((unsigned)((a->points_per_scene + 1023) / 1024), (unsigned)a->n_scenes);
     hipLaunchKernelGGL(bin_count_kernel, pgrid, dim3(256), 0, s, bp);

@@ -334,7 +334,8 @@ extern "C" int nfi_torgb_texels_fwd(const nfi_torgb_args* a, nfi_stream_t stream
   const int per_block = 64 * 4 * kTorgbTilesPerWave;
   dim3 grid((unsigned)((P + per_block - 1) / per_block), (unsigned)k.B);
   const size_t shmem = ((size_t)kTorgbOut * k.Cin + k.Cin + kTorgbOut) * sizeof(float);
-  NFI_ENSURE_DYNAMIC_LDS(&torgb_texels_fwd_kernel, ((size_t)kTorgbOut * kTorgbMaxCin + kTorgbMaxCin + kTorgbOut) * sizeof(float), "torgb_texels_fwd");
+  rc = ensure_dynamic_lds<&torgb_texels_fwd_kernel>(((size_t)kTorgbOut * kTorgbMaxCin + kTorgbMaxCin + kTorgbOut) * sizeof(float), "torgb_texels_fwd");
+  if (rc) return rc;
   hipLaunchKernelGGL(torgb_texels_fwd_kernel, grid, dim3(256), shmem, (hipStream_t)stream, k);
   return check_launch("torgb_texels_fwd");
 }
@@ -354,7 +355,8 @@ extern "C" int nfi_torgb_texels_bwd(const nfi_torgb_args* a, nfi_stream_t stream
     const int per_block = 64 * 4 * kTorgbTilesPerWave;
     dim3 grid((unsigned)((P + per_block - 1) / per_block), (unsigned)k.B);
     const size_t shmem = ((size_t)kTorgbOut * k.Cin + k.Cin) * sizeof(float);
-    NFI_ENSURE_DYNAMIC_LDS(&torgb_bwd_data_kernel, ((size_t)kTorgbOut * kTorgbMaxCin + kTorgbMaxCin) * sizeof(float), "torgb_texels_bwd");
+    rc = ensure_dynamic_lds<&torgb_bwd_data_kernel>(((size_t)kTorgbOut * kTorgbMaxCin + kTorgbMaxCin) * sizeof(float), "torgb_texels_bwd");
+    if (rc) return rc;
     hipLaunchKernelGGL(torgb_bwd_data_kernel, grid, dim3(256), shmem, s, k);
   }
   if (k.g_weight) {

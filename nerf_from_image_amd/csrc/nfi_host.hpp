@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <cstdio>
+#include <type_traits>
 
 extern thread_local char nfi_err_buf[256];          // defined in nfi_kernels.hip
 
@@ -22,23 +23,27 @@ static inline int check_launch(const char* what) {
   return NFI_OK;
 }
 
-// Raises a kernel's dynamic-LDS limit to `bytes` - the LARGEST size any launch of that kernel uses, a constant - once per
+// Raises Kernel's dynamic-LDS limit to `bytes` - the LARGEST size any launch of that kernel uses, a constant - once per
 // device.  The attribute is process-global per kernel and device; because the value never changes, host threads
-// launching concurrently (one per GPU under nn.DataParallel) cannot lower it under each other, and a failure is
-// reported instead of surfacing as a failed launch later.
-#define NFI_ENSURE_DYNAMIC_LDS(kernel, bytes, what)                                                                  \
-  do {                                                                                                               \
-    static std::atomic<unsigned long long> nfi_done_{0};                                                             \
-    int nfi_dev_ = 0;                                                                                                \
-    if (hipGetDevice(&nfi_dev_) != hipSuccess) return fail(NFI_ERR_LAUNCH, what ": hipGetDevice failed");            \
-    const unsigned long long nfi_bit_ = 1ull << (nfi_dev_ & 63);                                                     \
-    if (!(nfi_done_.load(std::memory_order_acquire) & nfi_bit_)) {                                                   \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                              (int)(bytes)) != hipSuccess)                                                           \
-        return fail(NFI_ERR_LAUNCH, what ": hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");                \
-      nfi_done_.fetch_or(nfi_bit_, std::memory_order_release);                                                       \
-    }                                                                                                                \
-  } while (0)
+// launching concurrently (one per GPU under nn.DataParallel) cannot lower it under each other (two that race both
+// write the same value), and a failure is reported instead of surfacing as a failed launch later.
+// One flag per kernel - the function's own static - with one bit per device.
+template <auto Kernel>
+static int ensure_dynamic_lds(size_t bytes, const char* what) {
+  static std::atomic<unsigned long long> done{0};
+  int dev = 0;
+  const char* failed = hipGetDevice(&dev) != hipSuccess ? "hipGetDevice" : nullptr;
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (!failed && !(done.load(std::memory_order_acquire) & bit)) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess)
+      done.fetch_or(bit, std::memory_order_release);
+    else
+      failed = "hipFuncSetAttribute(MaxDynamicSharedMemorySize)";
+  }
+  if (!failed) return NFI_OK;
+  snprintf(nfi_err_buf, sizeof(nfi_err_buf), "%s: %s failed", what, failed);
+  return NFI_ERR_LAUNCH;
+}
 
 #define REQUIRE(cond, msg) \
   do {                     \
@@ -46,6 +51,17 @@ static inline int check_launch(const char* what) {
   } while (0)
 
 static inline int texel_bytes(int dtype) { return dtype == NFI_TEXEL_F32 ? 128 : 64; }
+
+// The run-time -> compile-time step of the kernel dispatchers: calls f(std::integral_constant<int, TEX>, std::bool_constant<ATT>)
+// with the kernels' TEX argument of `texel_dtype` (0 fp32, 1 bf16, 2 fp16; the type was checked by check_field_common)
+// and ATT = the decoder has attention values.  f is a generic lambda; all six calls must return the same type.
+template <class F>
+static auto dispatch_texel_att(int texel_dtype, bool att, F&& f) {
+  auto with_tex = [&](auto tex) { return att ? f(tex, std::true_type{}) : f(tex, std::false_type{}); };
+  if (texel_dtype == NFI_TEXEL_F32) return with_tex(std::integral_constant<int, 0>{});
+  if (texel_dtype == NFI_TEXEL_BF16) return with_tex(std::integral_constant<int, 1>{});
+  return with_tex(std::integral_constant<int, 2>{});
+}
 
 static inline int check_field_common(const void* texels, int plane_res, int texel_dtype, const float* image, int A,
                               const float* att, int use_sdf, const float* beta, const float* alpha, int layout = 0) {

@@ -5,6 +5,7 @@
 #include "nfi_host.hpp"
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 
@@ -561,24 +562,16 @@ extern "C" int nfi_field_query_fwd(const nfi_field_args* a, nfi_stream_t stream)
   if (blocks > 2048) blocks = 2048;
   dim3 grid((unsigned)blocks, (unsigned)a->n_scenes);
   hipStream_t s = (hipStream_t)stream;
-  bool att = a->n_attention > 0;
-#define NFI_LAUNCH_FIELD(TEX)                                                                          \
-  do {                                                                                                \
-    if (a->ray_features) {                                                                            \
-      if (att) hipLaunchKernelGGL((field_query_kernel<TEX, true, true>), grid, dim3(256), 0, s, k);   \
-      else hipLaunchKernelGGL((field_query_kernel<TEX, false, true>), grid, dim3(256), 0, s, k);      \
-    } else if (a->mlp_precision == 1) {                                                               \
-      if (att) hipLaunchKernelGGL((field_query_kernel<TEX, true, false, 1>), grid, dim3(256), 0, s, k);  \
-      else hipLaunchKernelGGL((field_query_kernel<TEX, false, false, 1>), grid, dim3(256), 0, s, k);     \
-    } else {                                                                                          \
-      if (att) hipLaunchKernelGGL((field_query_kernel<TEX, true>), grid, dim3(256), 0, s, k);         \
-      else hipLaunchKernelGGL((field_query_kernel<TEX, false>), grid, dim3(256), 0, s, k);            \
-    }                                                                                                 \
-  } while (0)
-  if (a->texel_dtype == NFI_TEXEL_F32) NFI_LAUNCH_FIELD(0);
-  else if (a->texel_dtype == NFI_TEXEL_BF16) NFI_LAUNCH_FIELD(1);
-  else NFI_LAUNCH_FIELD(2);
-#undef NFI_LAUNCH_FIELD
+  const bool att = a->n_attention > 0;
+  using FieldKernel = void (*)(FieldKernelParams);
+  const FieldKernel kernel = dispatch_texel_att(a->texel_dtype, att, [&](auto tex, auto att_c) -> FieldKernel {
+    constexpr int TEX = decltype(tex)::value;
+    constexpr bool ATT = decltype(att_c)::value;
+    if (a->ray_features) return field_query_kernel<TEX, ATT, true>;
+    if (a->mlp_precision == 1) return field_query_kernel<TEX, ATT, false, 1>;
+    return field_query_kernel<TEX, ATT>;
+  });
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, k);
   return check_launch("field_query_fwd");
 }
 
@@ -2182,41 +2175,49 @@ __global__ __launch_bounds__(256, NFI_RENDER_OCC) void render_fwd_long_kernel(Re
   clock.stop(k);
 }
 
+// The render workspace: [RenderWorkspaceHeader][ro, rd: 3n floats each][near_raw, far_raw: n floats each][hit: n bytes,
+// padded to 64].  The header is what ONE memset of the ray set-up clears; callers read reduce[] from it (the first
+// three cells of the workspace).
+struct RenderWorkspaceHeader {
+  uint32_t reduce[3];            // the batch-wide miss-fill of the ray set-up: ~key(min near), key(max far), hit count
+  uint32_t counter;              // the device-wide work counter (RenderKernelParams::counter)
+  uint32_t pad[12];
+  uint32_t xcd_counter[8][16];   // the per-XCD work counters, 64 bytes apart (RenderKernelParams::xcd_counter)
+};
+static_assert(sizeof(RenderWorkspaceHeader) == 64 + 8 * 64 && offsetof(RenderWorkspaceHeader, xcd_counter) == 64,
+              "the render workspace header is read from Python and by the kernels' 16-dword counter stride");
+
 extern "C" size_t nfi_render_workspace_bytes(int64_t n_rays) {
-  // ro, rd, near_raw, far_raw (fp32) + hit (u8, padded) + reduce[4]
   size_t n = (size_t)n_rays;
-  return n * 8 * sizeof(float) + ((n + 63) & ~(size_t)63) + 64 + 8 * 64;     // + 8 per-XCD work counters
+  return sizeof(RenderWorkspaceHeader) + n * 8 * sizeof(float) + ((n + 63) & ~(size_t)63);
 }
 
 // workspace carve + ray set-up shared by nfi_render_setup and nfi_render_fwd
-struct RenderWorkspace { uint32_t* reduce; uint32_t* xcd_counter; float* ro; float* rd; float* near_raw; float* far_raw; uint8_t* hit; int64_t n; };
+struct RenderWorkspace { RenderWorkspaceHeader* head; float* ro; float* rd; float* near_raw; float* far_raw; uint8_t* hit; int64_t n; };
 
 static int render_carve(const nfi_render_args* a, RenderWorkspace& w) {
   REQUIRE(a && a->cam2world && a->workspace, "render: null pointer");
   REQUIRE(a->n_scenes > 0 && a->height > 0 && a->width > 0, "render: bad image shape");
   const int64_t n = (int64_t)a->n_scenes * a->height * a->width;
   if (a->workspace_bytes < nfi_render_workspace_bytes(n)) return fail(NFI_ERR_WORKSPACE_TOO_SMALL, "render: workspace too small");
-  // [reduce: 16 floats][8 per-XCD work counters, 64 B apart: 128 floats][ro rd near far: 8n floats][hit: n bytes, padded]
-  float* ws = reinterpret_cast<float*>(a->workspace);
-  constexpr int kRays0 = 16 + 128;
   w.n = n;
-  w.reduce = reinterpret_cast<uint32_t*>(ws);
-  w.xcd_counter = reinterpret_cast<uint32_t*>(ws + 16);
-  w.ro = a->ray_origins ? a->ray_origins : ws + kRays0;
-  w.rd = a->ray_directions ? a->ray_directions : ws + kRays0 + 3 * n;
-  w.near_raw = ws + kRays0 + 6 * n;
-  w.far_raw = ws + kRays0 + 7 * n;
-  w.hit = a->hit ? a->hit : reinterpret_cast<uint8_t*>(ws + kRays0 + 8 * n);
+  w.head = reinterpret_cast<RenderWorkspaceHeader*>(a->workspace);
+  float* rays = reinterpret_cast<float*>(w.head + 1);
+  w.ro = a->ray_origins ? a->ray_origins : rays;
+  w.rd = a->ray_directions ? a->ray_directions : rays + 3 * n;
+  w.near_raw = rays + 6 * n;
+  w.far_raw = rays + 7 * n;
+  w.hit = a->hit ? a->hit : reinterpret_cast<uint8_t*>(rays + 8 * n);
   return NFI_OK;
 }
 
 static int render_setup(const nfi_render_args* a, const RenderWorkspace& w, hipStream_t s) {
-  // (64 + 512 + 32n + pad(n) bytes = nfi_render_workspace_bytes)  ONE memset clears the reduction cells and the counters
-  if (hipMemsetAsync(w.reduce, 0, 64 + 8 * 64, s) != hipSuccess) return fail(NFI_ERR_LAUNCH, "render: memset failed");
+  // ONE memset clears the reduction cells and the counters
+  if (hipMemsetAsync(w.head, 0, sizeof(RenderWorkspaceHeader), s) != hipSuccess) return fail(NFI_ERR_LAUNCH, "render: memset failed");
   const int full_h = a->full_height > 0 ? a->full_height : a->height;
   REQUIRE(a->row_offset >= 0 && a->row_offset + a->height <= full_h, "render: row window outside the image");
   CameraParams cam{a->cam2world, a->focal, a->bbox, a->focal ? a->center : nullptr, full_h, a->width, 1, a->height, a->row_offset};
-  RaygenOut rout{w.ro, w.rd, w.near_raw, w.far_raw, w.hit, w.reduce, a->scene_range};
+  RaygenOut rout{w.ro, w.rd, w.near_raw, w.far_raw, w.hit, w.head->reduce, a->scene_range};
   hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)std::min<int64_t>((w.n + 255) / 256, kRayBlocks)), dim3(256), 0, s, cam, a->n_scenes, rout);
   return NFI_OK;
 }
@@ -2230,7 +2231,25 @@ extern "C" int nfi_render_setup(const nfi_render_args* a, nfi_stream_t stream) {
   return check_launch("render_setup");
 }
 
-extern "C" int nfi_render_fwd(const nfi_render_args* a, nfi_stream_t stream) {
+// What of a render call picks the kernel variant, besides the texel type and the sample count: the training stash, any
+// per-sample / per-ray debug tap (these switch the missed-ray skip off), either of the two (the kRenderTaps kernels), the
+// exact-fp32 MLP instead of the split-fp16 one, ray termination in the fine pass, a semantics / coords / normals map
+struct RenderFlags { bool stash, debug_tap, any_tap, strict, term, extra; };
+
+static RenderFlags render_flags(const nfi_render_args* a) {
+  RenderFlags f;
+  f.stash = a->stash_t || a->stash_sigma || a->stash_rgb;
+  f.debug_tap = a->t_coarse || a->sigma_coarse || a->rgb_coarse || a->t_fine || a->sigma_fine || a->rgb_fine ||
+                a->t_sorted || a->weights || a->perm || a->near_plane || a->far_plane;
+  f.any_tap = f.debug_tap || f.stash;
+  f.strict = (a->tuning & NFI_TUNING_EXACT_FP32_MLP) != 0;
+  f.term = a->termination_eps > 0.0f;
+  f.extra = a->semantics || a->coords || a->normals;
+  return f;
+}
+
+// The argument rules of nfi_render_fwd, in two parts: the ray set-up runs between them (rules are reported in this order)
+static int render_check_call(const nfi_render_args* a) {
   REQUIRE(a && a->cam2world && a->rgb && a->depth && a->mask && a->workspace, "render: null pointer");
   REQUIRE(a->n_scenes > 0 && a->height > 0 && a->width > 0, "render: bad image shape");
   REQUIRE(a->n_samples >= 4 && a->n_samples <= (a->fine_sampling ? NFI_MAX_SAMPLES : NFI_MAX_SAMPLES_SINGLE_PASS),
@@ -2240,37 +2259,37 @@ extern "C" int nfi_render_fwd(const nfi_render_args* a, nfi_stream_t stream) {
           "render: semantics / coords / normals maps exist for n_samples <= 128");
   REQUIRE(!a->fine_sampling || a->noise_fine, "render: fine sampling needs u (noise_fine)");
   REQUIRE(!a->semantics || a->n_attention > 0, "render: composited semantics need attention values (A > 0)");
-  int rc = check_field_common(a->texels, a->plane_res, a->texel_dtype, a->decoder_image, a->n_attention,
-                               a->attention_values, a->use_sdf, a->beta, a->alpha, a->texel_layout);
-  if (rc) return rc;
-  RenderWorkspace w;
-  rc = render_carve(a, w);
-  if (rc) return rc;
-  const int64_t n = w.n;
-  hipStream_t s = (hipStream_t)stream;
-  uint32_t* reduce = w.reduce;
-  uint32_t* xcd_counter = w.xcd_counter;
-  float *ro = w.ro, *rd = w.rd, *near_raw = w.near_raw, *far_raw = w.far_raw;
-  uint8_t* hit = w.hit;
-  REQUIRE(!(a->rays_ready && (a->ray_origins || a->ray_directions || a->hit || a->stash_t)),
-          "render: rays_ready needs the ray set-up in the workspace (no ray_origins / ray_directions / hit taps, no stash)");
-  if (!a->rays_ready) {
-    rc = render_setup(a, w, s);
-    if (rc) return rc;
-  }
+  return check_field_common(a->texels, a->plane_res, a->texel_dtype, a->decoder_image, a->n_attention,
+                            a->attention_values, a->use_sdf, a->beta, a->alpha, a->texel_layout);
+}
 
-  const bool stash = a->stash_t || a->stash_sigma || a->stash_rgb;
-  REQUIRE(!stash || (a->stash_t && a->stash_sigma && a->stash_rgb), "render: the training stash needs stash_t, stash_sigma and stash_rgb");
-  REQUIRE(!stash || !(a->t_coarse || a->sigma_coarse || a->rgb_coarse || a->t_fine || a->sigma_fine || a->rgb_fine),
+static int render_check_variant(const nfi_render_args* a, const RenderFlags& f) {
+  REQUIRE(!f.stash || (a->stash_t && a->stash_sigma && a->stash_rgb), "render: the training stash needs stash_t, stash_sigma and stash_rgb");
+  REQUIRE(!f.stash || !(a->t_coarse || a->sigma_coarse || a->rgb_coarse || a->t_fine || a->sigma_fine || a->rgb_fine),
           "render: the training stash and the per-sample debug taps are mutually exclusive");
-  const bool debug_tap = a->t_coarse || a->sigma_coarse || a->rgb_coarse || a->t_fine || a->sigma_fine || a->rgb_fine ||
-                         a->t_sorted || a->weights || a->perm || a->near_plane || a->far_plane;
-  const bool any_tap = debug_tap || stash;
+  REQUIRE(!a->normals || a->use_sdf, "render: the normals map needs the SDF decoder (use_sdf)");
+  REQUIRE(a->termination_eps >= 0.0f && a->termination_eps < 1.0f, "render: termination_eps must be in [0,1)");
+  REQUIRE(!f.term || a->fine_sampling, "render: termination_eps acts on the fine pass (fine_sampling)");
+  REQUIRE(!f.term || !(f.any_tap || f.extra || a->profile_cycles || a->ray_features || f.strict),
+          "render: termination_eps cannot be combined with stage taps, extra maps, the cycle profile, the view-direction decoder or the exact-fp32 MLP");
+  REQUIRE(!f.extra || !(f.any_tap || a->profile_cycles || f.strict),
+          "render: semantics / coords / normals maps cannot be combined with stage taps, the cycle profile or the exact-fp32 MLP");
+  REQUIRE(!(f.extra && a->ray_features) || a->texel_dtype == NFI_TEXEL_F32,
+          "render: with the view-direction decoder the semantics / coords / normals maps exist for fp32 texels");
+  // the exact-fp32 MLP (a diagnostic of the split-fp16 arithmetic) and the cycle profile are built for fp32 texels only:
+  // with 16-bit texel storage the texels, not the MLP operands, set the precision
+  REQUIRE(!(f.strict || a->profile_cycles) || a->texel_dtype == NFI_TEXEL_F32,
+          "render: the exact-fp32 MLP (tuning bit 3) and the cycle profile exist for fp32 texels");
+  REQUIRE(!(a->ray_features && a->profile_cycles), "render: no cycle profile with the view-direction decoder");
+  return NFI_OK;
+}
+
+static RenderKernelParams render_kernel_params(const nfi_render_args* a, const RenderWorkspace& w, const RenderFlags& f) {
   RenderKernelParams k;
   memset(&k, 0, sizeof(k));
   k.n_scenes = a->n_scenes; k.hw = a->height * a->width; k.S = a->n_samples;
   k.fine = a->fine_sampling; k.white = a->white_background; k.scene_range = a->scene_range;
-  k.ro = ro; k.rd = rd; k.near_raw = near_raw; k.far_raw = far_raw; k.hit = hit; k.reduce = reduce;
+  k.ro = w.ro; k.rd = w.rd; k.near_raw = w.near_raw; k.far_raw = w.far_raw; k.hit = w.hit; k.reduce = w.head->reduce;
   k.texels = a->texels; k.res = a->plane_res; k.layout = a->texel_layout; k.image = a->decoder_image; k.A = a->n_attention; k.att = a->attention_values;
   k.use_sdf = a->use_sdf; k.beta = a->beta; k.alpha = a->alpha;
   k.noise_c = a->noise_coarse; k.noise_f = a->noise_fine; k.noise_f_stride = a->noise_fine_row_stride;
@@ -2279,7 +2298,7 @@ extern "C" int nfi_render_fwd(const nfi_render_args* a, nfi_stream_t stream) {
   k.t_coarse = a->t_coarse; k.sigma_coarse = a->sigma_coarse; k.rgb_coarse = a->rgb_coarse;
   k.t_fine = a->t_fine; k.sigma_fine = a->sigma_fine; k.rgb_fine = a->rgb_fine;
   k.tap_stride = a->n_samples;
-  if (stash) {
+  if (f.stash) {
     // the stash rows hold the coarse samples in [0,S) and - with fine sampling - the fine samples in [S,2S)
     k.tap_stride = (a->fine_sampling ? 2 : 1) * a->n_samples; k.stash = 1;
     k.t_coarse = a->stash_t; k.sigma_coarse = a->stash_sigma; k.rgb_coarse = a->stash_rgb;
@@ -2290,168 +2309,135 @@ extern "C" int nfi_render_fwd(const nfi_render_args* a, nfi_stream_t stream) {
     }
   }
   k.t_sorted = a->t_sorted; k.weights = a->weights; k.perm = a->perm;
-  k.skip_missed = (a->skip_missed_rays && !debug_tap) ? 1 : 0;
+  k.skip_missed = (a->skip_missed_rays && !f.debug_tap) ? 1 : 0;
 
-  k.counter = reduce + 3;
+  k.counter = &w.head->counter;
+  k.xcd_counter = &w.head->xcd_counter[0][0];
   k.width = a->width;
-  // per-XCD queues (tuning bit 4 switches them off): square pixel blocks, needs image sides that are multiples of 8
-  {
-    // the largest of 32 / 16 / 8-pixel blocks that divides both image sides, TWO positions per atomic.
-    // MI355X, 8 x 128^2 x (64+64), ms per launch chairs-like / every ray hits / one image (round 3, build-time variants):
-    // 32x32 + 2: 0.854 / 1.299 / 0.164; 8x8 + 2: 0.848 / 1.328 / 0.167; 16x16 + 2: 0.891 / 1.301 / 0.170; 16x16 + 1 (the
-    // round-1 default): 0.933 / 1.311 / 0.185; 32x32 + 1: 0.882 / 1.317 / 0.174; 4 per atomic: 0.88-0.90 / 1.33-1.38; one
-    // device-wide counter 1.82 / 2.10.  Halving the atomics matters on every workload (the wave waits for each one's
-    // result); the block side mostly through the balance of the chairs-like images, whose rays that cross the cube are
-    // clustered.
-    k.fetch_batch = 2;
-    const int both = a->width | a->height;
-    k.xcd_block_shift = (both & 31) == 0 ? 5 : ((both & 15) == 0 ? 4 : 3);
-    const int side = 1 << k.xcd_block_shift;
-    k.xcd_blocks = (((a->tuning >> 4) & 1) == 0 && (a->width % side == 0) && (a->height % side == 0)) ? 1 : 0;
-    const uint32_t bw = (uint32_t)a->width >> k.xcd_block_shift, bh = (uint32_t)a->height >> k.xcd_block_shift;
-    k.div_hw = make_fastdiv((uint32_t)k.hw);
-    k.div_bw = make_fastdiv(bw > 0 ? bw : 1u);
-    k.div_bps = make_fastdiv(bw * bh > 0 ? bw * bh : 1u);
-  }
-  k.xcd_counter = xcd_counter;
-  k.tile_order = (((a->tuning >> 2) & 1) == 0 && (a->width % 8 == 0) && (a->height % 8 == 0)) ? 1 : 0;
+  // per-XCD queues (NFI_TUNING_SINGLE_WORK_COUNTER switches them off): square pixel blocks, needs image sides that are
+  // multiples of 8: the largest of 32 / 16 / 8-pixel blocks that divides both image sides, TWO positions per atomic.
+  // MI355X, 8 x 128^2 x (64+64), ms per launch chairs-like / every ray hits / one image (round 3, build-time variants):
+  // 32x32 + 2: 0.854 / 1.299 / 0.164; 8x8 + 2: 0.848 / 1.328 / 0.167; 16x16 + 2: 0.891 / 1.301 / 0.170; 16x16 + 1 (the
+  // round-1 default): 0.933 / 1.311 / 0.185; 32x32 + 1: 0.882 / 1.317 / 0.174; 4 per atomic: 0.88-0.90 / 1.33-1.38; one
+  // device-wide counter 1.82 / 2.10.  Halving the atomics matters on every workload (the wave waits for each one's
+  // result); the block side mostly through the balance of the chairs-like images, whose rays that cross the cube are
+  // clustered.
+  k.fetch_batch = 2;
+  const int both = a->width | a->height;
+  k.xcd_block_shift = (both & 31) == 0 ? 5 : ((both & 15) == 0 ? 4 : 3);
+  const int side = 1 << k.xcd_block_shift;
+  k.xcd_blocks = (!(a->tuning & NFI_TUNING_SINGLE_WORK_COUNTER) && (a->width % side == 0) && (a->height % side == 0)) ? 1 : 0;
+  const uint32_t bw = (uint32_t)a->width >> k.xcd_block_shift, bh = (uint32_t)a->height >> k.xcd_block_shift;
+  k.div_hw = make_fastdiv((uint32_t)k.hw);
+  k.div_bw = make_fastdiv(bw > 0 ? bw : 1u);
+  k.div_bps = make_fastdiv(bw * bh > 0 ? bw * bh : 1u);
+  k.tile_order = (!(a->tuning & NFI_TUNING_SCANLINE_ORDER) && (a->width % 8 == 0) && (a->height % 8 == 0)) ? 1 : 0;
   k.prof = (unsigned long long*)a->profile_cycles;
   k.xray = a->ray_features;
   k.clock_probe = reinterpret_cast<unsigned long long*>(a->clock_probe);
-  const bool strict = ((a->tuning >> 3) & 1) != 0;   // exact-fp32 MLP instead of the split-fp16 one
-  const bool term = a->termination_eps > 0.0f;
-  const bool extra = a->semantics || a->coords || a->normals;
-  REQUIRE(!a->normals || a->use_sdf, "render: the normals map needs the SDF decoder (use_sdf)");
-  REQUIRE(a->termination_eps >= 0.0f && a->termination_eps < 1.0f, "render: termination_eps must be in [0,1)");
-  REQUIRE(!term || a->fine_sampling, "render: termination_eps acts on the fine pass (fine_sampling)");
-  REQUIRE(!term || !(any_tap || extra || a->profile_cycles || a->ray_features || strict),
-          "render: termination_eps cannot be combined with stage taps, extra maps, the cycle profile, the view-direction decoder or the exact-fp32 MLP");
-  REQUIRE(!extra || !(any_tap || a->profile_cycles || strict),
-          "render: semantics / coords / normals maps cannot be combined with stage taps, the cycle profile or the exact-fp32 MLP");
-  REQUIRE(!(extra && a->ray_features) || a->texel_dtype == NFI_TEXEL_F32,
-          "render: with the view-direction decoder the semantics / coords / normals maps exist for fp32 texels");
-  // the exact-fp32 MLP (a diagnostic of the split-fp16 arithmetic) and the cycle profile are built for fp32 texels only:
-  // with 16-bit texel storage the texels, not the MLP operands, set the precision
-  REQUIRE(!(strict || a->profile_cycles) || a->texel_dtype == NFI_TEXEL_F32,
-          "render: the exact-fp32 MLP (tuning bit 3) and the cycle profile exist for fp32 texels");
   k.term_eps = a->termination_eps;
   k.semantics = a->semantics; k.coords = a->coords; k.normals = a->normals;
-  REQUIRE(!(a->ray_features && a->profile_cycles), "render: no cycle profile with the view-direction decoder");
-  // persistent 1-D grid: OCC blocks of 4 waves per CU, never more blocks than rays need
+  return k;
+}
+
+// One launch of a render kernel: which of the render_fwd* instantiations, and what its launch needs to know about it
+using RenderKernel = void (*)(RenderKernelParams);
+struct RenderLaunch {
+  RenderKernel kernel;
+  int occ;                                    // workgroups of 4 waves per CU it is compiled for: the persistent grid is 256 CUs x occ
+  size_t max_lds;                             // the largest dynamic LDS it is ever launched with (0: it uses none)
+  int (*raise_lds)(size_t, const char*);      // ensure_dynamic_lds of this kernel
+};
+template <auto Kernel>
+static RenderLaunch render_launch(int occ = NFI_RENDER_OCC, size_t max_lds = 0) { return {Kernel, occ, max_lds, &ensure_dynamic_lds<Kernel>}; }
+
+// THE rule "which kernel does a (validated) render call get": first match wins.  Every condition that is a template
+// argument is an `if constexpr`, so only kernels that some call can reach are instantiated.
+static RenderLaunch select_render_kernel(const nfi_render_args* a, const RenderFlags& f) {
+  const bool wide = a->n_samples > 64;
+  const bool lng = a->n_samples > NFI_MAX_SAMPLES;     // single pass of up to 512 samples (no fine sampling: checked)
+  const bool vd = a->ray_features != nullptr, normals = a->normals != nullptr, prof = a->profile_cycles != nullptr;
+  // persistent 1-D grid: OCC blocks of 4 waves per CU
   // 2 blocks (8 waves) per CU: with the whole 256-VGPR budget the field tile keeps more loads and MFMA chains in
   // flight than at 3 blocks/CU (MI355X, 8 x 128^2: 0.96 vs 1.01-1.08 ms; 4 blocks/CU spill: 1.52 ms)
-  // (fp16 texel storage, plain inference: the texels stay packed - 168 registers - and THREE blocks per CU fit without a
-  //  spill: 0.705 vs 0.756 ms at 8 x 128^2, every ray hits 1.040 vs 1.174 ms)
-  const int occ = NFI_RENDER_OCC;
-  int64_t blocks = (int64_t)256 * occ, blocks3 = (int64_t)256 * 3;
-  if (blocks > (n + 3) / 4) blocks = (n + 3) / 4;
-  if (blocks3 > (n + 3) / 4) blocks3 = (n + 3) / 4;
-  dim3 grid((unsigned)blocks), grid3((unsigned)blocks3);
-  bool att = a->n_attention > 0;
-  // kRenderExtra with semantics: the per-wave tables [A][pitch] in dynamic LDS
-  const bool wide = a->n_samples > 64;
-  const bool lng = a->n_samples > NFI_MAX_SAMPLES;     // single pass of up to 512 samples (no fine sampling: checked above)
-  // (fp16 texels, 128 + 128, at THREE workgroups per CU - 168 registers, ~40 scratch reloads per ray outside the field
-  //  tiles - was measured in round 4 and is slower: 1.387 vs 1.300 ms chairs-like, 2.249 vs 2.156 ms every ray hits, images
-  //  identical (profiles/r4/wide_fp16_three_workgroups.log); unlike the 64 + 64 kernel, whose fp16 form gains 8 % from the
-  //  third workgroup, a 256-sample ray's texel footprint makes 50 % more rays in flight cost more in the L2 than they hide)
-  const size_t sem_lds = (a->semantics ? (size_t)4 * a->n_attention * (wide ? kSemPitchWide * sizeof(unsigned short) : kSemPitch * sizeof(float)) : 0) +
-                         (a->normals ? (size_t)kNrmLdsFloats * sizeof(float) : 0);
+  constexpr int OCC = NFI_RENDER_OCC;
+  // kRenderExtra / kRenderNormals: the per-wave semantics tables [A][pitch] and the normal operands in dynamic LDS
   constexpr size_t kSemLdsMax = ((size_t)4 * NFI_MAX_ATTENTION * kSemPitch + kNrmLdsFloats) * sizeof(float);
   constexpr size_t kSemLdsMaxWide = (size_t)4 * NFI_MAX_ATTENTION * kSemPitchWide * sizeof(unsigned short) + kNrmLdsFloats * sizeof(float);
-  if (a->event_start) (void)hipEventRecord((hipEvent_t)a->event_start, s);
-#define NFI_LAUNCH_RENDER(TEX, ATT)                                                                                   \
-  do {                                                                                                                \
-    if (a->normals) {                                                                                                 \
-      NFI_ENSURE_DYNAMIC_LDS((render_fwd_kernel<TEX, ATT, NFI_RENDER_OCC, kRenderNormals, 1>), kSemLdsMax, "render");  \
-      hipLaunchKernelGGL((render_fwd_kernel<TEX, ATT, NFI_RENDER_OCC, kRenderNormals, 1>), grid, dim3(256), sem_lds, s, k); \
-    } else if (extra) {                                                                                               \
-      NFI_ENSURE_DYNAMIC_LDS((render_fwd_kernel<TEX, ATT, NFI_RENDER_OCC, kRenderExtra, 1>), kSemLdsMax, "render");    \
-      hipLaunchKernelGGL((render_fwd_kernel<TEX, ATT, NFI_RENDER_OCC, kRenderExtra, 1>), grid, dim3(256), sem_lds, s, k); \
-    } else if (term) hipLaunchKernelGGL((render_fwd_kernel<TEX, ATT, NFI_RENDER_OCC, kRenderTerm, 1>), grid, dim3(256), 0, s, k); \
-    else if (k.prof) hipLaunchKernelGGL((render_fwd_kernel<0, ATT, NFI_RENDER_OCC, kRenderProf, 1>), grid, dim3(256), 0, s, k);      \
-    else if (any_tap && strict) hipLaunchKernelGGL((render_fwd_kernel<0, ATT, NFI_RENDER_OCC, kRenderTaps, 0>), grid, dim3(256), 0, s, k);   \
-    else if (any_tap) hipLaunchKernelGGL((render_fwd_kernel<TEX, ATT, NFI_RENDER_OCC, kRenderTaps, 1>), grid, dim3(256), 0, s, k);          \
-    else if (strict) hipLaunchKernelGGL((render_fwd_kernel<0, ATT, NFI_RENDER_OCC, kRenderPlain, 0>), grid, dim3(256), 0, s, k);            \
-    else if (TEX != 0) hipLaunchKernelGGL((render_fwd_kernel<TEX, ATT, 3, kRenderPlain, 1>), grid3, dim3(256), 0, s, k);      \
-    else hipLaunchKernelGGL((render_fwd_kernel<TEX, ATT, NFI_RENDER_OCC, kRenderPlain, 1>), grid, dim3(256), 0, s, k);                      \
-  } while (0)
-#define NFI_LAUNCH_RENDER_WIDE(TEX, ATT)                                                                             \
-  do {                                                                                                                \
-    if (a->normals) {                                                                                                 \
-      NFI_ENSURE_DYNAMIC_LDS((render_fwd_wide_kernel<TEX, ATT, kRenderNormals, 1>), kSemLdsMaxWide, "render");         \
-      hipLaunchKernelGGL((render_fwd_wide_kernel<TEX, ATT, kRenderNormals, 1>), grid, dim3(256), sem_lds, s, k);       \
-    } else if (extra) {                                                                                               \
-      NFI_ENSURE_DYNAMIC_LDS((render_fwd_wide_kernel<TEX, ATT, kRenderExtra, 1>), kSemLdsMaxWide, "render");           \
-      hipLaunchKernelGGL((render_fwd_wide_kernel<TEX, ATT, kRenderExtra, 1>), grid, dim3(256), sem_lds, s, k);         \
-    } else if (term) hipLaunchKernelGGL((render_fwd_wide_kernel<TEX, ATT, kRenderTerm, 1>), grid, dim3(256), 0, s, k);   \
-    else if (any_tap && strict) hipLaunchKernelGGL((render_fwd_wide_kernel<0, ATT, kRenderTaps, 0>), grid, dim3(256), 0, s, k);   \
-    else if (any_tap) hipLaunchKernelGGL((render_fwd_wide_kernel<TEX, ATT, kRenderTaps, 1>), grid, dim3(256), 0, s, k);        \
-    else if (strict) hipLaunchKernelGGL((render_fwd_wide_kernel<0, ATT, kRenderPlain, 0>), grid, dim3(256), 0, s, k);          \
-    else hipLaunchKernelGGL((render_fwd_wide_kernel<TEX, ATT, kRenderPlain, 1>), grid, dim3(256), 0, s, k);                    \
-  } while (0)
-#define NFI_LAUNCH_RENDER_VD(TEX, ATT)                                                                                        \
-  do {                                                                                                                      \
-    if (a->normals && TEX == 0) { /* + the normal map (round 6): the distance is row 0 of the second layer here too */       \
-      if (wide) {                                                                                                           \
-        NFI_ENSURE_DYNAMIC_LDS((render_fwd_wide_kernel<0, ATT, kRenderNormals, 0, true>), kSemLdsMaxWide, "render");         \
-        hipLaunchKernelGGL((render_fwd_wide_kernel<0, ATT, kRenderNormals, 0, true>), grid, dim3(256), sem_lds, s, k);       \
-      } else {                                                                                                              \
-        NFI_ENSURE_DYNAMIC_LDS((render_fwd_kernel<0, ATT, NFI_RENDER_OCC, kRenderNormals, 0, true>), kSemLdsMax, "render");  \
-        hipLaunchKernelGGL((render_fwd_kernel<0, ATT, NFI_RENDER_OCC, kRenderNormals, 0, true>), grid, dim3(256), sem_lds, s, k); \
-      }                                                                                                                     \
-    } else if (extra && TEX == 0) { /* semantics / coords maps with the view-direction decoder (fp32 texels: checked above) */ \
-      if (wide) {                                                                                                           \
-        NFI_ENSURE_DYNAMIC_LDS((render_fwd_wide_kernel<0, ATT, kRenderExtra, 0, true>), kSemLdsMaxWide, "render");           \
-        hipLaunchKernelGGL((render_fwd_wide_kernel<0, ATT, kRenderExtra, 0, true>), grid, dim3(256), sem_lds, s, k);         \
-      } else {                                                                                                              \
-        NFI_ENSURE_DYNAMIC_LDS((render_fwd_kernel<0, ATT, NFI_RENDER_OCC, kRenderExtra, 0, true>), kSemLdsMax, "render");    \
-        hipLaunchKernelGGL((render_fwd_kernel<0, ATT, NFI_RENDER_OCC, kRenderExtra, 0, true>), grid, dim3(256), sem_lds, s, k); \
-      }                                                                                                                     \
-    } else if (wide) hipLaunchKernelGGL((render_fwd_wide_kernel<TEX, ATT, kRenderTaps, 0, true>), grid, dim3(256), 0, s, k);   \
-    else hipLaunchKernelGGL((render_fwd_kernel<TEX, ATT, NFI_RENDER_OCC, kRenderTaps, 0, true>), grid, dim3(256), 0, s, k);                \
-  } while (0)
-#define NFI_LAUNCH_RENDER_LONG(TEX, ATT)                                                                              \
-  do {                                                                                                                \
-    if (a->ray_features) hipLaunchKernelGGL((render_fwd_long_kernel<TEX, ATT, 0, true>), grid, dim3(256), 0, s, k);    \
-    else if (strict) hipLaunchKernelGGL((render_fwd_long_kernel<0, ATT, 0>), grid, dim3(256), 0, s, k);                \
-    else hipLaunchKernelGGL((render_fwd_long_kernel<TEX, ATT, 1>), grid, dim3(256), 0, s, k);                          \
-  } while (0)
-  if (lng) {
-    if (a->texel_dtype == NFI_TEXEL_F32) {
-      if (att) NFI_LAUNCH_RENDER_LONG(0, true); else NFI_LAUNCH_RENDER_LONG(0, false);
-    } else if (a->texel_dtype == NFI_TEXEL_BF16) {
-      if (att) NFI_LAUNCH_RENDER_LONG(1, true); else NFI_LAUNCH_RENDER_LONG(1, false);
-    } else {
-      if (att) NFI_LAUNCH_RENDER_LONG(2, true); else NFI_LAUNCH_RENDER_LONG(2, false);
+  return dispatch_texel_att(a->texel_dtype, a->n_attention > 0, [&](auto tex, auto att) -> RenderLaunch {
+    constexpr int TEX = decltype(tex)::value;
+    constexpr bool ATT = decltype(att)::value;
+    if (lng) {     // 128 < S <= 512: taps and stash are run-time switches of this kernel
+      if (vd) return render_launch<render_fwd_long_kernel<TEX, ATT, 0, true>>();
+      if (f.strict) return render_launch<render_fwd_long_kernel<0, ATT, 0>>();
+      return render_launch<render_fwd_long_kernel<TEX, ATT, 1>>();
     }
-  } else if (a->ray_features) {
-    if (a->texel_dtype == NFI_TEXEL_F32) {
-      if (att) NFI_LAUNCH_RENDER_VD(0, true); else NFI_LAUNCH_RENDER_VD(0, false);
-    } else if (a->texel_dtype == NFI_TEXEL_BF16) {
-      if (att) NFI_LAUNCH_RENDER_VD(1, true); else NFI_LAUNCH_RENDER_VD(1, false);
-    } else {
-      if (att) NFI_LAUNCH_RENDER_VD(2, true); else NFI_LAUNCH_RENDER_VD(2, false);
+    if (vd) {      // the view-direction decoder runs in exact fp32 (PREC 0); its one kernel without maps has the taps, used or not
+      if constexpr (TEX == 0) {      // the maps exist for fp32 texels (checked); the distance of the normals is row 0 of the second layer here too
+        if (normals) return wide ? render_launch<render_fwd_wide_kernel<0, ATT, kRenderNormals, 0, true>>(OCC, kSemLdsMaxWide)
+                                 : render_launch<render_fwd_kernel<0, ATT, OCC, kRenderNormals, 0, true>>(OCC, kSemLdsMax);
+        if (f.extra) return wide ? render_launch<render_fwd_wide_kernel<0, ATT, kRenderExtra, 0, true>>(OCC, kSemLdsMaxWide)
+                                 : render_launch<render_fwd_kernel<0, ATT, OCC, kRenderExtra, 0, true>>(OCC, kSemLdsMax);
+      }
+      return wide ? render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderTaps, 0, true>>()
+                  : render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderTaps, 0, true>>();
     }
-  } else if (wide) {
-    if (a->texel_dtype == NFI_TEXEL_F32) {
-      if (att) NFI_LAUNCH_RENDER_WIDE(0, true); else NFI_LAUNCH_RENDER_WIDE(0, false);
-    } else if (a->texel_dtype == NFI_TEXEL_BF16) {
-      if (att) NFI_LAUNCH_RENDER_WIDE(1, true); else NFI_LAUNCH_RENDER_WIDE(1, false);
-    } else {
-      if (att) NFI_LAUNCH_RENDER_WIDE(2, true); else NFI_LAUNCH_RENDER_WIDE(2, false);
+    if (wide) {    // 64 < S <= 128 per pass
+      if (normals) return render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderNormals, 1>>(OCC, kSemLdsMaxWide);
+      if (f.extra) return render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderExtra, 1>>(OCC, kSemLdsMaxWide);
+      if (f.term) return render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderTerm, 1>>();
+      if (f.any_tap && f.strict) return render_launch<render_fwd_wide_kernel<0, ATT, kRenderTaps, 0>>();
+      if (f.any_tap) return render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderTaps, 1>>();
+      if (f.strict) return render_launch<render_fwd_wide_kernel<0, ATT, kRenderPlain, 0>>();
+      // (fp16 texels, 128 + 128, at THREE workgroups per CU - 168 registers, ~40 scratch reloads per ray outside the field
+      //  tiles - was measured in round 4 and is slower: 1.387 vs 1.300 ms chairs-like, 2.249 vs 2.156 ms every ray hits, images
+      //  identical (profiles/r4/wide_fp16_three_workgroups.log); unlike the 64 + 64 kernel, whose fp16 form gains 8 % from the
+      //  third workgroup, a 256-sample ray's texel footprint makes 50 % more rays in flight cost more in the L2 than they hide)
+      return render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderPlain, 1>>();
     }
-  } else if (a->texel_dtype == NFI_TEXEL_F32) {
-    if (att) NFI_LAUNCH_RENDER(0, true); else NFI_LAUNCH_RENDER(0, false);
-  } else if (a->texel_dtype == NFI_TEXEL_BF16) {
-    if (att) NFI_LAUNCH_RENDER(1, true); else NFI_LAUNCH_RENDER(1, false);
-  } else {
-    if (att) NFI_LAUNCH_RENDER(2, true); else NFI_LAUNCH_RENDER(2, false);
+    if (normals) return render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderNormals, 1>>(OCC, kSemLdsMax);
+    if (f.extra) return render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderExtra, 1>>(OCC, kSemLdsMax);
+    if (f.term) return render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderTerm, 1>>();
+    if (prof) return render_launch<render_fwd_kernel<0, ATT, OCC, kRenderProf, 1>>();
+    if (f.any_tap && f.strict) return render_launch<render_fwd_kernel<0, ATT, OCC, kRenderTaps, 0>>();
+    if (f.any_tap) return render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderTaps, 1>>();
+    if (f.strict) return render_launch<render_fwd_kernel<0, ATT, OCC, kRenderPlain, 0>>();
+    // (16-bit texel storage, plain inference: the texels stay packed - 168 registers - and THREE blocks per CU fit without a
+    //  spill: 0.705 vs 0.756 ms at 8 x 128^2, every ray hits 1.040 vs 1.174 ms)
+    if constexpr (TEX != 0) return render_launch<render_fwd_kernel<TEX, ATT, 3, kRenderPlain, 1>>(3);
+    else return render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderPlain, 1>>();
+  });
+}
+
+extern "C" int nfi_render_fwd(const nfi_render_args* a, nfi_stream_t stream) {
+  int rc = render_check_call(a);
+  if (rc) return rc;
+  RenderWorkspace w;
+  rc = render_carve(a, w);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  REQUIRE(!(a->rays_ready && (a->ray_origins || a->ray_directions || a->hit || a->stash_t)),
+          "render: rays_ready needs the ray set-up in the workspace (no ray_origins / ray_directions / hit taps, no stash)");
+  if (!a->rays_ready) {
+    rc = render_setup(a, w, s);
+    if (rc) return rc;
   }
-#undef NFI_LAUNCH_RENDER_LONG
-#undef NFI_LAUNCH_RENDER_VD
-#undef NFI_LAUNCH_RENDER_WIDE
-#undef NFI_LAUNCH_RENDER
+  const RenderFlags f = render_flags(a);
+  rc = render_check_variant(a, f);
+  if (rc) return rc;
+  const RenderKernelParams k = render_kernel_params(a, w, f);
+  const RenderLaunch launch = select_render_kernel(a, f);
+  // kRenderExtra with semantics: the per-wave tables [A][pitch] in dynamic LDS; kRenderNormals: + the normal operands
+  const size_t lds = (a->semantics ? (size_t)4 * a->n_attention * (a->n_samples > 64 ? kSemPitchWide * sizeof(unsigned short) : kSemPitch * sizeof(float)) : 0) +
+                     (a->normals ? (size_t)kNrmLdsFloats * sizeof(float) : 0);
+  if (launch.max_lds) {
+    rc = launch.raise_lds(launch.max_lds, "render");
+    if (rc) return rc;
+  }
+  // persistent grid: never more blocks than the rays need (4 per block: one wave per ray)
+  const int64_t blocks = std::min<int64_t>((int64_t)256 * launch.occ, (w.n + 3) / 4);
+  if (a->event_start) (void)hipEventRecord((hipEvent_t)a->event_start, s);
+  hipLaunchKernelGGL(launch.kernel, dim3((unsigned)blocks), dim3(256), lds, s, k);
   if (a->event_stop) (void)hipEventRecord((hipEvent_t)a->event_stop, s);
   return check_launch("render_fwd");
 }

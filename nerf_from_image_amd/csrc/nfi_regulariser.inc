@@ -587,7 +587,8 @@ extern "C" int nfi_sdf_gradient_bwd(const nfi_sdf_gradient_args* a, nfi_stream_t
   if (blocks > cap) blocks = cap;
   dim3 grid((unsigned)blocks, (unsigned)a->n_scenes);
   const size_t shmem = (size_t)kRgLdsFloats * sizeof(float);
-  NFI_ENSURE_DYNAMIC_LDS(sdf_gradient_bwd_kernel, shmem, "sdf_gradient_bwd");
+  rc = ensure_dynamic_lds<&sdf_gradient_bwd_kernel>(shmem, "sdf_gradient_bwd");
+  if (rc) return rc;
   hipLaunchKernelGGL(sdf_gradient_bwd_kernel, grid, dim3(256), shmem, (hipStream_t)stream, k);
   return check_launch("sdf_gradient_bwd");
 }
