@@ -183,6 +183,11 @@ typedef struct nfi_field_args {
                                   * renderer's decoder arithmetic (sigma within 3e-5 relative of mode 0) */
 } nfi_field_args;
 int nfi_field_query_fwd(const nfi_field_args* a, nfi_stream_t stream);
+/* Which kernel nfi_field_query_fwd launches for *a: the canonical name of the instantiation - the template's name with
+ * every argument as an integer, "field_query_kernel<TEX,ATT,VD,PREC>" - in static storage, or NULL (nfi_last_error()
+ * says why) for a call the argument rules refuse.  Host only: the same rules and the same selection code as the launch,
+ * no HIP call, no pointer of *a is dereferenced (usable without a GPU, with placeholder pointers). */
+const char* nfi_field_kernel_name(const nfi_field_args* a);
 
 /* 'bbox' visualisation overlay of the sampler closure (models/generator.py:645-659, only with 'coords' in the
  * sampler request and 'bbox' in the model request): sigma_out = sigma_in + 100 for points inside the scene cube
@@ -359,6 +364,8 @@ size_t nfi_field_bwd_workspace_bytes(const nfi_field_bwd_args* a);  /* for the s
 size_t nfi_decoder_bwd_image_floats(void);          /* workspace floats, plain decoder */
 size_t nfi_decoder_bwd_image_floats_viewdir(void);  /* workspace floats, view-direction decoder */
 int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t stream);
+/* as nfi_field_kernel_name, for nfi_field_query_bwd: "field_query_bwd_kernel<ATT,COORD,VD,TEX>" */
+const char* nfi_field_bwd_kernel_name(const nfi_field_bwd_args* a);
 
 /* ------------------------------------------------------------------------------------------
  * Distance field + its spatial gradient as one differentiable operator: the regulariser branch of
@@ -438,7 +445,7 @@ typedef struct nfi_render_args {
    * counter when not even 8 does). */
   int tuning;
   /* optional uint64[12] device array: per-phase shader-cycle sums over all waves (profiling build of
-   * the kernel; NULL = off): field tile {issue, wait+interp, mlp, count}, ray set-up, coarse field,
+   * the kernel; NULL = off): field tile {unused (0), gather issue+wait+interp, mlp, count}, ray set-up, coarse field,
    * resample, fine field, merge, composite, rays marched, wave lifetime; fp32 texels only */
   void* profile_cycles;
   /* view-direction decoder: NULL, or [N, NFI_RAY_FEATURE_PITCH] (decoder_image from nfi_decoder_pack_viewdir;
@@ -487,7 +494,8 @@ typedef struct nfi_render_args {
    * the SAME render launch (rgb / depth / mask bit-identical to a call without it); neither is available together with
    * stage taps, the cycle profile or the exact-fp32 MLP; with the view-direction decoder (ray_features) both exist for fp32
    * texels.  (The 128 + 128 kernel parks the probabilities of `semantics` as unorm16 between the passes: |error| <= 7.7e-6
-   * per sample under a convex combination.) */
+   * per sample under a convex combination; the composited map is then scaled to sum to the mask, as the fp32 table's
+   * does - the roundings of a sample's A probabilities do not cancel.) */
   float* coords;
   /* [N,3] or NULL: the composited normal map, sum_k w_k normalize(d sdf / d x)_k over the merged samples, + (1 - mask)
    * on a white background (compute_normals: run.py:228-230, 241-245, 296-300; lib/nerf_utils.py:149-151, 159; the
@@ -498,6 +506,11 @@ typedef struct nfi_render_args {
 } nfi_render_args;
 size_t nfi_render_workspace_bytes(int64_t n_rays);
 int nfi_render_fwd(const nfi_render_args* a, nfi_stream_t stream);
+/* as nfi_field_kernel_name, for the render kernel of nfi_render_fwd (its argument rules except the workspace size, the
+ * row window and rays_ready, which do not bear on the selection): "render_fwd_kernel<TEX,ATT,OCC,MODE,PREC,VD>" for
+ * n_samples <= 64, "render_fwd_wide_kernel<TEX,ATT,MODE,PREC,VD,OCC>" up to 128, "render_fwd_long_kernel<TEX,ATT,PREC,VD>"
+ * for a single pass beyond that */
+const char* nfi_render_kernel_name(const nfi_render_args* a);
 /* The ray set-up of nfi_render_fwd alone (get_ray_bundle + normalize + the scene-cube test of
  * lib/nerf_utils.py:28-91, 237-268 into the workspace, the batch-wide miss-fill reduction and the work counters cleared).
  * Reads only the camera / shape / scene_range / workspace fields (and ray_origins / ray_directions / hit if given). */

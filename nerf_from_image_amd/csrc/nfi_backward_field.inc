@@ -1334,7 +1334,8 @@ static int launch_field_bwd(dim3 grid, size_t shmem, hipStream_t s, const FieldB
   return NFI_OK;
 }
 
-extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t stream) {
+// The argument rules of nfi_field_query_bwd (pointers against null, integers against limits: nothing is dereferenced)
+static int field_bwd_check_call(const nfi_field_bwd_args* a) {
   REQUIRE(a && a->points && a->texels && a->decoder_image && a->w1 && a->w2 && a->workspace && a->g_sigma && a->g_rgb,
           "field_query_bwd: null pointer");
   REQUIRE(a->points_only ? a->g_points != nullptr : (a->g_texels && a->g_w1 && a->g_b1 && a->g_w2 && a->g_b2),
@@ -1343,7 +1344,7 @@ extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t str
   REQUIRE(a->texel_dtype >= NFI_TEXEL_F32 && a->texel_dtype <= NFI_TEXEL_F16, "field_query_bwd: bad texel dtype");
   REQUIRE(a->texel_dtype == NFI_TEXEL_F32 || !a->ray_features, "field_query_bwd: the view-direction decoder needs fp32 texels");
   int rc = check_field_common(a->texels, a->plane_res, a->texel_dtype, a->decoder_image, a->n_attention,
-                               a->attention_values, a->use_sdf, a->beta, a->alpha, a->texel_layout);
+                              a->attention_values, a->use_sdf, a->beta, a->alpha, a->texel_layout);
   if (rc) return rc;
   REQUIRE(a->points_only || a->n_attention == 0 || a->g_attention_values, "field_query_bwd: g_attention_values missing");
   REQUIRE(a->points_only || !a->use_sdf || (a->g_beta && a->g_alpha), "field_query_bwd: g_beta / g_alpha missing");
@@ -1356,6 +1357,36 @@ extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t str
   REQUIRE(!vd || (a->w3 && a->samples_per_ray > 0 && a->points_per_scene % a->samples_per_ray == 0),
           "field_query_bwd: view-direction decoder needs w3 and points_per_scene % samples_per_ray == 0");
   REQUIRE(!vd || a->points_only || (a->g_w3 && a->g_b3), "field_query_bwd: g_w3 / g_b3 missing");
+  return NFI_OK;
+}
+
+// which field_query_bwd_kernel instantiation a (validated) call gets: its launcher and its canonical name
+struct FieldBwdLaunch { int (*launch)(dim3, size_t, hipStream_t, const FieldBwdParams&); const char* name; };
+static constexpr char kFieldBwdFamily[] = "field_query_bwd_kernel";
+template <bool ATT, bool COORD, bool VD, int TEX>
+static FieldBwdLaunch field_bwd_launch() { return {&launch_field_bwd<ATT, COORD, VD, TEX>, KernelName<kFieldBwdFamily, ATT, COORD, VD, TEX>::value.s}; }
+
+static FieldBwdLaunch select_field_bwd_kernel(const nfi_field_bwd_args* a) {
+  const bool vd = a->ray_features != nullptr, coord = a->g_points != nullptr;
+  return dispatch_texel_att(a->texel_dtype, a->n_attention > 0, [&](auto tex, auto att_c) -> FieldBwdLaunch {
+    constexpr int TEX = decltype(tex)::value;
+    constexpr bool ATT = decltype(att_c)::value;
+    if constexpr (TEX == 0) {     // the view-direction decoder: fp32 texels (checked)
+      if (vd) return coord ? field_bwd_launch<ATT, true, true, 0>() : field_bwd_launch<ATT, false, true, 0>();
+    }
+    return coord ? field_bwd_launch<ATT, true, false, TEX>() : field_bwd_launch<ATT, false, false, TEX>();
+  });
+}
+
+extern "C" const char* nfi_field_bwd_kernel_name(const nfi_field_bwd_args* a) {
+  if (field_bwd_check_call(a)) return nullptr;
+  return select_field_bwd_kernel(a).name;
+}
+
+extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t stream) {
+  int rc = field_bwd_check_call(a);
+  if (rc) return rc;
+  const bool vd = a->ray_features != nullptr;
   hipStream_t s = (hipStream_t)stream;
   const int n_out = a->n_attention > 0 ? 1 + a->n_attention : 4;
   float* image_bwd = reinterpret_cast<float*>(a->workspace);
@@ -1426,15 +1457,7 @@ extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t str
   dim3 grid((unsigned)blocks, (unsigned)a->n_scenes);
   const size_t shmem = vd ? (size_t)(kVdFieldLdsFloats + kVbImageFloats + 4 * kStFloatsVd) * sizeof(float)
                           : (size_t)(kBwdFwdFloats + kBwdImageFloats + 4 * kStFloats) * sizeof(float);
-  const bool att = a->n_attention > 0, coord = a->g_points != nullptr;
-  rc = dispatch_texel_att(a->texel_dtype, att, [&](auto tex, auto att_c) {
-    constexpr int TEX = decltype(tex)::value;
-    constexpr bool ATT = decltype(att_c)::value;
-    if constexpr (TEX == 0) {     // the view-direction decoder: fp32 texels (checked above)
-      if (vd) return coord ? launch_field_bwd<ATT, true, true, 0>(grid, shmem, s, k) : launch_field_bwd<ATT, false, true, 0>(grid, shmem, s, k);
-    }
-    return coord ? launch_field_bwd<ATT, true, false, TEX>(grid, shmem, s, k) : launch_field_bwd<ATT, false, false, TEX>(grid, shmem, s, k);
-  });
+  rc = select_field_bwd_kernel(a).launch(grid, shmem, s, k);
   if (rc) return rc;
   if (binned) {
     const dim3 pgrid((unsigned)((a->points_per_scene + 1023) / 1024), (unsigned)a->n_scenes);

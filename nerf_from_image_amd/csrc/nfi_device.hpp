@@ -1187,8 +1187,8 @@ struct SampleOut {
 // sem_base: null, or global pointer to this wave's [64][A] semantics rows (written for valid points); with SEMP > 0
 // the wave's LDS table [A][SEMP] at the column of this call's point 0 (tile_epilogue).
 // stage: 16 x 36 floats of LDS owned by this wave (feature-tile transpose).
-// prof: null, or 4 cycle accumulators {tile set-up + load issue, load wait + interpolation,
-// transpose + MLP + epilogue, tiles} filled with s_memtime deltas (profiling builds only)
+// prof: null, or 4 cycle accumulators {unused (stays 0), tile set-up + load issue + wait + interpolation,
+// transpose + MLP + epilogue, tiles} filled with cycle-counter deltas (profiling builds only)
 // VD: view-direction decoder; xray = padded per-ray features [rays][kRayFeatPad], ray_idx = this lane's ray.
 // NRM (fused renderer, compute_normals): the sample's unit normal normalize(d sdf / d x) - the decoder's distance
 // differentiated analytically: G = W1'^T (sigmoid(h) * W2'[0]) on 12 split-fp16 MFMAs per tile, times d feature / d axis of the

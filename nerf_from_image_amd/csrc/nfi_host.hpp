@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <cstdio>
+#include <initializer_list>
 #include <type_traits>
 
 extern thread_local char nfi_err_buf[256];          // defined in nfi_kernels.hip
@@ -62,6 +63,32 @@ static auto dispatch_texel_att(int texel_dtype, bool att, F&& f) {
   if (texel_dtype == NFI_TEXEL_BF16) return with_tex(std::integral_constant<int, 1>{});
   return with_tex(std::integral_constant<int, 2>{});
 }
+
+// The canonical name of a kernel instantiation - the template's name with every argument as an integer, in order, e.g.
+// "render_fwd_kernel<0,1,2,0,1,0>" - built at compile time from the arguments the dispatchers instantiate the kernel
+// with (what nfi_render_kernel_name / nfi_field_kernel_name / nfi_field_bwd_kernel_name return: static storage).
+struct KernelNameText { char s[64]; };
+constexpr KernelNameText make_kernel_name(const char* family, std::initializer_list<int> args) {
+  KernelNameText t{};
+  int n = 0;
+  for (const char* p = family; *p; ++p) t.s[n++] = *p;
+  t.s[n++] = '<';
+  bool first = true;
+  for (int v : args) {           // template arguments of the kernels: never negative
+    if (!first) t.s[n++] = ',';
+    first = false;
+    char digits[12] = {};
+    int m = 0;
+    do { digits[m++] = (char)('0' + v % 10); v /= 10; } while (v);
+    while (m) t.s[n++] = digits[--m];
+  }
+  t.s[n++] = '>';
+  t.s[n] = 0;
+  return t;
+}
+// Family: a constexpr char array of static storage (the template's name)
+template <const char* Family, int... Args>
+struct KernelName { static constexpr KernelNameText value = make_kernel_name(Family, {Args...}); };
 
 static inline int check_field_common(const void* texels, int plane_res, int texel_dtype, const float* image, int A,
                               const float* att, int use_sdf, const float* beta, const float* alpha, int layout = 0) {

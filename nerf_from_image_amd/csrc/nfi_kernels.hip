@@ -542,36 +542,56 @@ __global__ __launch_bounds__(256) void field_query_kernel(FieldKernelParams k) {
   }
 }
 
-extern "C" int nfi_field_query_fwd(const nfi_field_args* a, nfi_stream_t stream) {
+// The argument rules of nfi_field_query_fwd (pointers against null, integers against limits: nothing is dereferenced)
+static int field_check_call(const nfi_field_args* a) {
   REQUIRE(a && a->points && a->sigma && a->rgb, "field_query: null pointer");
   REQUIRE(a->n_scenes > 0 && a->points_per_scene > 0, "field_query: bad shape");
   int rc = check_field_common(a->texels, a->plane_res, a->texel_dtype, a->decoder_image, a->n_attention,
-                               a->attention_values, a->use_sdf, a->beta, a->alpha, a->texel_layout);
+                              a->attention_values, a->use_sdf, a->beta, a->alpha, a->texel_layout);
   if (rc) return rc;
   REQUIRE(!a->semantics || a->n_attention > 0, "field_query: semantics need attention_values > 0");
-  // (semantics rows are stored per valid point only: field_wave guards them with the lane's valid flag)
-  FieldKernelParams k{a->points, a->points_per_scene, a->texels, a->plane_res, a->texel_dtype, a->decoder_image,
-                      a->n_attention, a->attention_values, a->use_sdf, a->beta, a->alpha, a->scene_range,
-                      a->sigma, a->rgb, a->sdf, a->semantics, a->outside, a->ray_features, a->samples_per_ray, a->texel_layout};
   REQUIRE(!a->ray_features || (a->samples_per_ray > 0 && a->points_per_scene % a->samples_per_ray == 0),
           "field_query: with ray_features, points_per_scene must be a multiple of samples_per_ray");
   REQUIRE(a->mlp_precision == 0 || (a->mlp_precision == 1 && !a->ray_features),
           "field_query: mlp_precision must be 0 (exact fp32) or 1 (split fp16; not with the view-direction decoder)");
+  return NFI_OK;
+}
+
+// which field_query_kernel instantiation a (validated) call gets, and its canonical name
+using FieldKernel = void (*)(FieldKernelParams);
+struct FieldLaunch { FieldKernel kernel; const char* name; };
+static constexpr char kFieldFamily[] = "field_query_kernel";
+template <int TEX, bool ATT, bool VD = false, int PREC = 0>
+static FieldLaunch field_launch() { return {&field_query_kernel<TEX, ATT, VD, PREC>, KernelName<kFieldFamily, TEX, ATT, VD, PREC>::value.s}; }
+
+static FieldLaunch select_field_kernel(const nfi_field_args* a) {
+  return dispatch_texel_att(a->texel_dtype, a->n_attention > 0, [&](auto tex, auto att_c) -> FieldLaunch {
+    constexpr int TEX = decltype(tex)::value;
+    constexpr bool ATT = decltype(att_c)::value;
+    if (a->ray_features) return field_launch<TEX, ATT, true>();
+    if (a->mlp_precision == 1) return field_launch<TEX, ATT, false, 1>();
+    return field_launch<TEX, ATT>();
+  });
+}
+
+extern "C" const char* nfi_field_kernel_name(const nfi_field_args* a) {
+  if (field_check_call(a)) return nullptr;
+  return select_field_kernel(a).name;
+}
+
+extern "C" int nfi_field_query_fwd(const nfi_field_args* a, nfi_stream_t stream) {
+  int rc = field_check_call(a);
+  if (rc) return rc;
+  // (semantics rows are stored per valid point only: field_wave guards them with the lane's valid flag)
+  FieldKernelParams k{a->points, a->points_per_scene, a->texels, a->plane_res, a->texel_dtype, a->decoder_image,
+                      a->n_attention, a->attention_values, a->use_sdf, a->beta, a->alpha, a->scene_range,
+                      a->sigma, a->rgb, a->sdf, a->semantics, a->outside, a->ray_features, a->samples_per_ray, a->texel_layout};
   int64_t chunks = (a->points_per_scene + 63) / 64;
   int64_t blocks = (chunks + 3) / 4;
   if (blocks > 2048) blocks = 2048;
   dim3 grid((unsigned)blocks, (unsigned)a->n_scenes);
   hipStream_t s = (hipStream_t)stream;
-  const bool att = a->n_attention > 0;
-  using FieldKernel = void (*)(FieldKernelParams);
-  const FieldKernel kernel = dispatch_texel_att(a->texel_dtype, att, [&](auto tex, auto att_c) -> FieldKernel {
-    constexpr int TEX = decltype(tex)::value;
-    constexpr bool ATT = decltype(att_c)::value;
-    if (a->ray_features) return field_query_kernel<TEX, ATT, true>;
-    if (a->mlp_precision == 1) return field_query_kernel<TEX, ATT, false, 1>;
-    return field_query_kernel<TEX, ATT>;
-  });
-  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, k);
+  hipLaunchKernelGGL(select_field_kernel(a).kernel, grid, dim3(256), 0, s, k);
   return check_launch("field_query_fwd");
 }
 
@@ -2003,6 +2023,11 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_wide_kernel(RenderKernelP
               const float sa = wave_sum((ws[0] * (float)row[0] + ws[1] * (float)row[64]) + (ws[2] * (float)row[128] + ws[3] * (float)row[192]));
               if (lane == a) mine = sa * (1.0f / 65535.0f);
             }
+            // The unorm16 roundings of a sample's A probabilities do not cancel: their sum is off by up to A / 2 steps, and
+            // on a ray that one sample dominates so is the map's (2.1e-5 seen at A = 14, 1.07e-4 possible).  Scale the map so
+            // that it sums to the mask, as the fp32 table's does: entry a moves by (its share of the mask) x that error.
+            const float tot = wave_sum(mine);
+            if (tot > 0.0f) mine *= o.mask / tot;
             if (lane < k.A) k.semantics[(size_t)ray * k.A + lane] = mine;
           }
         }
@@ -2344,12 +2369,28 @@ static RenderKernelParams render_kernel_params(const nfi_render_args* a, const R
 using RenderKernel = void (*)(RenderKernelParams);
 struct RenderLaunch {
   RenderKernel kernel;
+  const char* name;                           // canonical name of the instantiation (nfi_render_kernel_name)
   int occ;                                    // workgroups of 4 waves per CU it is compiled for: the persistent grid is 256 CUs x occ
   size_t max_lds;                             // the largest dynamic LDS it is ever launched with (0: it uses none)
   int (*raise_lds)(size_t, const char*);      // ensure_dynamic_lds of this kernel
 };
-template <auto Kernel>
-static RenderLaunch render_launch(int occ = NFI_RENDER_OCC, size_t max_lds = 0) { return {Kernel, occ, max_lds, &ensure_dynamic_lds<Kernel>}; }
+// one maker per kernel family: the kernel pointer and its name come from the SAME template arguments
+static constexpr char kFwdFamily[] = "render_fwd_kernel", kWideFamily[] = "render_fwd_wide_kernel", kLongFamily[] = "render_fwd_long_kernel";
+template <int TEX, bool ATT, int OCC, int MODE, int PREC, bool VD = false>
+static RenderLaunch fwd_launch(size_t max_lds = 0) {
+  constexpr auto kernel = &render_fwd_kernel<TEX, ATT, OCC, MODE, PREC, VD>;
+  return {kernel, KernelName<kFwdFamily, TEX, ATT, OCC, MODE, PREC, VD>::value.s, OCC, max_lds, &ensure_dynamic_lds<kernel>};
+}
+template <int TEX, bool ATT, int MODE, int PREC, bool VD = false>
+static RenderLaunch wide_launch(size_t max_lds = 0) {
+  constexpr auto kernel = &render_fwd_wide_kernel<TEX, ATT, MODE, PREC, VD, NFI_RENDER_OCC>;
+  return {kernel, KernelName<kWideFamily, TEX, ATT, MODE, PREC, VD, NFI_RENDER_OCC>::value.s, NFI_RENDER_OCC, max_lds, &ensure_dynamic_lds<kernel>};
+}
+template <int TEX, bool ATT, int PREC, bool VD = false>
+static RenderLaunch long_launch() {
+  constexpr auto kernel = &render_fwd_long_kernel<TEX, ATT, PREC, VD>;
+  return {kernel, KernelName<kLongFamily, TEX, ATT, PREC, VD>::value.s, NFI_RENDER_OCC, 0, &ensure_dynamic_lds<kernel>};
+}
 
 // THE rule "which kernel does a (validated) render call get": first match wins.  Every condition that is a template
 // argument is an `if constexpr`, so only kernels that some call can reach are instantiated.
@@ -2368,45 +2409,53 @@ static RenderLaunch select_render_kernel(const nfi_render_args* a, const RenderF
     constexpr int TEX = decltype(tex)::value;
     constexpr bool ATT = decltype(att)::value;
     if (lng) {     // 128 < S <= 512: taps and stash are run-time switches of this kernel
-      if (vd) return render_launch<render_fwd_long_kernel<TEX, ATT, 0, true>>();
-      if (f.strict) return render_launch<render_fwd_long_kernel<0, ATT, 0>>();
-      return render_launch<render_fwd_long_kernel<TEX, ATT, 1>>();
+      if (vd) return long_launch<TEX, ATT, 0, true>();
+      if (f.strict) return long_launch<0, ATT, 0>();
+      return long_launch<TEX, ATT, 1>();
     }
     if (vd) {      // the view-direction decoder runs in exact fp32 (PREC 0); its one kernel without maps has the taps, used or not
       if constexpr (TEX == 0) {      // the maps exist for fp32 texels (checked); the distance of the normals is row 0 of the second layer here too
-        if (normals) return wide ? render_launch<render_fwd_wide_kernel<0, ATT, kRenderNormals, 0, true>>(OCC, kSemLdsMaxWide)
-                                 : render_launch<render_fwd_kernel<0, ATT, OCC, kRenderNormals, 0, true>>(OCC, kSemLdsMax);
-        if (f.extra) return wide ? render_launch<render_fwd_wide_kernel<0, ATT, kRenderExtra, 0, true>>(OCC, kSemLdsMaxWide)
-                                 : render_launch<render_fwd_kernel<0, ATT, OCC, kRenderExtra, 0, true>>(OCC, kSemLdsMax);
+        if (normals) return wide ? wide_launch<0, ATT, kRenderNormals, 0, true>(kSemLdsMaxWide)
+                                 : fwd_launch<0, ATT, OCC, kRenderNormals, 0, true>(kSemLdsMax);
+        if (f.extra) return wide ? wide_launch<0, ATT, kRenderExtra, 0, true>(kSemLdsMaxWide)
+                                 : fwd_launch<0, ATT, OCC, kRenderExtra, 0, true>(kSemLdsMax);
       }
-      return wide ? render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderTaps, 0, true>>()
-                  : render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderTaps, 0, true>>();
+      return wide ? wide_launch<TEX, ATT, kRenderTaps, 0, true>()
+                  : fwd_launch<TEX, ATT, OCC, kRenderTaps, 0, true>();
     }
     if (wide) {    // 64 < S <= 128 per pass
-      if (normals) return render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderNormals, 1>>(OCC, kSemLdsMaxWide);
-      if (f.extra) return render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderExtra, 1>>(OCC, kSemLdsMaxWide);
-      if (f.term) return render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderTerm, 1>>();
-      if (f.any_tap && f.strict) return render_launch<render_fwd_wide_kernel<0, ATT, kRenderTaps, 0>>();
-      if (f.any_tap) return render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderTaps, 1>>();
-      if (f.strict) return render_launch<render_fwd_wide_kernel<0, ATT, kRenderPlain, 0>>();
+      if (normals) return wide_launch<TEX, ATT, kRenderNormals, 1>(kSemLdsMaxWide);
+      if (f.extra) return wide_launch<TEX, ATT, kRenderExtra, 1>(kSemLdsMaxWide);
+      if (f.term) return wide_launch<TEX, ATT, kRenderTerm, 1>();
+      if (f.any_tap && f.strict) return wide_launch<0, ATT, kRenderTaps, 0>();
+      if (f.any_tap) return wide_launch<TEX, ATT, kRenderTaps, 1>();
+      if (f.strict) return wide_launch<0, ATT, kRenderPlain, 0>();
       // (fp16 texels, 128 + 128, at THREE workgroups per CU - 168 registers, ~40 scratch reloads per ray outside the field
       //  tiles - was measured in round 4 and is slower: 1.387 vs 1.300 ms chairs-like, 2.249 vs 2.156 ms every ray hits, images
       //  identical (profiles/r4/wide_fp16_three_workgroups.log); unlike the 64 + 64 kernel, whose fp16 form gains 8 % from the
       //  third workgroup, a 256-sample ray's texel footprint makes 50 % more rays in flight cost more in the L2 than they hide)
-      return render_launch<render_fwd_wide_kernel<TEX, ATT, kRenderPlain, 1>>();
+      return wide_launch<TEX, ATT, kRenderPlain, 1>();
     }
-    if (normals) return render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderNormals, 1>>(OCC, kSemLdsMax);
-    if (f.extra) return render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderExtra, 1>>(OCC, kSemLdsMax);
-    if (f.term) return render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderTerm, 1>>();
-    if (prof) return render_launch<render_fwd_kernel<0, ATT, OCC, kRenderProf, 1>>();
-    if (f.any_tap && f.strict) return render_launch<render_fwd_kernel<0, ATT, OCC, kRenderTaps, 0>>();
-    if (f.any_tap) return render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderTaps, 1>>();
-    if (f.strict) return render_launch<render_fwd_kernel<0, ATT, OCC, kRenderPlain, 0>>();
+    if (normals) return fwd_launch<TEX, ATT, OCC, kRenderNormals, 1>(kSemLdsMax);
+    if (f.extra) return fwd_launch<TEX, ATT, OCC, kRenderExtra, 1>(kSemLdsMax);
+    if (f.term) return fwd_launch<TEX, ATT, OCC, kRenderTerm, 1>();
+    if (prof) return fwd_launch<0, ATT, OCC, kRenderProf, 1>();
+    if (f.any_tap && f.strict) return fwd_launch<0, ATT, OCC, kRenderTaps, 0>();
+    if (f.any_tap) return fwd_launch<TEX, ATT, OCC, kRenderTaps, 1>();
+    if (f.strict) return fwd_launch<0, ATT, OCC, kRenderPlain, 0>();
     // (16-bit texel storage, plain inference: the texels stay packed - 168 registers - and THREE blocks per CU fit without a
     //  spill: 0.705 vs 0.756 ms at 8 x 128^2, every ray hits 1.040 vs 1.174 ms)
-    if constexpr (TEX != 0) return render_launch<render_fwd_kernel<TEX, ATT, 3, kRenderPlain, 1>>(3);
-    else return render_launch<render_fwd_kernel<TEX, ATT, OCC, kRenderPlain, 1>>();
+    if constexpr (TEX != 0) return fwd_launch<TEX, ATT, 3, kRenderPlain, 1>();
+    else return fwd_launch<TEX, ATT, OCC, kRenderPlain, 1>();
   });
+}
+
+// which kernel nfi_render_fwd launches for *a: the same rules, the same selector, no HIP call (nothing is dereferenced)
+extern "C" const char* nfi_render_kernel_name(const nfi_render_args* a) {
+  if (render_check_call(a)) return nullptr;
+  const RenderFlags f = render_flags(a);
+  if (render_check_variant(a, f)) return nullptr;
+  return select_render_kernel(a, f).name;
 }
 
 extern "C" int nfi_render_fwd(const nfi_render_args* a, nfi_stream_t stream) {

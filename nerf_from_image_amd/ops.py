@@ -411,8 +411,8 @@ def render_fwd(cam2world, focal, height, width, num_samples, texels, decoder_ima
     texels) from the SAME launch.
     Precision of 'semantics': with num_samples <= 64 the per-sample probabilities wait for the compositing in fp32; the
     64 < num_samples <= 128 kernel parks them as unorm16 (|error| <= 2^-17 = 7.7e-6 per sample, values below that become
-    0), so its map is within 1e-5 of the reference's instead of 1e-6 (tests/test_hip_parity.py,
-    test_wide_kernel_semantics_table_precision)."""
+    0) and scales the composited map to sum to the mask, so its map is within 1e-5 of the reference's instead of 1e-6
+    (tests/test_hip_parity.py, test_wide_kernel_semantics_table_precision; tests/test_kernel_matrix.py for A = 14)."""
     cam2world = _f32c(cam2world, 'tform_cam2world')
     B = cam2world.shape[0]
     dev = cam2world.device
