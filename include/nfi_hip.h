@@ -428,7 +428,10 @@ typedef struct nfi_render_args {
   float* t_coarse; float* sigma_coarse; float* rgb_coarse;   /* [N,S], [N,S], [N,S,3] */
   float* t_fine; float* sigma_fine; float* rgb_fine;
   float* t_sorted; float* weights; int32_t* perm;            /* [N,2S] */
-  /* workspace: nfi_render_workspace_bytes(n_scenes*height*width) bytes */
+  /* workspace: nfi_render_workspace_bytes(n_scenes*height*width) bytes, 4-byte aligned, contents arbitrary (the ray set-up
+   * writes every cell it or the render kernel reads).  Layout: a 576-byte header (the three reduction cells of the ray
+   * set-up first), ray_origins and ray_directions [N,3], near and far [N], hit [N] bytes padded to 64, and behind those the
+   * set-up's per-block partial reductions (internal). */
   void* workspace; size_t workspace_bytes;
   /* 1: rays whose line misses the scene cube inflated by 1e-4 skip both passes (exact:
    * every sample of such a ray is outside the cube, sigma==0).  0: evaluate every ray. */

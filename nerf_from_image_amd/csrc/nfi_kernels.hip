@@ -300,10 +300,18 @@ extern "C" int nfi_decoder_pack_viewdir(const float* w1, const float* b1, const 
 // reduce[0] = ~key(min near | hit) (so that zero-initialised memory + atomicMax works),
 // reduce[1] = key(max far | hit), reduce[2] = hit count.
 // Per-thread accumulators (a thread may have seen several rays): kmin/kmax keys as above, cnt = its hit count.
-// The three atomics per block all go to the same three addresses, and same-address device atomics serialise at
-// ~12 ns on this chip, so the ray kernels run a grid-stride loop over at most kRayBlocks blocks.
-constexpr int kRayBlocks = 256;
-__device__ __forceinline__ void block_reduce_keys(uint32_t kmin, uint32_t kmax, uint32_t cnt, uint32_t* reduce) {
+// block_reduce_keys leaves the block's totals in thread 0's arguments.  From there
+//   raygen_kernel (the render's ray set-up) stores them as its block's RayPartial, and the one-block raygen_finish_kernel
+//     behind it reduces the partials into reduce[] with plain stores: no cell has to be clear beforehand, no atomic;
+//   slab_kernel (nfi_near_far) sends them to the three cells with atomics.  They all go to the same three addresses, and
+//     same-address device atomics serialise at ~12 ns on this chip, so it runs a grid-stride loop over at most kSlabBlocks
+//     blocks.
+// kRayBlocks bounds raygen_kernel's grid, hence the partials (one thread per ray up to 262 144 rays, a grid-stride loop
+// beyond).
+constexpr int kSlabBlocks = 256;
+constexpr int kRayBlocks = 1024;
+struct RayPartial { uint32_t kmin, kmax, cnt, pad; };
+__device__ __forceinline__ void block_reduce_keys(uint32_t& kmin, uint32_t& kmax, uint32_t& cnt) {
   __shared__ uint32_t s_min[4], s_max[4], s_cnt[4];
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
@@ -322,18 +330,13 @@ __device__ __forceinline__ void block_reduce_keys(uint32_t kmin, uint32_t kmax, 
       kmax = s_max[w] > kmax ? s_max[w] : kmax;
       cnt += s_cnt[w];
     }
-    if (cnt) {
-      atomicMax(&reduce[0], kmin);
-      atomicMax(&reduce[1], kmax);
-      atomicAdd(&reduce[2], cnt);
-    }
   }
 }
 
 struct RaygenOut {
   float* ro; float* rd;          // [N,3] or null
   float* near_raw; float* far_raw; uint8_t* hit;  // [N] or null (null near_raw -> no slab test)
-  uint32_t* reduce;
+  RayPartial* partial;           // [gridDim.x] (with near_raw)
   float scene_range;
 };
 
@@ -366,7 +369,10 @@ __global__ __launch_bounds__(256) void raygen_kernel(CameraParams cam, int n_sce
       }
     }
   }
-  if (out.near_raw) block_reduce_keys(kmin, kmax, cnt, out.reduce);
+  if (out.near_raw) {
+    block_reduce_keys(kmin, kmax, cnt);
+    if (threadIdx.x == 0) out.partial[blockIdx.x] = RayPartial{kmin, kmax, cnt, 0u};
+  }
 }
 
 __global__ __launch_bounds__(256) void slab_kernel(const float* __restrict__ ro, const float* __restrict__ rd, int64_t n,
@@ -391,7 +397,12 @@ __global__ __launch_bounds__(256) void slab_kernel(const float* __restrict__ ro,
       ++cnt;
     }
   }
-  block_reduce_keys(kmin, kmax, cnt, reduce);
+  block_reduce_keys(kmin, kmax, cnt);
+  if (threadIdx.x == 0 && cnt) {
+    atomicMax(&reduce[0], kmin);
+    atomicMax(&reduce[1], kmax);
+    atomicAdd(&reduce[2], cnt);
+  }
 }
 
 __global__ __launch_bounds__(256) void finish_planes_kernel(const float* __restrict__ near_raw,
@@ -426,7 +437,7 @@ extern "C" int nfi_near_far(const nfi_near_far_args* a, nfi_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(a->reduce, 0, 16, s) != hipSuccess) return fail(NFI_ERR_LAUNCH, "near_far: memset failed");
   unsigned blocks = (unsigned)((a->n_rays + 255) / 256);
-  hipLaunchKernelGGL(slab_kernel, dim3(std::min<unsigned>(blocks, kRayBlocks)), dim3(256), 0, s, a->ray_origins, a->ray_directions, a->n_rays,
+  hipLaunchKernelGGL(slab_kernel, dim3(std::min<unsigned>(blocks, kSlabBlocks)), dim3(256), 0, s, a->ray_origins, a->ray_directions, a->n_rays,
                      a->scene_range, a->near_raw, a->far_raw, a->hit, a->reduce);
   if (a->near_plane && a->far_plane)
     hipLaunchKernelGGL(finish_planes_kernel, dim3(blocks), dim3(256), 0, s, a->near_raw, a->far_raw, a->hit, a->reduce,
@@ -2201,8 +2212,8 @@ __global__ __launch_bounds__(256, NFI_RENDER_OCC) void render_fwd_long_kernel(Re
 }
 
 // The render workspace: [RenderWorkspaceHeader][ro, rd: 3n floats each][near_raw, far_raw: n floats each][hit: n bytes,
-// padded to 64].  The header is what ONE memset of the ray set-up clears; callers read reduce[] from it (the first
-// three cells of the workspace).
+// padded to 64][kRayBlocks RayPartial: the per-block partials of the ray set-up's reduction].  The header is what
+// raygen_finish_kernel writes, every cell of it; callers read reduce[] from it (the first three cells of the workspace).
 struct RenderWorkspaceHeader {
   uint32_t reduce[3];            // the batch-wide miss-fill of the ray set-up: ~key(min near), key(max far), hit count
   uint32_t counter;              // the device-wide work counter (RenderKernelParams::counter)
@@ -2212,13 +2223,38 @@ struct RenderWorkspaceHeader {
 static_assert(sizeof(RenderWorkspaceHeader) == 64 + 8 * 64 && offsetof(RenderWorkspaceHeader, xcd_counter) == 64,
               "the render workspace header is read from Python and by the kernels' 16-dword counter stride");
 
-extern "C" size_t nfi_render_workspace_bytes(int64_t n_rays) {
+// the documented prefix of the workspace: header and ray arrays
+static size_t render_workspace_prefix_bytes(int64_t n_rays) {
   size_t n = (size_t)n_rays;
   return sizeof(RenderWorkspaceHeader) + n * 8 * sizeof(float) + ((n + 63) & ~(size_t)63);
 }
 
+extern "C" size_t nfi_render_workspace_bytes(int64_t n_rays) {
+  return render_workspace_prefix_bytes(n_rays) + kRayBlocks * sizeof(RayPartial);
+}
+
+// The tail of the ray set-up, one block behind raygen_kernel in the stream: reduce[0..2] from the blocks' partials (max,
+// max, sum: any order gives the same cells) and zeros in the work counters - plain stores to every cell of the header, so
+// a workspace straight from the allocator needs no clearing.
+__global__ __launch_bounds__(256) void raygen_finish_kernel(const RayPartial* __restrict__ partial, int n_partials,
+                                                            RenderWorkspaceHeader* __restrict__ head) {
+  uint32_t kmin = 0u, kmax = 0u, cnt = 0u;
+  for (int i = threadIdx.x; i < n_partials; i += blockDim.x) {
+    const RayPartial p = partial[i];
+    kmin = p.kmin > kmin ? p.kmin : kmin;
+    kmax = p.kmax > kmax ? p.kmax : kmax;
+    cnt += p.cnt;
+  }
+  block_reduce_keys(kmin, kmax, cnt);
+  uint32_t* cells = reinterpret_cast<uint32_t*>(head);
+  for (int i = 3 + threadIdx.x; i < (int)(sizeof(RenderWorkspaceHeader) / sizeof(uint32_t)); i += blockDim.x) cells[i] = 0u;
+  if (threadIdx.x == 0) { head->reduce[0] = kmin; head->reduce[1] = kmax; head->reduce[2] = cnt; }
+}
+
 // workspace carve + ray set-up shared by nfi_render_setup and nfi_render_fwd
-struct RenderWorkspace { RenderWorkspaceHeader* head; float* ro; float* rd; float* near_raw; float* far_raw; uint8_t* hit; int64_t n; };
+struct RenderWorkspace {
+  RenderWorkspaceHeader* head; float* ro; float* rd; float* near_raw; float* far_raw; uint8_t* hit; RayPartial* partial; int64_t n;
+};
 
 static int render_carve(const nfi_render_args* a, RenderWorkspace& w) {
   REQUIRE(a && a->cam2world && a->workspace, "render: null pointer");
@@ -2233,17 +2269,18 @@ static int render_carve(const nfi_render_args* a, RenderWorkspace& w) {
   w.near_raw = rays + 6 * n;
   w.far_raw = rays + 7 * n;
   w.hit = a->hit ? a->hit : reinterpret_cast<uint8_t*>(rays + 8 * n);
+  w.partial = reinterpret_cast<RayPartial*>(reinterpret_cast<char*>(a->workspace) + render_workspace_prefix_bytes(n));
   return NFI_OK;
 }
 
 static int render_setup(const nfi_render_args* a, const RenderWorkspace& w, hipStream_t s) {
-  // ONE memset clears the reduction cells and the counters
-  if (hipMemsetAsync(w.head, 0, sizeof(RenderWorkspaceHeader), s) != hipSuccess) return fail(NFI_ERR_LAUNCH, "render: memset failed");
   const int full_h = a->full_height > 0 ? a->full_height : a->height;
   REQUIRE(a->row_offset >= 0 && a->row_offset + a->height <= full_h, "render: row window outside the image");
   CameraParams cam{a->cam2world, a->focal, a->bbox, a->focal ? a->center : nullptr, full_h, a->width, 1, a->height, a->row_offset};
-  RaygenOut rout{w.ro, w.rd, w.near_raw, w.far_raw, w.hit, w.head->reduce, a->scene_range};
-  hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)std::min<int64_t>((w.n + 255) / 256, kRayBlocks)), dim3(256), 0, s, cam, a->n_scenes, rout);
+  RaygenOut rout{w.ro, w.rd, w.near_raw, w.far_raw, w.hit, w.partial, a->scene_range};
+  const int blocks = (int)std::min<int64_t>((w.n + 255) / 256, kRayBlocks);
+  hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)blocks), dim3(256), 0, s, cam, a->n_scenes, rout);
+  hipLaunchKernelGGL(raygen_finish_kernel, dim3(1), dim3(256), 0, s, w.partial, blocks, w.head);
   return NFI_OK;
 }
 
