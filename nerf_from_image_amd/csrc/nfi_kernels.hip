@@ -1398,10 +1398,7 @@ __device__ __forceinline__ float uniform_f32(float v) {
   return bits2f((uint32_t)__builtin_amdgcn_readfirstlane((int)f2bits(v)));
 }
 
-// Persistent kernel: one wave per ray, rays handed out by one device-scope counter (scene-major,
-// so the chip works on one scene's 25 MB of texels at a time).  The ray index two steps ahead is
-// being fetched and the next ray's inputs are loaded while the current ray is marched.
-// OCC = waves per SIMD the register budget is held to; TAPS = write the optional stage taps.
+// one ray's inputs, as render_fwd_kernel loads them one ray ahead
 struct RayInputs {
   float ox, oy, oz, dx, dy, dz, near, far, noise, u;
   uint32_t hit;
@@ -1417,7 +1414,7 @@ struct RayInputs {
 struct RayQueue {
   const RenderKernelParams& k;
   int lane;
-  uint32_t n_rays, xcd, bsh, bw, bps, n_blocks, q_cur, pos_next, pos_end, batch;
+  uint32_t n_rays, xcd, bsh, bw, bps, n_blocks, q_cur, pos_next, pos_end, batch, tiles_x;
   bool dry;
   __device__ __forceinline__ RayQueue(const RenderKernelParams& kk, int l) : k(kk), lane(l) {
     n_rays = (uint32_t)k.n_scenes * (uint32_t)k.hw;
@@ -1428,6 +1425,7 @@ struct RayQueue {
     n_blocks = bps * (uint32_t)k.n_scenes;
     q_cur = xcd; pos_next = 0; pos_end = 0; dry = false;
     batch = (uint32_t)k.fetch_batch;
+    tiles_x = (uint32_t)k.width >> 3;
   }
   __device__ __forceinline__ uint32_t ray_at(uint32_t q, uint32_t pos) const {
     const uint32_t b = (pos >> (2 * bsh)) * 8u + q;
@@ -1455,6 +1453,16 @@ struct RayQueue {
     }
     if (dry) return n_rays;
     return ray_at(q_cur, pos_next++);
+  }
+  // position of the single queue -> ray id.  Tile order: consecutive positions walk 8x8 pixel tiles, so the few thousand
+  // rays in flight at any time cover a compact image region (a compact part of the three planes) instead of a band of
+  // scanlines - better L2/Infinity-Cache reuse of the gather stream.  (A ray id of the per-XCD queues passes through.)
+  __device__ __forceinline__ uint32_t ray_of(uint32_t pos) const {
+    if (k.xcd_blocks || !k.tile_order) return pos;
+    const uint32_t scene = pos / (uint32_t)k.hw, p = pos - scene * (uint32_t)k.hw;
+    const uint32_t tile = p >> 6, in = p & 63u;
+    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    return scene * (uint32_t)k.hw + ((ty << 3) + (in >> 3)) * (uint32_t)k.width + (tx << 3) + (in & 7u);
   }
 };
 
@@ -1504,6 +1512,92 @@ __device__ __forceinline__ void composite_coords(const Slab& slab, const float (
   if (lane == 0) { out3[0] = cx; out3[1] = cy; out3[2] = cz; }
 }
 
+// ---- what the three persistent render kernels share around their per-ray pipelines ----
+
+// decoder image -> LDS: the fp32 fragments, or (PREC == 1) the fp16 fragments overlaying the fp32 fragment area with the
+// biases staying where they are; ends with the workgroup barrier
+template <int PREC, int kImg>
+__device__ __forceinline__ void stage_decoder_image(float* lds, const float* image) {
+  if (PREC == 1) {
+    for (int i = threadIdx.x; i < kB1F; i += blockDim.x) lds[i] = image[kW1H + i];
+    for (int i = kB1F + threadIdx.x; i < kLdsImageFloats; i += blockDim.x) lds[i] = image[i];
+  } else {
+    for (int i = threadIdx.x; i < kImg; i += blockDim.x) lds[i] = image[i];
+  }
+  __syncthreads();
+}
+
+// a wave moves on to another scene: the scene's texel buffer descriptor, and its attention rows into the wave's vf
+template <int TEX>
+__device__ __forceinline__ void enter_scene(FieldParams& P, const RenderKernelParams& k, float* vf, int scene, int lane) {
+  const size_t tb = TEX == 0 ? 128 : 64;
+  const char* tex_scene = reinterpret_cast<const char*>(k.texels) + (size_t)scene * 3 * k.res * k.res * tb;
+  P.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(tex_scene), 0, (int)P.scene_bytes, 0x00020000);
+  wave_lds_fence();
+  {
+    int c = lane & 3, row = lane >> 2;
+    float v = 0.0f;
+    if (k.att && c < 3 && row >= 1 && row <= k.A) v = k.att[((size_t)scene * k.A + (row - 1)) * 3 + c];
+    vf[lane] = v;
+  }
+  wave_lds_fence();
+}
+
+// a ray's five results (the caller picks the lane, and the place: see the work fetch of render_fwd_kernel)
+__device__ __forceinline__ void store_pixel(const RenderKernelParams& k, uint32_t ray, float r, float g, float b, float depth,
+                                            float mask) {
+  k.rgb[(size_t)ray * 3] = r; k.rgb[(size_t)ray * 3 + 1] = g; k.rgb[(size_t)ray * 3 + 2] = b;
+  k.depth[ray] = depth; k.mask[ray] = mask;
+}
+
+// one sample's entry of the optional per-sample taps (coarse or fine; entry i of the ray-major arrays)
+__device__ __forceinline__ void store_sample_tap(float* t_out, float* sigma_out, float* rgb_out, size_t i, float t, float sigma,
+                                                 float r, float g, float b) {
+  if (t_out) t_out[i] = t;
+  if (sigma_out) sigma_out[i] = sigma;
+  if (rgb_out) { float* q = rgb_out + i * 3; q[0] = r; q[1] = g; q[2] = b; }
+}
+
+// the composite weights and the depths in merged order: n entries per ray, element e = slot * 64 + lane
+template <int NS, class Slab>
+__device__ __forceinline__ void store_sorted_taps(const RenderKernelParams& k, const Slab& slab, const float (&w)[NS], uint32_t ray,
+                                                  int n, int lane) {
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    const int e = j * 64 + lane;
+    if (e < n) {
+      if (k.weights) k.weights[(size_t)ray * n + e] = w[j];
+      if (k.t_sorted) k.t_sorted[(size_t)ray * n + e] = slab.srt[0][e];
+    }
+  }
+}
+
+// kRenderExtra / kRenderNormals, a ray whose line stays outside the scene cube: its composited attribute maps
+template <bool NRM>
+__device__ __forceinline__ void zero_missed_maps(const RenderKernelParams& k, uint32_t ray, int lane, float bg) {
+  if (k.coords && lane < 3) k.coords[(size_t)ray * 3 + lane] = 0.0f;
+  if (k.semantics && lane < k.A) k.semantics[(size_t)ray * k.A + lane] = 0.0f;
+  if (NRM && lane < 3) k.normals[(size_t)ray * 3 + lane] = bg;      // sum w n + (1 - mask) on a white background
+}
+
+// training stash, a ray whose line stays outside the scene cube: an all-zero row - its composite backward is exactly
+// zero and its points (the ray origin) carry no gradient
+__device__ __forceinline__ void zero_stash_row(const RenderKernelParams& k, uint32_t ray, int S, int lane) {
+  for (int e = lane; e < S; e += 64) {
+    const size_t zs = (size_t)ray * (size_t)k.tap_stride + e;
+    k.t_coarse[zs] = 0.0f; k.sigma_coarse[zs] = 0.0f;
+    float* q = k.rgb_coarse + zs * 3; q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
+    if (k.fine) {
+      k.t_fine[zs] = 0.0f; k.sigma_fine[zs] = 0.0f;
+      q = k.rgb_fine + zs * 3; q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
+    }
+  }
+}
+
+// Persistent kernel, S <= 64 samples per pass: one wave per ray, rays handed out by a RayQueue (scene-major, so the chip
+// works on one scene's 25 MB of texels at a time).  The ray index two steps ahead is being fetched and the next ray's
+// inputs are loaded (RayInputs) while the current ray is marched.
+// OCC = waves per SIMD the register budget is held to; MODE = one of the kRender... variants above.
 template <int TEX, bool ATT, int OCC, int MODE, int PREC, bool VD = false>
 __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams k) {
   constexpr bool TAPS = MODE == kRenderTaps, PROF = MODE == kRenderProf, TERM = MODE == kRenderTerm;
@@ -1516,14 +1610,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
   if constexpr (NRM) stage_normal_operands(nfi_dyn_lds, k.image, VD ? kVdW1F : kW1F, VD ? kVdW2 : kW2F);
   ClockProbe clock;
   clock.start(k);
-  if (PREC == 1) {
-    // fp16 fragments overlay the fp32 fragment area; biases stay where they are
-    for (int i = threadIdx.x; i < kB1F; i += blockDim.x) lds[i] = k.image[kW1H + i];
-    for (int i = kB1F + threadIdx.x; i < kLdsImageFloats; i += blockDim.x) lds[i] = k.image[i];
-  } else {
-    for (int i = threadIdx.x; i < kImg; i += blockDim.x) lds[i] = k.image[i];
-  }
-  __syncthreads();
+  stage_decoder_image<PREC, kImg>(lds, k.image);
   const int lane = lane_id();
   const int wave = threadIdx.x >> 6;
   WaveSlab& slab = slabs[wave];
@@ -1532,19 +1619,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
   const bool valid = lane < S;
   const float fill_near = ordered_key_inv(~k.reduce[0]), fill_far = ordered_key_inv(k.reduce[1]);
   const float bg = k.white ? 1.0f : 0.0f;
-  const size_t tb = TEX == 0 ? 128 : 64;
   const uint32_t n_rays = (uint32_t)k.n_scenes * (uint32_t)k.hw;
-  // queue position -> ray id.  Tile order: consecutive positions walk 8x8 pixel tiles, so the few
-  // thousand rays in flight at any time cover a compact image region (a compact part of the three
-  // planes) instead of a band of scanlines - better L2/Infinity-Cache reuse of the gather stream.
-  const uint32_t tiles_x = (uint32_t)k.width >> 3;
-  auto ray_of = [&](uint32_t pos) -> uint32_t {
-    if (k.xcd_blocks || !k.tile_order) return pos;
-    const uint32_t scene = pos / (uint32_t)k.hw, p = pos - scene * (uint32_t)k.hw;
-    const uint32_t tile = p >> 6, in = p & 63u;
-    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    return scene * (uint32_t)k.hw + ((ty << 3) + (in >> 3)) * (uint32_t)k.width + (tx << 3) + (in & 7u);
-  };
 
   FieldParams P = make_field_params(k.texels, k.res, TEX, k.A, k.use_sdf, k.beta, k.alpha, lds, kImg, k.layout);
   P.vf = vf;
@@ -1582,47 +1657,25 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
   // [6] resample, [7] fine field, [8] merge, [9] composite + store, [10] rays, [11] total
   unsigned long long pc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tk0 = PROF ? __builtin_readcyclecounter() : 0;
-  if (cur < n_rays) load_inputs(ray_of(cur), in);
+  if (cur < n_rays) load_inputs(queue.ray_of(cur), in);
   while (cur < n_rays) {
-    if (nxt < n_rays) load_inputs(ray_of(nxt), pre);
-    const uint32_t ray = ray_of(cur);
+    if (nxt < n_rays) load_inputs(queue.ray_of(nxt), pre);
+    const uint32_t ray = queue.ray_of(cur);
     const uint32_t hitb = in.hit;
     // the ray's five results: stored after the work fetch at the end of the iteration (see there)
     float out_r = bg, out_g = bg, out_b = bg, out_d = 0.0f, out_m = 0.0f;
     if (k.skip_missed && !(hitb & 2)) {
       // the ray's line stays outside the (inflated) scene cube: every sample has sigma == 0
-      if constexpr (EXTRA) {
-        if (k.coords && lane < 3) k.coords[(size_t)ray * 3 + lane] = 0.0f;
-        if (k.semantics && lane < k.A) k.semantics[(size_t)ray * k.A + lane] = 0.0f;
-        if (NRM && lane < 3) k.normals[(size_t)ray * 3 + lane] = bg;      // sum w n + (1 - mask) on a white background
-      }
+      if constexpr (EXTRA) zero_missed_maps<NRM>(k, ray, lane, bg);
       if constexpr (TAPS) {
-        if (k.stash && valid) {
-          // an all-zero row: its composite backward is exactly zero and its points (the ray origin) carry no gradient
-          const size_t zs = (size_t)ray * (size_t)k.tap_stride + lane;
-          k.t_coarse[zs] = 0.0f; k.sigma_coarse[zs] = 0.0f;
-          float* q = k.rgb_coarse + zs * 3; q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
-          if (k.fine) {
-            k.t_fine[zs] = 0.0f; k.sigma_fine[zs] = 0.0f;
-            q = k.rgb_fine + zs * 3; q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
-          }
-        }
+        if (k.stash) zero_stash_row(k, ray, S, lane);
       }
     } else {
       unsigned long long t0 = PROF ? __builtin_readcyclecounter() : 0;
       const int scene = (int)fastdiv(ray, k.div_hw);
       if (scene != cur_scene) {
         cur_scene = scene;
-        const char* tex_scene = reinterpret_cast<const char*>(k.texels) + (size_t)scene * 3 * k.res * k.res * tb;
-        P.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(tex_scene), 0, (int)P.scene_bytes, 0x00020000);
-        wave_lds_fence();
-        {
-          int c = lane & 3, row = lane >> 2;
-          float v = 0.0f;
-          if (k.att && c < 3 && row >= 1 && row <= k.A) v = k.att[((size_t)scene * k.A + (row - 1)) * 3 + c];
-          vf[lane] = v;
-        }
-        wave_lds_fence();
+        enter_scene<TEX>(P, k, vf, scene, lane);
       }
       const float ox = in.ox, oy = in.oy, oz = in.oz, dx = in.dx, dy = in.dy, dz = in.dz;
       float near = in.near, far = in.far;
@@ -1680,11 +1733,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
           if constexpr (NRM) { nfx = q.nx; nfy = q.ny; nfz = q.nz; }
         }
         if constexpr (TAPS) {
-          if (valid) {
-            if (k.t_fine) k.t_fine[rs + lane] = tf;
-            if (k.sigma_fine) k.sigma_fine[rs + lane] = f.sigma;
-            if (k.rgb_fine) { float* q = k.rgb_fine + (rs + lane) * 3; q[0] = f.r; q[1] = f.g; q[2] = f.b; }
-          }
+          if (valid) store_sample_tap(k.t_fine, k.sigma_fine, k.rgb_fine, rs + lane, tf, f.sigma, f.r, f.g, f.b);
         }
         n = 2 * S;
         if (PROF) t4 = __builtin_readcyclecounter();
@@ -1733,22 +1782,13 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
           if (k.far_plane) k.far_plane[ray] = far;
         }
         if (valid) {
-          if (k.t_coarse) k.t_coarse[rs + lane] = tc;
-          if (k.sigma_coarse) k.sigma_coarse[rs + lane] = c.sigma;
-          if (k.rgb_coarse) { float* q = k.rgb_coarse + (rs + lane) * 3; q[0] = c.r; q[1] = c.g; q[2] = c.b; }
+          store_sample_tap(k.t_coarse, k.sigma_coarse, k.rgb_coarse, rs + lane, tc, c.sigma, c.r, c.g, c.b);
           if (k.perm) {
             k.perm[(size_t)ray * n + rank_c] = lane;
             if (k.fine) k.perm[(size_t)ray * n + rank_f] = S + lane;
           }
         }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          int e = j * 64 + lane;
-          if (e < n) {
-            if (k.weights) k.weights[(size_t)ray * n + e] = w[j];
-            if (k.t_sorted) k.t_sorted[(size_t)ray * n + e] = slab.srt[0][e];
-          }
-        }
+        store_sorted_taps<2>(k, slab, w, ray, n, lane);
       }
       wave_lds_fence();  // slab is reused by the next ray
       if (PROF) {
@@ -1760,10 +1800,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
     // every store the wave has in flight.  Here, after the ray's arithmetic and BEFORE its result stores, nothing of this
     // ray is in flight any more (the taps / extra maps of those variants excepted): the wait is the atomic's alone.
     fly = fetch();
-    if (lane == 0) {
-      k.rgb[(size_t)ray * 3] = out_r; k.rgb[(size_t)ray * 3 + 1] = out_g; k.rgb[(size_t)ray * 3 + 2] = out_b;
-      k.depth[ray] = out_d; k.mask[ray] = out_m;
-    }
+    if (lane == 0) store_pixel(k, ray, out_r, out_g, out_b, out_d, out_m);
     in = pre;
     cur = nxt;
     nxt = fly;
@@ -1800,13 +1837,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_wide_kernel(RenderKernelP
   if constexpr (NRM) stage_normal_operands(nfi_dyn_lds, k.image, VD ? kVdW1F : kW1F, VD ? kVdW2 : kW2F);
   ClockProbe clock;
   clock.start(k);
-  if (PREC == 1) {
-    for (int i = threadIdx.x; i < kB1F; i += blockDim.x) lds[i] = k.image[kW1H + i];
-    for (int i = kB1F + threadIdx.x; i < kLdsImageFloats; i += blockDim.x) lds[i] = k.image[i];
-  } else {
-    for (int i = threadIdx.x; i < kImg; i += blockDim.x) lds[i] = k.image[i];
-  }
-  __syncthreads();
+  stage_decoder_image<PREC, kImg>(lds, k.image);
   const int lane = lane_id();
   const int wave = threadIdx.x >> 6;
   WaveSlabWide& slab = slabs[wave];
@@ -1814,16 +1845,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_wide_kernel(RenderKernelP
   const int S = k.S;
   const float fill_near = ordered_key_inv(~k.reduce[0]), fill_far = ordered_key_inv(k.reduce[1]);
   const float bg = k.white ? 1.0f : 0.0f;
-  const size_t tb = TEX == 0 ? 128 : 64;
   const uint32_t n_rays = (uint32_t)k.n_scenes * (uint32_t)k.hw;
-  const uint32_t tiles_x = (uint32_t)k.width >> 3;
-  auto ray_of = [&](uint32_t pos) -> uint32_t {
-    if (k.xcd_blocks || !k.tile_order) return pos;
-    const uint32_t scene = pos / (uint32_t)k.hw, p = pos - scene * (uint32_t)k.hw;
-    const uint32_t tile = p >> 6, in = p & 63u;
-    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    return scene * (uint32_t)k.hw + ((ty << 3) + (in >> 3)) * (uint32_t)k.width + (tx << 3) + (in & 7u);
-  };
   FieldParams P = make_field_params(k.texels, k.res, TEX, k.A, k.use_sdf, k.beta, k.alpha, lds, kImg, k.layout);
   P.vf = vf;
   P.w1t = nfi_dyn_lds; P.w2r0 = nfi_dyn_lds + kW1TFloats;       // (kRenderNormals only)
@@ -1847,48 +1869,19 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_wide_kernel(RenderKernelP
   uint32_t cur = queue.fetch(), nxt = 0;
   while (cur < n_rays) {
     nxt = queue.fetch();
-    const uint32_t ray = ray_of(cur);
+    const uint32_t ray = queue.ray_of(cur);
     const uint32_t hitb = k.hit[ray];
     if (k.skip_missed && !(hitb & 2)) {
-      if (lane == 0) {
-        k.rgb[(size_t)ray * 3] = bg; k.rgb[(size_t)ray * 3 + 1] = bg; k.rgb[(size_t)ray * 3 + 2] = bg;
-        k.depth[ray] = 0.0f; k.mask[ray] = 0.0f;
-      }
-      if constexpr (EXTRA) {
-        if (k.coords && lane < 3) k.coords[(size_t)ray * 3 + lane] = 0.0f;
-        if (k.semantics && lane < k.A) k.semantics[(size_t)ray * k.A + lane] = 0.0f;
-        if (NRM && lane < 3) k.normals[(size_t)ray * 3 + lane] = bg;
-      }
+      if (lane == 0) store_pixel(k, ray, bg, bg, bg, 0.0f, 0.0f);
+      if constexpr (EXTRA) zero_missed_maps<NRM>(k, ray, lane, bg);
       if constexpr (TAPS) {
-        if (k.stash) {
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            if (j * 64 + lane < S) {
-              const size_t zs = (size_t)ray * (size_t)k.tap_stride + j * 64 + lane;
-              k.t_coarse[zs] = 0.0f; k.sigma_coarse[zs] = 0.0f;
-              float* q = k.rgb_coarse + zs * 3; q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
-              if (k.fine) {
-                k.t_fine[zs] = 0.0f; k.sigma_fine[zs] = 0.0f;
-                q = k.rgb_fine + zs * 3; q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
-              }
-            }
-          }
-        }
+        if (k.stash) zero_stash_row(k, ray, S, lane);
       }
     } else {
       const int scene = (int)fastdiv(ray, k.div_hw);
       if (scene != cur_scene) {
         cur_scene = scene;
-        const char* tex_scene = reinterpret_cast<const char*>(k.texels) + (size_t)scene * 3 * k.res * k.res * tb;
-        P.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(tex_scene), 0, (int)P.scene_bytes, 0x00020000);
-        wave_lds_fence();
-        {
-          int c = lane & 3, row = lane >> 2;
-          float v = 0.0f;
-          if (k.att && c < 3 && row >= 1 && row <= k.A) v = k.att[((size_t)scene * k.A + (row - 1)) * 3 + c];
-          vf[lane] = v;
-        }
-        wave_lds_fence();
+        enter_scene<TEX>(P, k, vf, scene, lane);
       }
       const size_t r3 = (size_t)ray * 3;
       const float ox = k.ro[r3], oy = k.ro[r3 + 1], oz = k.ro[r3 + 2];
@@ -1975,12 +1968,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_wide_kernel(RenderKernelP
           dep[2 + j] = tf[j]; sig[2 + j] = q.sigma; cr[2 + j] = q.r; cg[2 + j] = q.g; cb[2 + j] = q.b;
           eidx[2 + j] = val[j] ? S + j * 64 + lane : 0x7fffffff;
           if constexpr (TAPS) {
-            if (val[j]) {
-              const size_t i = ts + j * 64 + lane;
-              if (k.t_fine) k.t_fine[i] = tf[j];
-              if (k.sigma_fine) k.sigma_fine[i] = q.sigma;
-              if (k.rgb_fine) { float* o3 = k.rgb_fine + i * 3; o3[0] = q.r; o3[1] = q.g; o3[2] = q.b; }
-            }
+            if (val[j]) store_sample_tap(k.t_fine, k.sigma_fine, k.rgb_fine, ts + j * 64 + lane, tf[j], q.sigma, q.r, q.g, q.b);
           }
         }
         n = 2 * S;
@@ -1998,10 +1986,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_wide_kernel(RenderKernelP
       }
       float w[4];
       CompositeOut o = composite_slab<4>(slab, n, dnorm, k.white, lane, w);
-      if (lane == 0) {
-        k.rgb[(size_t)ray * 3] = o.r; k.rgb[(size_t)ray * 3 + 1] = o.g; k.rgb[(size_t)ray * 3 + 2] = o.b;
-        k.depth[ray] = o.depth; k.mask[ray] = o.mask;
-      }
+      if (lane == 0) store_pixel(k, ray, o.r, o.g, o.b, o.depth, o.mask);
       if constexpr (EXTRA) {
         if (k.coords) composite_coords<4>(slab, w, n, lane, ox, oy, oz, dx, dy, dz, k.coords + (size_t)ray * 3);
         float ws[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -2051,24 +2036,14 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_wide_kernel(RenderKernelP
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           if (val[j]) {
-            const size_t i = ts + j * 64 + lane;
-            if (k.t_coarse) k.t_coarse[i] = tc[j];
-            if (k.sigma_coarse) k.sigma_coarse[i] = sc[j];
-            if (k.rgb_coarse) { float* o3 = k.rgb_coarse + i * 3; o3[0] = rc[j]; o3[1] = gc[j]; o3[2] = bc[j]; }
+            store_sample_tap(k.t_coarse, k.sigma_coarse, k.rgb_coarse, ts + j * 64 + lane, tc[j], sc[j], rc[j], gc[j], bc[j]);
             if (k.perm) {
               k.perm[(size_t)ray * n + rank[j]] = j * 64 + lane;
               if (k.fine) k.perm[(size_t)ray * n + rank[2 + j]] = S + j * 64 + lane;
             }
           }
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          int e = j * 64 + lane;
-          if (e < n) {
-            if (k.weights) k.weights[(size_t)ray * n + e] = w[j];
-            if (k.t_sorted) k.t_sorted[(size_t)ray * n + e] = slab.srt[0][e];
-          }
-        }
+        store_sorted_taps<4>(k, slab, w, ray, n, lane);
       }
       wave_lds_fence();  // slab is reused by the next ray
     }
@@ -2101,13 +2076,7 @@ __global__ __launch_bounds__(256, NFI_RENDER_OCC) void render_fwd_long_kernel(Re
   __shared__ WaveSlabLong slabs[4];
   ClockProbe clock;
   clock.start(k);
-  if (PREC == 1) {
-    for (int i = threadIdx.x; i < kB1F; i += blockDim.x) lds[i] = k.image[kW1H + i];
-    for (int i = kB1F + threadIdx.x; i < kLdsImageFloats; i += blockDim.x) lds[i] = k.image[i];
-  } else {
-    for (int i = threadIdx.x; i < kImg; i += blockDim.x) lds[i] = k.image[i];
-  }
-  __syncthreads();
+  stage_decoder_image<PREC, kImg>(lds, k.image);
   const int lane = lane_id();
   const int wave = threadIdx.x >> 6;
   WaveSlabLong& slab = slabs[wave];
@@ -2116,16 +2085,7 @@ __global__ __launch_bounds__(256, NFI_RENDER_OCC) void render_fwd_long_kernel(Re
   const int slots = (S + 63) >> 6;
   const float fill_near = ordered_key_inv(~k.reduce[0]), fill_far = ordered_key_inv(k.reduce[1]);
   const float bg = k.white ? 1.0f : 0.0f;
-  const size_t tb = TEX == 0 ? 128 : 64;
   const uint32_t n_rays = (uint32_t)k.n_scenes * (uint32_t)k.hw;
-  const uint32_t tiles_x = (uint32_t)k.width >> 3;
-  auto ray_of = [&](uint32_t pos) -> uint32_t {
-    if (k.xcd_blocks || !k.tile_order) return pos;
-    const uint32_t scene = pos / (uint32_t)k.hw, p = pos - scene * (uint32_t)k.hw;
-    const uint32_t tile = p >> 6, in = p & 63u;
-    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    return scene * (uint32_t)k.hw + ((ty << 3) + (in >> 3)) * (uint32_t)k.width + (tx << 3) + (in & 7u);
-  };
   FieldParams P = make_field_params(k.texels, k.res, TEX, k.A, k.use_sdf, k.beta, k.alpha, lds, kImg, k.layout);
   P.vf = vf;
   int cur_scene = -1;
@@ -2133,34 +2093,17 @@ __global__ __launch_bounds__(256, NFI_RENDER_OCC) void render_fwd_long_kernel(Re
   uint32_t cur = queue.fetch(), nxt = 0;
   while (cur < n_rays) {
     nxt = queue.fetch();
-    const uint32_t ray = ray_of(cur);
+    const uint32_t ray = queue.ray_of(cur);
     const uint32_t hitb = k.hit[ray];
     const size_t ts = (size_t)ray * (size_t)k.tap_stride;
     if (k.skip_missed && !(hitb & 2)) {
-      if (lane == 0) {
-        k.rgb[(size_t)ray * 3] = bg; k.rgb[(size_t)ray * 3 + 1] = bg; k.rgb[(size_t)ray * 3 + 2] = bg;
-        k.depth[ray] = 0.0f; k.mask[ray] = 0.0f;
-      }
-      if (k.stash) {
-        for (int e = lane; e < S; e += 64) {
-          k.t_coarse[ts + e] = 0.0f; k.sigma_coarse[ts + e] = 0.0f;
-          float* q = k.rgb_coarse + (ts + e) * 3; q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
-        }
-      }
+      if (lane == 0) store_pixel(k, ray, bg, bg, bg, 0.0f, 0.0f);
+      if (k.stash) zero_stash_row(k, ray, S, lane);
     } else {
       const int scene = (int)fastdiv(ray, k.div_hw);
       if (scene != cur_scene) {
         cur_scene = scene;
-        const char* tex_scene = reinterpret_cast<const char*>(k.texels) + (size_t)scene * 3 * k.res * k.res * tb;
-        P.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(tex_scene), 0, (int)P.scene_bytes, 0x00020000);
-        wave_lds_fence();
-        {
-          int c = lane & 3, row = lane >> 2;
-          float v = 0.0f;
-          if (k.att && c < 3 && row >= 1 && row <= k.A) v = k.att[((size_t)scene * k.A + (row - 1)) * 3 + c];
-          vf[lane] = v;
-        }
-        wave_lds_fence();
+        enter_scene<TEX>(P, k, vf, scene, lane);
       }
       const size_t r3 = (size_t)ray * 3;
       const float ox = k.ro[r3], oy = k.ro[r3 + 1], oz = k.ro[r3 + 2];
@@ -2179,30 +2122,20 @@ __global__ __launch_bounds__(256, NFI_RENDER_OCC) void render_fwd_long_kernel(Re
                                                            nullptr, nullptr, slab.stage, nullptr, k.xray, (int)ray);
         if (val) {
           slab.srt[0][e] = t; slab.srt[1][e] = q.sigma; slab.srt[2][e] = q.r; slab.srt[3][e] = q.g; slab.srt[4][e] = q.b;
-          if (k.t_coarse) k.t_coarse[ts + e] = t;
-          if (k.sigma_coarse) k.sigma_coarse[ts + e] = q.sigma;
-          if (k.rgb_coarse) { float* o3 = k.rgb_coarse + (ts + e) * 3; o3[0] = q.r; o3[1] = q.g; o3[2] = q.b; }
+          store_sample_tap(k.t_coarse, k.sigma_coarse, k.rgb_coarse, ts + e, t, q.sigma, q.r, q.g, q.b);
         }
       }
       wave_lds_fence();
       float w[NS];
       CompositeOut o = composite_slab<NS>(slab, S, dnorm, k.white, lane, w);
       if (lane == 0) {
-        k.rgb[(size_t)ray * 3] = o.r; k.rgb[(size_t)ray * 3 + 1] = o.g; k.rgb[(size_t)ray * 3 + 2] = o.b;
-        k.depth[ray] = o.depth; k.mask[ray] = o.mask;
+        store_pixel(k, ray, o.r, o.g, o.b, o.depth, o.mask);
         if (k.near_plane) k.near_plane[ray] = near;
         if (k.far_plane) k.far_plane[ray] = far;
       }
-      if (k.weights || k.t_sorted || k.perm) {
-#pragma unroll
-        for (int j = 0; j < NS; ++j) {
-          const int e = j * 64 + lane;
-          if (e < S) {
-            if (k.weights) k.weights[rs + e] = w[j];
-            if (k.t_sorted) k.t_sorted[rs + e] = slab.srt[0][e];
-            if (k.perm) k.perm[rs + e] = e;
-          }
-        }
+      if (k.weights || k.t_sorted) store_sorted_taps<NS>(k, slab, w, ray, S, lane);
+      if (k.perm) {
+        for (int e = lane; e < S; e += 64) k.perm[rs + e] = e;
       }
       wave_lds_fence();  // the rows are reused by the next ray
     }

@@ -242,6 +242,43 @@ def test_work_queues_cover_every_ray_exactly_once(gpu_device, H, W, S, B):
     assert outs[0]['mask'].max() > 0.1
 
 
+def test_hand_out_changes_no_pixel_in_any_kernel_family(gpu_device):
+    """The three persistent render kernels (S <= 64, 64 < S <= 128, one pass of up to 512) share their ray hand-out
+    (RayQueue, RayQueue::ray_of), scene switch and result stores.  The hand-out order does not enter a ray's arithmetic,
+    so the per-XCD queues (tuning 0), the single queue in 8x8 tile order (16: the ray_of arithmetic) and the single queue
+    in scanline order (16 | 4) must give the same bits - tolerance zero - in all three, stash rows included.  Two scenes
+    (the scene switch runs mid-launch) of 16x24 pixels (multiples of 8 but not of 16: block side 8), under a camera that
+    leaves rays on both sides of the missed-ray branch.  (test_work_queues_cover_every_ray_exactly_once above renders the
+    128-sample kernel in tile order too, at 64x64; the single-pass kernel's tile order and the stash rows are only here.)"""
+    B, H, W, A = 2, 16, 24, 10
+    d, g = scene(B, A, 32, 23)
+    dev = gpu_device
+    cam = look_at_cameras(B, 1.8, g)
+    focal = torch.full((B,), 1.0)
+    ro, rd = orc.ray_bundle(H, W, focal, cam)
+    missed = 1.0 - orc.near_far(ro, orc.unit_dirs(rd), 0.55)[2].float().mean().item()
+    print('rays that miss the cube: %.3f' % missed)
+    assert 0.0 < missed < 1.0
+    cam, focal = cam.to(dev), focal.to(dev)
+    texels = ops.planes_to_texels(d['planes'].to(dev))
+    image = ops.decoder_pack(d['w1'].to(dev), d['b1'].to(dev), d['w2'].to(dev), d['b2'].to(dev), A)
+    args = (texels, image, 0.55, A, d['att'].to(dev), True, d['beta'].to(dev), d['alpha'].to(dev))
+    for S, fine in ((24, True), (100, True), (200, False)):
+        noise_c = torch.rand(B, H, W, S, generator=g).to(dev)
+        noise_f = torch.rand(B * H * W, S, generator=g).to(dev) if fine else None
+        for stash in ((False, True) if fine else (False,)):
+            keys = ('rgb', 'depth', 'mask') + (('stash_t', 'stash_sigma', 'stash_rgb') if stash else ())
+            outs = [ops.render_fwd(cam, focal, H, W, S, *args, noise_coarse=noise_c, noise_fine=noise_f, fine_sampling=fine,
+                                   stash=stash, tuning=tuning) for tuning in (0, 16, 16 | 4)]
+            assert all(torch.isfinite(outs[0][k]).all() for k in keys)
+            for r in outs[1:]:
+                for k in keys:
+                    assert torch.equal(r[k], outs[0][k]), (S, stash, k)
+            # both branches ran: background pixels of skipped rays, and pixels that saw the object
+            bgpix = (outs[0]['mask'] == 0.0).float().mean().item()
+            assert 0.0 < bgpix < 1.0 and outs[0]['mask'].max() > 0.1, (S, stash, bgpix)
+
+
 def test_two_host_threads_on_their_own_streams(gpu_device):
     """under nn.DataParallel the reference calls render() from one Python thread per replica, concurrently - the
     library has to be re-entrant (no global mutable state, the caller's stream, thread-local error text).  One GPU here, so
