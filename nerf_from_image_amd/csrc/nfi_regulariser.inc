@@ -27,7 +27,6 @@ struct SdfGradParams {
   const float* points; int64_t P; int n_scenes;
   const float* texels; int res; float scene_range;
   const float* w1; const float* b1; const float* w2; const float* b2;     // raw parameters (row 0 of w2 / b2 is used)
-  int w2_stride;
   float* d; float* g;                                                        // forward outputs
   const float* gd; const float* gg;                                          // backward: upstream gradients
   float* g_texels; float* g_w1; float* g_b1; float* g_w2; float* g_b2;

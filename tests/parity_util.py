@@ -51,6 +51,21 @@ def err(a, b):
                 exact=float((a == b).float().mean()), nonfinite=int((~fin).sum()))
 
 
+def grad_close(got, ref, tol, what, ref32=None):
+    """|got - ref| <= tol x max |ref|.  ref32 (the float32 oracle's gradient): its own distance from ref is printed beside
+    the figure, it does not enter the bound."""
+    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    scale = float(ref.abs().max().clamp_min(1e-12))
+    e = float((got - ref).abs().max()) / scale
+    if ref32 is not None:
+        e32 = float((ref32.detach().double().cpu() - ref).abs().max()) / scale
+        print('%-60s rel %.3e (bound %.1e, float32 oracle %.3e)' % (what, e, tol, e32))
+    else:
+        print('%-60s rel %.3e (bound %.1e)' % (what, e, tol))
+    assert torch.isfinite(got).all() and e <= tol, (what, e, tol, scale)
+
+
 def oracle_normal_map(meta, t, o):
     """The composited normal map of a golden case as the reference computes it (generator.py:599-623 + lib/nerf_utils.py:
     149-151, 159): autograd of the oracle's distance at every sample, normalised, composited with the oracle's weights."""

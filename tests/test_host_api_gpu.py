@@ -584,7 +584,8 @@ def test_regulariser_outputs(gpu_device):
     """Generator.forward's regulariser branch (generator.py:505-585) on the HIP path of a bare container: eikonal
     (d sdf/dx as an operator output, its backward = the reference's double backward), distance, total variation and
     entropy terms, and their gradients w.r.t. the plane producer and the decoder, against float64 autograd of the
-    oracle with the same two random draws."""
+    oracle with the same two random draws.  (One shape, four summed losses: the operator itself is held to the float64
+    oracle per point, per texel and per shape in test_regulariser_operator.py.)"""
     import copy
     torch.manual_seed(3)
     model = StandInGenerator(0.55, attention_values=10, use_sdf=True, plane_res=32).to(gpu_device).train()
@@ -635,7 +636,8 @@ def test_regulariser_outputs(gpu_device):
 
 def test_regulariser_outputs_with_view_direction_decoder(gpu_device):
     """--use_viewdir models (33-output decoder): all four regulariser terms (the total-variation one used to fail on
-    the decoder shape) against the float64 oracle, which like the reference uses output row 0 only."""
+    the decoder shape) against the float64 oracle, which like the reference uses output row 0 only.  (Per
+    element, with this decoder shape at the tile and chunk boundaries: test_regulariser_operator.py, the tail_P* cases.)"""
     import copy
     torch.manual_seed(3)
     model = StandInGenerator(0.55, attention_values=10, use_sdf=True, plane_res=32, use_viewdir=True).to(gpu_device).train()

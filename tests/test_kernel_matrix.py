@@ -16,7 +16,7 @@ import re
 import pytest
 import torch
 
-from parity_util import err, hip_field_setup, hip_render, oracle_normal_map, oracle_render
+from parity_util import err, grad_close, hip_field_setup, hip_render, oracle_normal_map, oracle_render
 from stand_in import look_at_cameras
 from test_hip_parity import ATOL, sigma_close
 from nerf_from_image_amd import _lib, ops
@@ -603,21 +603,6 @@ def test_field_row(gpu_device, row):
     close(q['rgb'], ref['rgb'], ATOL, what + ': rgb')
     if row.A > 0:
         close(q['semantics'], ref['semantics'], 1e-5, what + ': semantics')
-
-
-def grad_close(got, ref, tol, what, ref32=None):
-    """|got - ref| <= tol x max |ref|.  ref32 (the float32 oracle's gradient): its own distance from ref is printed beside
-    the figure, it does not enter the bound."""
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    scale = float(ref.abs().max().clamp_min(1e-12))
-    e = float((got - ref).abs().max()) / scale
-    if ref32 is not None:
-        e32 = float((ref32.detach().double().cpu() - ref).abs().max()) / scale
-        print('%-60s rel %.3e (bound %.1e, float32 oracle %.3e)' % (what, e, tol, e32))
-    else:
-        print('%-60s rel %.3e (bound %.1e)' % (what, e, tol))
-    assert torch.isfinite(got).all() and e <= tol, (what, e, tol, scale)
 
 
 def field_grads(t, x, ups, use_sdf, A, vd, spr, dtype):
