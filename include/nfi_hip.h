@@ -400,18 +400,25 @@ int nfi_sdf_gradient_bwd(const nfi_sdf_gradient_args* a, nfi_stream_t stream);
 /* bits of nfi_render_args.tuning that the library reads (described at the field; every other bit is ignored) */
 enum { NFI_TUNING_SCANLINE_ORDER = 4, NFI_TUNING_EXACT_FP32_MLP = 8, NFI_TUNING_SINGLE_WORK_COUNTER = 16 };
 typedef struct nfi_render_args {
-  int n_scenes, height, width;
+  int n_scenes, height, width;   /* n_scenes: the number of images (= scenes x views_per_scene) */
   int n_samples;                 /* S per pass, <= NFI_MAX_SAMPLES; without fine_sampling a single pass of up to
                                   * NFI_MAX_SAMPLES_SINGLE_PASS (run.py:2271), with stage taps / stash / viewdir but
                                   * without the extra maps, the cycle profile and termination_eps */
   int fine_sampling;             /* args.fine_sampling (run.py:259) */
   int white_background;          /* dataset_config['white_background'] (run.py:348) */
   float scene_range;             /* dataset_config['scene_range'] (run.py:200) */
+  /* Views per scene, V (0 and 1 both mean one view).  The images of a call are ordered scene-major: image i has camera i,
+   * noise rows i and output / tap / stash rows i, and reads the texels and attention rows of scene i / V.  n_scenes stays
+   * the number of IMAGES and must be a multiple of V; `texels` and `attention_values` then hold n_scenes / V scenes.
+   * Everything per ray is unchanged, and the batch-wide miss-fill of lib/nerf_utils.py:258-259 is taken over all n_scenes
+   * images - the result is bit for bit that of a one-view call with every scene's texels and attention rows repeated V
+   * times.  nfi_render_setup does not read the field. */
+  int views_per_scene;
   /* camera (as nfi_raygen_args) */
   const float* cam2world; const float* focal; const float* bbox; const float* center;
   /* field (as nfi_field_args) */
-  const void* texels; int plane_res; int texel_dtype;
-  const float* decoder_image; int n_attention; const float* attention_values;
+  const void* texels; int plane_res; int texel_dtype;              /* texels of n_scenes / views_per_scene scenes */
+  const float* decoder_image; int n_attention; const float* attention_values;   /* [n_scenes / views_per_scene, A] */
   int use_sdf; const float* beta; const float* alpha;
   /* the reference's two random draws (nerf_utils.py:115, 202); NULL = deterministic */
   const float* noise_coarse;     /* [N,S] or NULL */

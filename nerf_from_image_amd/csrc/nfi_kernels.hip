@@ -14,7 +14,7 @@ using namespace nfi;
 // error plumbing, argument checks and the LDS staging helpers shared with nfi_backward_field.hip: nfi_host.hpp
 thread_local char nfi_err_buf[256] = "";
 extern "C" const char* nfi_last_error(void) { return nfi_err_buf; }
-extern "C" int nfi_version(void) { return 100; }
+extern "C" int nfi_version(void) { return 101; }
 
 
 // ------------------------------------------------------------------------------------------------
@@ -1373,7 +1373,7 @@ struct RenderKernelParams {
   float* coords;       // kRenderExtra kernels: composited query points [N][3], or null
   float* normals;      // kRenderNormals kernels: composited unit normals [N][3]
   unsigned long long* clock_probe;   // null, or {shader cycles, 100 MHz ticks} lived by workgroup 0 / wave 0
-  FastDiv div_hw, div_bps, div_bw;   // division by rays per image, blocks per scene, blocks per image row (nfi_device.hpp)
+  FastDiv div_scene_rays, div_bps, div_bw;   // division by rays per scene (rays per image x views per scene), blocks per image, blocks per image row (nfi_device.hpp)
   int tap_stride;      // entries per ray in the per-sample tap arrays: S, or 2S for the training stash (fine half at +S)
   int stash;           // 1: the taps are the training stash: missed rays keep being skipped and get an all-zero row
 };
@@ -1672,7 +1672,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
       }
     } else {
       unsigned long long t0 = PROF ? __builtin_readcyclecounter() : 0;
-      const int scene = (int)fastdiv(ray, k.div_hw);
+      const int scene = (int)fastdiv(ray, k.div_scene_rays);
       if (scene != cur_scene) {
         cur_scene = scene;
         enter_scene<TEX>(P, k, vf, scene, lane);
@@ -1878,7 +1878,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_wide_kernel(RenderKernelP
         if (k.stash) zero_stash_row(k, ray, S, lane);
       }
     } else {
-      const int scene = (int)fastdiv(ray, k.div_hw);
+      const int scene = (int)fastdiv(ray, k.div_scene_rays);
       if (scene != cur_scene) {
         cur_scene = scene;
         enter_scene<TEX>(P, k, vf, scene, lane);
@@ -2100,7 +2100,7 @@ __global__ __launch_bounds__(256, NFI_RENDER_OCC) void render_fwd_long_kernel(Re
       if (lane == 0) store_pixel(k, ray, bg, bg, bg, 0.0f, 0.0f);
       if (k.stash) zero_stash_row(k, ray, S, lane);
     } else {
-      const int scene = (int)fastdiv(ray, k.div_hw);
+      const int scene = (int)fastdiv(ray, k.div_scene_rays);
       if (scene != cur_scene) {
         cur_scene = scene;
         enter_scene<TEX>(P, k, vf, scene, lane);
@@ -2247,6 +2247,8 @@ static RenderFlags render_flags(const nfi_render_args* a) {
 static int render_check_call(const nfi_render_args* a) {
   REQUIRE(a && a->cam2world && a->rgb && a->depth && a->mask && a->workspace, "render: null pointer");
   REQUIRE(a->n_scenes > 0 && a->height > 0 && a->width > 0, "render: bad image shape");
+  REQUIRE(a->views_per_scene >= 0, "render: views_per_scene must not be negative (0 and 1 both mean one view)");
+  REQUIRE(a->n_scenes % std::max(a->views_per_scene, 1) == 0, "render: n_scenes (the number of images) must be a multiple of views_per_scene");
   REQUIRE(a->n_samples >= 4 && a->n_samples <= (a->fine_sampling ? NFI_MAX_SAMPLES : NFI_MAX_SAMPLES_SINGLE_PASS),
           "render: n_samples must be in [4,128] per pass with fine sampling, [4,512] for a single pass");
   REQUIRE(a->n_samples <= 64 || !a->profile_cycles, "render: the cycle profile exists for n_samples <= 64 only");
@@ -2323,7 +2325,8 @@ static RenderKernelParams render_kernel_params(const nfi_render_args* a, const R
   const int side = 1 << k.xcd_block_shift;
   k.xcd_blocks = (!(a->tuning & NFI_TUNING_SINGLE_WORK_COUNTER) && (a->width % side == 0) && (a->height % side == 0)) ? 1 : 0;
   const uint32_t bw = (uint32_t)a->width >> k.xcd_block_shift, bh = (uint32_t)a->height >> k.xcd_block_shift;
-  k.div_hw = make_fastdiv((uint32_t)k.hw);
+  // the scene of a ray: its image / views_per_scene (the images of a call are scene-major); hw * V <= rays of the call < 2^32
+  k.div_scene_rays = make_fastdiv((uint32_t)k.hw * (uint32_t)std::max(a->views_per_scene, 1));
   k.div_bw = make_fastdiv(bw > 0 ? bw : 1u);
   k.div_bps = make_fastdiv(bw * bh > 0 ? bw * bh : 1u);
   k.tile_order = (!(a->tuning & NFI_TUNING_SCANLINE_ORDER) && (a->width % 8 == 0) && (a->height % 8 == 0)) ? 1 : 0;

@@ -18,6 +18,11 @@ where ``Generator.forward`` does (407-503) and hands their output to the kernels
 
 Any module with the attributes listed in ``REQUIRED_ATTRS`` works the same way (the GPU-box tests
 use a stand-in plane producer, the reference checkout is not available there).
+
+Produce once, render many: ``bake(model, model_input)`` runs the plane producer of an attached model once and returns
+the ``FusedField`` of its scenes; ``nerf_from_image_amd.render.render_views(field, H, W, cameras [B,V,4,4], ...)`` then
+renders any number of views per scene from it without calling the model again (turntables, viewers, the front and
+random views of evaluate_inversion).
 """
 import math
 import types
@@ -52,6 +57,8 @@ class FusedField:
         self.scene_range = scene_range
         self.planes = planes                    # autograd handles (None in inference)
         self.decoder_params = decoder_params
+        self.ray_features = None                # padded per-ray features [B,N,48] of the view-direction decoder
+        self.bbox_overlay = False               # the 'bbox' request edits sigma (generator.py:645-659): staged path only
 
     @property
     def requires_grad(self):
@@ -424,6 +431,29 @@ def wrapped_forward(self, viewdir, c, request_model_outputs=['sampler'], model_i
     if added_att:
         del model_outputs['attention_values']
     return model_outputs
+
+
+def bake(model, model_input, model_inputs={}):
+    """One forward of an attached model under no_grad, asking for the sampler only: the FusedField of model_input's scenes
+    (texels, packed decoder, attention values, beta / alpha) - a snapshot, detached from the producer and from the model's
+    parameters.  Render it from any cameras with render.render_views.  Not for a --use_viewdir model: its field takes the cameras' view directions per ray."""
+    if getattr(model, 'use_viewdir', False):
+        raise ValueError('bake(): the field of a use_viewdir model depends on the cameras (per-ray view-direction features); '
+                         'use render() with the option views_per_scene')
+    with torch.no_grad():
+        sampler = model(None, model_input, ['sampler'], model_inputs)['sampler']
+    fused = getattr(sampler, 'fused', None)
+    if fused is None:
+        raise TypeError('bake(): the model is not attached (its sampler carries no FusedField); call attach(model) first')
+    # nothing of the returned field requires a gradient (the decoder's parameters, beta and alpha are the model's own
+    # otherwise): render_views then takes the fused inference path with or without no_grad around it.  The model's
+    # parameters are COPIED, as the packed decoder image is: the field stays the snapshot it is when the model is updated
+    det = (lambda t: None if t is None else t.detach())
+    snap = (lambda t: None if t is None else t.detach().clone())
+    baked = FusedField(fused.texels, fused.decoder_image, det(fused.attention_values), fused.n_attention, fused.use_sdf,
+                       snap(fused.beta), snap(fused.alpha), fused.scene_range, planes=det(fused.planes),
+                       decoder_params=tuple(snap(t) for t in fused.decoder_params))
+    return baked
 
 
 def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_handoff=False):

@@ -384,8 +384,12 @@ def render_fwd(cam2world, focal, height, width, num_samples, texels, decoder_ima
                noise_coarse=None, noise_fine=None, fine_sampling=True, white_background=True, taps=(),
                skip_missed_rays=True, workspace=None, events=None, tuning=0, profile_cycles=None, ray_features=None,
                termination_eps=0.0, row_window=None, clock_probe=None, stash=False, rays_ready=False,
-               want_semantics=False, want_coords=False, want_normals=False, strict=False):
+               want_semantics=False, want_coords=False, want_normals=False, strict=False, views_per_scene=1):
     """Fused forward render.  Returns dict(rgb [B,H,W,3], depth, mask [B,H,W], + requested taps).
+    views_per_scene: V >= 1 images per scene, scene-major: image i (camera i, noise rows i, output rows i; B of them, a
+    multiple of V) reads the texels and attention rows of scene i // V, so `texels` / `attention_values` hold B / V
+    scenes - bit for bit the result of V = 1 with both repeat_interleave(V, 0).  Whatever V, a call whose texels or
+    attention values hold fewer scenes than its cameras need is refused (ValueError) before any launch.
     row_window: None, or (row_offset, full_height): `height` rows starting at row_offset of an image full_height rows tall
     (bit-identical to those rows of the full render; noise / outputs / taps are sized for the window).
     clock_probe: None or a uint64 / int64 [2] device tensor receiving {shader cycles, 100 MHz ticks} of the render kernel.
@@ -418,6 +422,15 @@ def render_fwd(cam2world, focal, height, width, num_samples, texels, decoder_ima
     dev = cam2world.device
     n = B * height * width
     S = num_samples
+    V = int(views_per_scene)
+    if V < 1 or B % V != 0:
+        raise ValueError('render_fwd: %d cameras are not a multiple of views_per_scene = %d (>= 1)' % (B, V))
+    if texels.shape[0] * V < B:
+        raise ValueError('render_fwd: texels of %d scene(s) x views_per_scene %d do not cover %d cameras' % (
+            texels.shape[0], V, B))
+    if n_attention > 0 and (attention_values is None or attention_values.shape[0] * V < B):
+        raise ValueError('render_fwd: attention_values of %d scene(s) x views_per_scene %d do not cover %d cameras' % (
+            0 if attention_values is None else attention_values.shape[0], V, B))
     lib = _lib.load()
     tdt = texel_dtype_of(texels)
     out = {'rgb': torch.empty((B, height, width, 3), dtype=torch.float32, device=dev),
@@ -497,7 +510,7 @@ def render_fwd(cam2world, focal, height, width, num_samples, texels, decoder_ima
         _lib.call_struct(
             'nfi_render_fwd', 'nfi_render_args', _stream(cam2world), n_scenes=B, height=height, width=width,
             n_samples=S, fine_sampling=int(fine_sampling), white_background=int(white_background),
-            scene_range=float(scene_range), cam2world=cam2world, focal=_f32c(focal, 'focal_length'),
+            scene_range=float(scene_range), views_per_scene=V, cam2world=cam2world, focal=_f32c(focal, 'focal_length'),
             bbox=_f32c(bbox, 'bbox'), center=_f32c(center, 'center'), texels=texels, plane_res=texel_res(texels),
             texel_layout=texel_layout_of(texels), texel_dtype=tdt, decoder_image=decoder_image, n_attention=n_attention,
             attention_values=_f32c(attention_values, 'attention_values') if n_attention > 0 else None,

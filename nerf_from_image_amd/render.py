@@ -51,6 +51,19 @@ process-wide - the reference calls render from one thread per GPU):
                     render kernel (parallel.allreduce_ray_setup), so that every band is bit-identical to the same rows
                     of the full render.  Without it the fill is the band's own: identical only where no marched ray
                     misses the exact cube (the default cameras) - stated in include/nfi_hip.h.
+  views_per_scene   1 (default), or V: every scene of the model call is rendered from V cameras.  tform_cam2world is then
+                    [B*V,4,4], scene-major (the V cameras of scene 0 first), focal_length / bbox / center follow the cameras,
+                    model_input keeps its B rows: the plane producer runs once per scene.  Outputs are [B*V,H,W,...], bit for
+                    bit those of the call with every latent repeated V times (the batch-wide miss-fill of
+                    lib/nerf_utils.py:258-259 runs over all B*V images, the random draws keep their shapes and order); on
+                    every path: fused (nfi_render_args.views_per_scene), fused + stash (ONE field backward launch over
+                    V*H*W rays per scene sums the views' plane / attention-value / decoder gradients, camera and focal
+                    gradients stay per camera; at most 2^25 points per scene, V*H*W*samples - else ValueError), staged (the V
+                    views of a scene as one image V*H rows tall; so are the viewdirs a use_viewdir model receives).
+
+``render_views(fused, height, width, tform_cam2world, focal_length, depth_samples_per_ray, ...)`` renders from planes that
+exist already (``generator.bake(model, model_input)``, or any sampler's ``.fused``) without calling a model: cameras
+[B,V,4,4] or [B*V,4,4], V inferred; produce once, render many (turntable, viewer, the views of evaluate_inversion).
 """
 import types
 
@@ -62,7 +75,8 @@ from .field_backward import field_query_bwd
 
 args = None
 dataset_config = None
-_DEFAULTS = dict(termination_eps=0.0, strict_near_far=True, row_window=None, row_window_sync=False)
+_DEFAULTS = dict(termination_eps=0.0, strict_near_far=True, row_window=None, row_window_sync=False, views_per_scene=1)
+MAX_STASH_POINTS_PER_SCENE = 1 << 25      # nfi_field_query_bwd's binned scatter addresses a scene's points by 32-bit byte offsets
 options = types.SimpleNamespace(**_DEFAULTS)
 
 
@@ -114,19 +128,23 @@ def _needs_grad(*tensors):
 
 
 def _render_with_stash(fused, height, width, S, cam, focal, bbox, center, noise_c, noise_f, white, cam_grad, fine=True,
-                       strict=False):
+                       strict=False, views_per_scene=1):
     """The fused render as ONE autograd node (see the module docstring).  Gradients follow the reference's graph:
     rgb_map / mask -> sigma, rgb of every sample and (through dists * ||rd||) the ray directions; depth_map and the
     depth samples carry none; the field -> planes, decoder, colour table, beta, alpha and - unless the camera is
     detached - the query points -> rays -> tform_cam2world / focal_length.  fine=False: one pass of S samples
     (run.py without --fine_sampling).  With the view-direction decoder (fused.ray_features: --use_viewdir, carla) the
     per-ray feature of the ViewDirectionMapper and its output layer are inputs of the node too: their gradients go
-    back into the PyTorch mapper and, through its view directions, into the camera."""
+    back into the PyTorch mapper and, through its view directions, into the camera.
+    views_per_scene = V: `cam` holds V cameras per scene of `fused`, scene-major.  The stash is ray-major, so the V views of
+    a scene are one contiguous run of points: the ONE field backward launch sees B scenes of V * H * W rays (an image
+    V * H rows tall) and sums the plane, attention-value and decoder gradients of all views; camera and focal gradients
+    stay per camera."""
     texels, image = fused.texels, fused.decoder_image
     A, use_sdf, scene_range = fused.n_attention, fused.use_sdf, fused.scene_range
     w1, b1, w2, b2 = fused.decoder_params[:4]
     vd = fused.ray_features is not None
-    B = cam.shape[0]
+    B = cam.shape[0] // views_per_scene          # scenes: the batch of the field backward
     n_list = (2 if fine else 1) * S
     keep = {}
 
@@ -134,7 +152,7 @@ def _render_with_stash(fused, height, width, S, cam, focal, bbox, center, noise_
         out = ops.render_fwd(a_cam, a_focal, height, width, S, texels, image, scene_range, A, att, use_sdf, be, al,
                              bbox=bbox, center=center, noise_coarse=noise_c, noise_fine=noise_f, fine_sampling=fine,
                              white_background=bool(white), skip_missed_rays=True, stash=True,
-                             ray_features=fused.ray_features, strict=strict)
+                             ray_features=fused.ray_features, strict=strict, views_per_scene=views_per_scene)
         keep.update({k: out[k] for k in ('stash_t', 'stash_sigma', 'stash_rgb', 'ray_origins', 'ray_directions')})
         return out['rgb'], out['depth'], out['mask']
 
@@ -178,6 +196,14 @@ def _render_with_stash(fused, height, width, S, cam, focal, bbox, center, noise_
     return res
 
 
+def _views(opts, n_images):
+    """views_per_scene of the bound options, checked against the number of cameras of a call."""
+    V = int(opts.views_per_scene)
+    if V < 1 or n_images % V != 0:
+        raise ValueError('views_per_scene = %d: %d cameras are not a whole number of scenes' % (V, n_images))
+    return V
+
+
 def _render(cfg, dcfg, opts, target_model, height, width, tform_cam2world, focal_length, center, bbox, model_input,
             depth_samples_per_ray, randomize=True, compute_normals=False, compute_semantics=False,
             compute_coords=False, extra_model_outputs=[], extra_model_inputs={}, force_no_cam_grad=False):
@@ -185,16 +211,14 @@ def _render(cfg, dcfg, opts, target_model, height, width, tform_cam2world, focal
     if S > 512 or (S > 128 and cfg.fine_sampling):
         raise NotImplementedError('depth_samples_per_ray: at most 128 per pass with fine sampling, 512 without '
                                   '(run.py asks for 64 + 64, or 128 / 512 in one pass), got %d' % S)
-    scene_range = dcfg['scene_range']
-    white = dcfg['white_background']
     if compute_normals:
         assert cfg.use_sdf
     if compute_semantics:
         assert cfg.attention_values > 0
 
-    B = tform_cam2world.shape[0]
+    B = tform_cam2world.shape[0]          # images: scenes x views_per_scene
+    V = _views(opts, B)
     dev = tform_cam2world.device
-    plain = not (compute_normals or compute_semantics or compute_coords)
     cam_grad = (not force_no_cam_grad) and _needs_grad(tform_cam2world, focal_length, bbox, center)
     if force_no_cam_grad and cfg.fine_sampling and _needs_grad(tform_cam2world, bbox, center):
         # run.py:211-214 detaches the COARSE query points, the depths and the ray directions - and then builds the fine pass's
@@ -213,16 +237,87 @@ def _render(cfg, dcfg, opts, target_model, height, width, tform_cam2world, focal
         # run.py:192-219: the model needs the normalised ray directions before it can build the sampler
         rays = nerf_utils.get_ray_bundle_normalized(height, width, focal_length, tform_cam2world, bbox, center)
         viewdirs = (rays[1].detach() if force_no_cam_grad else rays[1]).unsqueeze(-2)
+        if V > 1:
+            # the V views of a scene as ONE image V * H rows tall: the model's batch is the scenes', and the per-ray MLP of
+            # the ViewDirectionMapper (generator.py:223-251) returns its features in the same form
+            viewdirs = viewdirs.reshape(B // V, V * height, width, 1, 3)
     noise_c = torch.rand((B, rows, width, S), dtype=torch.float32, device=dev) if randomize else None
 
     model_outputs = target_model(viewdirs, model_input, ['sampler'] + extra_model_outputs, extra_model_inputs)
     sampler = model_outputs['sampler']
     del model_outputs['sampler']
     fused = getattr(sampler, 'fused', None)
+    if V > 1:
+        first = model_input[0] if isinstance(model_input, (list, tuple)) else model_input
+        scenes = fused.texels.shape[0] if fused is not None else first.shape[0]
+        if B != V * scenes:
+            raise ValueError('views_per_scene = %d: %d cameras for the %d scene(s) of the model call (expected %d)' % (
+                V, B, scenes, V * scenes))
+    out = _render_from_field(opts, fused, sampler, height, width, tform_cam2world, focal_length, center, bbox, S,
+                             bool(cfg.fine_sampling), dcfg['scene_range'], dcfg['white_background'], randomize,
+                             compute_normals, compute_semantics, compute_coords, noise_c, rays, cam_grad,
+                             force_no_cam_grad, getattr(target_model, 'training', False))
+    return out + (model_outputs,)
+
+
+def render_views(fused, height, width, tform_cam2world, focal_length, depth_samples_per_ray, center=None, bbox=None,
+                 randomize=True, fine_sampling=True, white_background=True, compute_normals=False,
+                 compute_semantics=False, compute_coords=False, **render_options):
+    """Renders views of scenes whose planes exist already: `fused` is a generator.FusedField (generator.bake(model, z), or
+    the `.fused` of a sampler), no model is called.  Returns (rgb, depth, mask, normals, extra) as render() does.
+
+    tform_cam2world: [B,V,4,4] or [B*V,4,4] (scene-major) for the B scenes of `fused`; V is inferred.  focal_length / bbox /
+    center follow the cameras.  Takes the fused inference path, or the fused + stash node when the field's tensors or the
+    cameras require a gradient; the random draws are render()'s, in its order.  What needs the staged path - the 'bbox'
+    overlay, extra maps with a gradient, a field with ray features (the view-direction decoder: its field depends on the
+    cameras) - raises NotImplementedError: call render() with the option views_per_scene for those.  `render_options` are
+    render()'s options (views_per_scene is inferred, not passed)."""
+    scenes = fused.texels.shape[0]
+    if tform_cam2world.dim() == 4:
+        if tform_cam2world.shape[0] != scenes:
+            raise ValueError('render_views: cameras [%d,%d,4,4] for a field of %d scene(s): the leading dimension is the scenes\''
+                             % (tform_cam2world.shape[0], tform_cam2world.shape[1], scenes))
+        # [B,V,...] -> scene-major [B*V,...]: cameras [.,4,4], focal [.], bbox [.,2,2], center [.,2]
+        tform_cam2world = tform_cam2world.flatten(0, 1)
+        focal_length = focal_length.flatten(0, 1) if focal_length is not None and focal_length.dim() == 2 else focal_length
+        bbox = bbox.flatten(0, 1) if bbox is not None and bbox.dim() == 4 else bbox
+        center = center.flatten(0, 1) if center is not None and center.dim() == 3 else center
+    if 'views_per_scene' in render_options:
+        raise TypeError('render_views infers views_per_scene from the cameras and the field')
+    B = tform_cam2world.shape[0]
+    if B == 0 or B % scenes != 0:
+        raise ValueError('render_views: %d cameras are not a whole number of views of the field\'s %d scene(s)' % (B, scenes))
+    if getattr(fused, 'ray_features', None) is not None:
+        raise NotImplementedError('render_views: a field with ray features (view-direction decoder) depends on the cameras; '
+                                  'use render() with the option views_per_scene')
+    opts = _options(dict(render_options, views_per_scene=B // scenes))
+    S = depth_samples_per_ray
+    if S > 512 or (S > 128 and fine_sampling):
+        raise NotImplementedError('depth_samples_per_ray: at most 128 per pass with fine sampling, 512 without, got %d' % S)
+    rows = height if opts.row_window is None else int(opts.row_window[1])
+    noise_c = torch.rand((B, rows, width, S), dtype=torch.float32, device=tform_cam2world.device) if randomize else None
+    cam_grad = _needs_grad(tform_cam2world, focal_length, bbox, center)
+    return _render_from_field(opts, fused, None, height, width, tform_cam2world, focal_length, center, bbox, S,
+                              bool(fine_sampling), fused.scene_range, white_background, randomize, compute_normals,
+                              compute_semantics, compute_coords, noise_c, None, cam_grad, False, False)
+
+
+def _render_from_field(opts, fused, sampler, height, width, tform_cam2world, focal_length, center, bbox, S, fine_sampling,
+                       scene_range, white, randomize, compute_normals, compute_semantics, compute_coords, noise_c, rays,
+                       cam_grad, force_no_cam_grad, training):
+    """Everything of a render behind the model call - THE path selection, shared by render() (sampler = the model's) and
+    render_views() (sampler = None: what would need the staged path raises).  noise_c: the stratified jitter, drawn by the
+    caller (before its model call); rays: the normalised ray bundle if the caller needed it already.
+    Returns (rgb, depth, mask, normals, extra)."""
+    B = tform_cam2world.shape[0]
+    V = int(opts.views_per_scene)
+    dev = tform_cam2world.device
+    rows = height if opts.row_window is None else int(opts.row_window[1])
+    plain = not (compute_normals or compute_semantics or compute_coords)
     ray_features = getattr(fused, 'ray_features', None)
 
     def inverse_cdf_draws():
-        if not cfg.fine_sampling:
+        if not fine_sampling:
             return None
         if randomize:
             return torch.rand([B * rows * width, S], dtype=torch.float32, device=dev)
@@ -236,7 +331,7 @@ def _render(cfg, dcfg, opts, target_model, height, width, tform_cam2world, focal
                            (ray_features is None or fused.texels.dtype == torch.float32))
     if compute_normals and fused is not None:
         # the sampler's own condition (generator.py:599-602; torch.is_grad_enabled() is autograd's business there)
-        assert fused.use_sdf and not getattr(target_model, 'training', False)
+        assert fused.use_sdf and not training
     # (one pass of 129..512 samples - no fine sampling, checked above - has its own fused kernel: plain maps only)
     if fused is not None and fused_maps and not cam_grad and not fused.requires_grad and (S <= 128 or plain):
         # ---------------- fused inference path (the kernel generates the rays itself) ----------------
@@ -255,18 +350,18 @@ def _render(cfg, dcfg, opts, target_model, height, width, tform_cam2world, focal
             None if fused.attention_values is None else fused.attention_values.detach(), fused.use_sdf,
             None if fused.beta is None else fused.beta.detach(), None if fused.alpha is None else fused.alpha.detach(),
             bbox=None if bbox is None else bbox.detach(), center=None if center is None else center.detach(),
-            noise_coarse=noise_c, noise_fine=inverse_cdf_draws(), fine_sampling=bool(cfg.fine_sampling),
+            noise_coarse=noise_c, noise_fine=inverse_cdf_draws(), fine_sampling=fine_sampling,
             white_background=bool(white), skip_missed_rays=True, ray_features=ray_features,
-            termination_eps=opts.termination_eps if (cfg.fine_sampling and not extras and ray_features is None) else 0.0,
+            termination_eps=opts.termination_eps if (fine_sampling and not extras and ray_features is None) else 0.0,
             row_window=window, want_semantics=compute_semantics and not compute_coords, want_coords=compute_coords,
             want_normals=compute_normals, workspace=ws, rays_ready=ws is not None,
             # a band's own hit count says nothing about the image (the top rows of a centred object are all background):
             # the check applies to the whole image - every call without a window, windowed calls only once
             # row_window_sync has summed the count over the bands
-            strict=_strict(opts) if (window is None or ws is not None) else False)
+            strict=_strict(opts) if (window is None or ws is not None) else False, views_per_scene=V)
         # run.py:337-338: coords take the semantics slot of render_volume_density when both are asked for
         extra_map = out['coords'] if compute_coords else (out['semantics'] if compute_semantics else None)
-        return out['rgb'], out['depth'], out['mask'], out.get('normals'), extra_map, model_outputs
+        return out['rgb'], out['depth'], out['mask'], out.get('normals'), extra_map
     if opts.row_window is not None:
         raise NotImplementedError('row_window is an option of the fused inference path (no gradient, no extra maps)')
 
@@ -275,15 +370,30 @@ def _render(cfg, dcfg, opts, target_model, height, width, tform_cam2world, focal
         # (with or without fine sampling, plain or view-direction decoder; the view-direction rays of run.py:216-222 were
         #  computed above for the model - the kernel regenerates the same rays, and the camera gradient of the viewdirs
         #  flows through the PyTorch mapper into that first ray op)
+        points_per_scene = V * height * width * (2 if fine_sampling else 1) * S
+        if points_per_scene > MAX_STASH_POINTS_PER_SCENE:
+            # refused here, before the render launch and the stash: the backward of this node is ONE field backward launch
+            raise ValueError('render with a gradient: %d views x %d x %d rays x %d samples = %d points per scene, above the '
+                             'field backward\'s limit of 2^25 = %d points per scene (render fewer views per call)' % (
+                                 V, height, width, (2 if fine_sampling else 1) * S, points_per_scene,
+                                 MAX_STASH_POINTS_PER_SCENE))
         det = (lambda t: None if t is None else t.detach())
         rgb_map, depth_map, mask = _render_with_stash(
             fused, height, width, S, tform_cam2world, focal_length, det(bbox), det(center), noise_c, inverse_cdf_draws(),
-            white, cam_grad, fine=bool(cfg.fine_sampling), strict=_strict(opts))
-        return rgb_map, depth_map, mask, None, None, model_outputs
+            white, cam_grad, fine=fine_sampling, strict=_strict(opts), views_per_scene=V)
+        return rgb_map, depth_map, mask, None, None
 
     # ---------------- staged path (extra maps with a gradient or over a pass of more than 128 samples) ----------------
+    if sampler is None:
+        raise NotImplementedError('render_views: this call needs the staged path (the bbox overlay, extra maps with a '
+                                  'gradient or over more than 128 samples); use render() with the option views_per_scene')
     ray_origins, ray_directions = rays if rays is not None else nerf_utils.get_ray_bundle_normalized(
         height, width, focal_length, tform_cam2world, bbox, center)
+    if V > 1:
+        # the V views of a scene are ONE image V * H rows tall: everything below is per ray or per scene
+        tall = (lambda t: t.reshape(B // V, V * height, *t.shape[2:]))
+        ray_origins, ray_directions = tall(ray_origins), tall(ray_directions)
+        noise_c = None if noise_c is None else tall(noise_c)
     with torch.no_grad():
         # (the staged path has one place to look at the counter - behind the near / far launch: 'after' is True here)
         near, far = nerf_utils.compute_near_far_planes(ray_origins.detach(), ray_directions.detach(), scene_range,
@@ -315,7 +425,7 @@ def _render(cfg, dcfg, opts, target_model, height, width, tform_cam2world, focal
     sigma, rgb, normals, semantics, coords = unpack(sampler(query_points, req, **hip_kw))
 
     extra = coords if coords is not None else semantics      # run.py:337-338: coords hijack the semantics slot
-    if cfg.fine_sampling:
+    if fine_sampling:
         with torch.no_grad():
             if randomize:
                 u = torch.rand([B * height * width, S], dtype=torch.float32, device=dev)
@@ -328,10 +438,13 @@ def _render(cfg, dcfg, opts, target_model, height, width, tform_cam2world, focal
         query_fine = nerf_utils.points_on_rays(ray_origins, ray_directions, z_samples)
         sigma_f, rgb_f, normals_f, semantics_f, coords_f = unpack(sampler(query_fine, req, **hip_kw))
         extra_f = coords_f if coords_f is not None else semantics_f
-        rgb_map, depth_map, mask, normal_map, extra_map = nerf_utils.merge_and_composite(
+        maps = nerf_utils.merge_and_composite(
             ray_directions, depth_values, sigma, rgb, z_samples, sigma_f, rgb_f, normals, normals_f, extra, extra_f,
             white_background=white)
     else:
-        rgb_map, depth_map, mask, normal_map, extra_map = nerf_utils.render_volume_density(
+        maps = nerf_utils.render_volume_density(
             sigma, rgb, ray_origins, ray_directions, depth_values, normals, extra, white_background=white)
-    return rgb_map, depth_map, mask, normal_map, extra_map, model_outputs
+    if V > 1:
+        # back to one image per camera: (rgb, depth, mask, normals, extra) [B/V, V*H, W, ...] -> [B, H, W, ...]
+        maps = tuple(None if t is None else t.reshape(B, height, *t.shape[2:]) for t in maps)
+    return tuple(maps)

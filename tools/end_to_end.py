@@ -5,6 +5,8 @@ rendered by run.py::render (reference) or by the drop-in with the attach()ed HIP
 Legs (what run.py executes, with the parts that cannot exist offline named):
   render     render() INCLUDING Generator.forward (run.py:221 -> models/generator.py:475-477), BASELINE cfg2: chairs
              geometry, B images x 128 x 128 rays x (64 + 64) samples, latents ws given (the eval / inversion callers), no grad.
+             --views V (drop-in only): B scenes x V views in one call through the render option views_per_scene - the
+             producer runs for B latents, the renderer for B x V images.
   inversion  one optimisation step of --run_inversion (run.py:2264-2299) in BASELINE cfg3's per-GPU shape: p3d_car-like
              geometry, 4 images, Adam(2e-3, betas 0.9 / 0.95, run.py:2007) on latents + camera + focal, MSE on image and
              mask against a synthetic target.  NOT included: the 15-way augmentation and the LPIPS network (needs the
@@ -120,8 +122,16 @@ def _scene(geometry, batch, dev, impl, texels, fused_handoff=False, hip_regulari
 
 
 def leg_render(dev, impl, batch=8, texels='fp32', iters=20, warmup=3, markers=False, res=128, samples=64, channels_last=False,
-               graph=False):
-    sc, model, ren = _scene('chairs', batch, dev, impl, texels, channels_last=channels_last)
+               graph=False, views=1):
+    images = batch * views
+    sc, model, ren = _scene('chairs', images, dev, impl, texels, channels_last=channels_last)
+    ws = sc.ws
+    if views > 1:
+        # `batch` scenes (the first latents) seen from `views` cameras each, scene-major: ONE producer run per scene
+        assert impl == 'hip' and not graph, '--views is an option of the drop-in\'s render()'
+        import nerf_from_image_amd.render as nfi_render
+        ren = nfi_render.make_render(sc.args, sc.dcfg, views_per_scene=views)
+        ws = sc.ws[:batch].contiguous()
     mk = Markers(dev, markers)
     mk.instrument(model)
     graphed = None
@@ -140,10 +150,12 @@ def leg_render(dev, impl, batch=8, texels='fp32', iters=20, warmup=3, markers=Fa
             return
         mk.emit('step_begin')
         with torch.no_grad():
-            ren(model, res, res, sc.cam, sc.focal, None, None, sc.ws, samples)
+            ren(model, res, res, sc.cam, sc.focal, None, None, ws, samples)
         mk.emit('render_end')
     r = _time_steps(step, iters, warmup)
-    r.update(rays_per_s=batch * res * res / (r['ms_median'] * 1e-3), images=batch, rays=batch * res * res)
+    r.update(rays_per_s=images * res * res / (r['ms_median'] * 1e-3), images=images, rays=images * res * res)
+    if views > 1:
+        r.update(scenes=batch, views=views)
     return r
 
 
@@ -273,6 +285,7 @@ def main():
     ap.add_argument('--quick', action='store_true')
     ap.add_argument('--channels-last', action='store_true', help='render leg: the synthesis network in NHWC memory format (experiment)')
     ap.add_argument('--graph', action='store_true', help='render leg, hip: the whole call captured in a HIP graph (GraphedRender)')
+    ap.add_argument('--views', type=int, default=1, help='render leg, hip: views per scene (--batch scenes x --views cameras in one call)')
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     if a.leg is None:
@@ -282,7 +295,7 @@ def main():
     if a.batch:
         kw['batch'] = a.batch
     if a.leg == 'render':
-        kw.update(channels_last=a.channels_last, graph=a.graph)
+        kw.update(channels_last=a.channels_last, graph=a.graph, views=a.views)
     if a.leg == 'gstep':
         kw.update(fused_handoff=a.fused_handoff, path_length=a.path_length, hip_regularisers=not a.reference_regularisers)
     r = LEGS[a.leg](dev, a.impl, **kw)

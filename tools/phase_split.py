@@ -100,7 +100,7 @@ def main():
     total = sum(per.values())
     top = sorted(by_kernel.items(), key=lambda kv: -kv[1])[:14]
     out = {'leg': sidecar['result'].get('leg'), 'impl': sidecar['result'].get('impl'), 'options': {k: v for k, v in sidecar['result'].items()
-                                                                                                   if k in ('texels', 'fused_handoff', 'path_length', 'hip_regularisers', 'batch')},
+                                                                                                   if k in ('texels', 'fused_handoff', 'path_length', 'hip_regularisers', 'batch', 'views')},
            'step_ms_events_median': sidecar['result']['ms_median'], 'steps': iters,
            'gpu_busy_ms_per_step': total, 'wall_ms_per_step_in_trace': (t_last - t_first) * 1e-6 / iters,
            'group_ms_per_step': per, 'group_share_of_gpu_time': {k: v / total for k, v in per.items()},
