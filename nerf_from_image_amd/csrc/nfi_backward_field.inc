@@ -4,12 +4,12 @@
 // backward (atomic scatter-add into the planes + coordinate gradients), the decoder MLP, the
 // Laplace-CDF density and the attention colour head.  Here: one kernel, forward recomputed per
 // 16-point tile (nothing but the points and the upstream gradients is read from HBM), every
-// contraction on v_mfma_f32_16x16x4_f32:
+// contraction on the matrix pipe (split-fp16 or fp32 operands: the two decoder back ends below):
 //
-//   gs^T [64x16] = W2^T [64x16] g_o^T [16x16]      16 MFMA   (operands in accumulator layout)
-//   gf^T [32x16] = W1^T [32x64] gh^T  [64x16]      32 MFMA
-//   dW2  [16x64] += g_o [16xpts] s^T  [ptsx64]     16 MFMA   (points along K: operands staged in LDS)
-//   dW1  [64x32] += gh  [64xpts] f^T  [ptsx32]     32 MFMA
+//   gs^T [64x16] = W2^T [64x16] g_o^T [16x16]      (operands in accumulator layout)
+//   gf^T [32x16] = W1^T [32x64] gh^T  [64x16]
+//   dW2  [16x64] += g_o [16xpts] s^T  [ptsx64]     (points along K: operands staged in LDS)
+//   dW1  [64x32] += gh  [64xpts] f^T  [ptsx32]
 //
 // Weight/bias/attention/beta/alpha gradients accumulate in registers over all tiles a wave
 // processes and are flushed once per block with atomics.  The per-point feature gradient gf (32 floats) either goes
@@ -123,839 +123,1011 @@ struct FieldBwdParams {
   FastDiv div_cpr, div_tside, div_tiles_x;      // the tile walk's three divisions (wave-uniform operands: scalar-ALU work)
 };
 
-// per-wave LDS staging (floats): F_T [16][36], GO_T [16][20], S_T [16][68] (reused as G_T [16][36]), GH_T [16][68]
-// view-direction decoder adds Y_T [16][52] (third-layer input) and GO2_T [16][52] (second-layer output gradient)
-constexpr int kStF = 0, kStGO = kStF + 16 * 36, kStS = kStGO + 16 * 20, kStGH = kStS + 16 * 68, kStFloats = kStGH + 16 * 68;
-constexpr int kStY = kStFloats, kStGO2 = kStY + 16 * 52, kStFloatsVd = kStGO2 + 16 * 52;
+// ================================================================================================
+// field_query_bwd_kernel = one shell (chunk walk, point set-up, gather, epilogue backward, row hand-off, scatter,
+// coordinate gradients: the named steps below) around one of two decoder back ends (PlainDecoderBwd, ViewdirDecoderBwd:
+// accumulators, per-wave LDS layout, forward recompute, backward to the feature gradient, flush).
+// ================================================================================================
 
-// ---- weight gradients of the plain decoder on the 16-bit matrix pipe ----
-// dW[m][n] = sum_pt A[m][pt] B[n][pt] has the POINT index on K.  The f32-input MFMA that did this (48 per tile) runs at
-// the fp32 vector rate on gfx950 and blocks the VALU while it does (tools/probes/mfma_valu_overlap.hip): 1.5 k of the
-// 7.6 k cycles of a tile.  Now: every operand as fp16 hi + lo in point-major LDS tiles [pt][unit], read back through
-// ds_read_b64_tr_b16 (a 16-lane group's 16 x 8-byte rows come back transposed: lane c gets, as element i, element c & 3
-// of the row addressed by lane 4 i + (c >> 2) - tools/probes/tr_read.hip), with the two halves of the K = 32 slots of
-// v_mfma_f32_16x16x32_f16 holding the SAME 16 points: A' = [A_hi | A_lo] against [B_hi ; B_hi] and [B_lo ; B_lo] gives
-// (A_hi + A_lo)(B_hi + B_lo) in two MFMAs per 16 x 16 output tile (16 cycles each instead of 4 x 32).
-// Gradient operands have no natural scale, and a weight gradient is a sum over points of very different magnitude: the
-// A side is scaled by a power of two S per accumulator set (sticky: it changes - and the accumulators are rescaled,
-// exactly - only when a tile's largest entry times S leaves [2^-2, 2^14)), so that every entry is resolved to 2^-22 of
-// its TILE's largest entry whatever the loss scale; the accumulators are in units of 1/S until the flush.
-// per-wave LDS of the plain decoder's backward, in bytes from the wave's base: R0 = the fp32 feature tile F_T [16][36]
-// of the load -> MFMA layout change, then the fp16 feature tiles; R1 = one phase at a time (see the kernel)
-constexpr int kW16F = 96, kW16H = 144, kW16O = 32;                 // row pitch of the [pt][32] / [pt][64] / [pt][16] fp16 tiles
-constexpr int kF16Hi = 0, kF16Lo = 16 * kW16F;                     // R0: 3 072 B
-constexpr int kR1 = 768;                                           // floats
-constexpr int kGH16Hi = kR1 * 4, kGH16Lo = kGH16Hi + 16 * kW16H, kGHT = (kGH16Lo + 16 * kW16H) / 4;   // phase B (+ GH_T fp32 [16][68])
-constexpr int kGO16Hi = kR1 * 4 + 1536, kGO16Lo = kGO16Hi + 16 * kW16O;        // phase A: behind the colour-table scratch (1 536 B)
-constexpr int kS16Hi = kR1 * 4 + 4608, kS16Lo = kS16Hi + 16 * kW16H;            // written by the forward recompute, read by phase A
-static_assert(kGHT + 16 * 68 <= 3072 && kS16Lo + 16 * kW16H <= 3072 * 4, "per-wave LDS of the backward kernel");
+// A tile's 16 points are held in two lane layouts: L (load: lane = 4 lp + lq - point lp, channel chunk lq) and
+// M (MFMA accumulator: lane = 16 g + j - point j, rows 4 g .. 4 g + 3)
+struct BwdLane { int lane, j, g, lp, lq; };
 
-// TEX: texel storage of the planes (0 fp32, 1 bf16, 2 fp16).  With 16-bit storage the forward recompute gathers the
-// rounded texels and the gradient image stays fp32: it is the gradient w.r.t. the rounded planes, handed to the
-// producer unchanged (straight-through rounding), which is what a bf16 / fp16 plane tensor gives under autograd.
-template <bool ATT, bool COORD, bool VD = false, int TEX = 0>
-__global__ __launch_bounds__(256, VD ? 1 : 2) void field_query_bwd_kernel(FieldBwdParams k) {
-  constexpr int kFwd = VD ? kVdFieldLdsFloats : kBwdFwdFloats;       // forward operand image + attention values
-  constexpr int kFwdImg = VD ? kVdImageFloats : kLdsImageFloats;
-  constexpr int kBwdImg = VD ? kVbImageFloats : kBwdImageFloats;
-  constexpr int kSt = VD ? kStFloatsVd : kStFloats;
-  constexpr int oW1F = VD ? kVdW1F : kW1F, oB1F = VD ? kVdB1F : kB1F, oW1T = VD ? kVbW1T : kBwdW1T;
-  extern __shared__ __attribute__((aligned(16))) float dyn[];
-  float* lds = dyn;                                   // fp32 part of the forward operand image + VF
-  float* ldb = dyn + kFwd;                            // backward operand image
-  float* stage_all = ldb + kBwdImg;
-  const int scene = blockIdx.y;
-  stage_field_lds(lds, k.image, k.att ? k.att + (size_t)scene * k.A * 3 : nullptr, k.A, kFwdImg);
-  if (!VD) {
-    // plain decoder: the forward recompute runs on the split-fp16 fragments (they overlay the fp32 ones, biases stay)
-    __syncthreads();
-    for (int i = threadIdx.x; i < kB1F; i += blockDim.x) lds[i] = k.image[kW1H + i];
-  }
-  for (int i = threadIdx.x; i < kBwdImg; i += blockDim.x) ldb[i] = k.image_bwd[i];
-  __syncthreads();
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  float* st = stage_all + wave * kSt;
-  const char* tex_scene = reinterpret_cast<const char*>(k.texels) + (size_t)scene * 3 * k.res * k.res * (TEX == 0 ? 128 : 64);
-  FieldParams P = make_field_params(tex_scene, k.res, TEX, k.A, k.use_sdf, k.beta, k.alpha, lds, kFwdImg, k.layout);
-  float* gtex_scene = k.g_texels + (size_t)scene * 3 * k.res * k.res * kC;
-  // gradient image strides in floats (fp32 whatever the texel storage; same layout as the texels)
-  const size_t g_pix = k.layout ? 3 * kC : kC, g_plane = k.layout ? (size_t)kC : (size_t)k.res * k.res * kC, g_row = (size_t)k.res * g_pix;
-  // column of feature slot group q / g in the [point][channel] LDS tiles: fp32 texels: a lane owns channels
-  // {4q..4q+3, 16+4q..16+4q+3}; 16-bit texels: {8q..8q+7} (load_texel8)
-  constexpr int kColA = TEX == 0 ? 4 : 8, kColB = TEX == 0 ? 16 : 4;      // first four slots at kColA*q, the other four kColB further
-  const int j = lane & 15, g = lane >> 4, lp = lane >> 2, lq = lane & 3;
-  const f32x4* ldsv = reinterpret_cast<const f32x4*>(lds);
-  const u32x4* ldsu = reinterpret_cast<const u32x4*>(lds);
-  const f32x4* ldbv = reinterpret_cast<const f32x4*>(ldb);
-  const int A = k.A;
-  const int n_out = A > 0 ? 1 + A : 4;
-  const float* xray_scene = VD ? k.xray + (size_t)scene * (size_t)(k.P / k.spr) * kRayFeatPad : nullptr;
-  float* gxray_scene = (VD && k.g_xray) ? k.g_xray + (size_t)scene * (size_t)(k.P / k.spr) * kRayFeatPad : nullptr;
-  const float alpha_v = k.use_sdf ? k.alpha[0] : 1.0f;
-  // per-scene bases (uniform: scalar registers) and 32-bit point offsets instead of 64-bit address arithmetic per access
-  // (round 5: - 3 % with the softplus median below; points_per_scene <= 2^30 - and <= 2^25 where the 128-byte rows exist -
-  // keep every element offset under 2^32: checked by the launcher)
-  const float* const pts_sc = k.points + (size_t)scene * k.P * 3;
-  const float* const gsig_sc = k.g_sigma + (size_t)scene * k.P;
-  const float* const grgb_sc = k.g_rgb + (size_t)scene * k.P * 3;
-  const float* const gsdf_sc = k.g_sdf ? k.g_sdf + (size_t)scene * k.P : nullptr;
-  float* const gfout_sc = k.gf_out ? k.gf_out + (size_t)scene * k.P * kC : nullptr;
-  uint8_t* const flag_sc = k.bin_flag ? k.bin_flag + (size_t)scene * k.P : nullptr;
+// per-scene bases (uniform: scalar registers) and 32-bit point offsets instead of 64-bit address arithmetic per access
+// (round 5: - 3 % with the softplus median below; points_per_scene <= 2^30 - and <= 2^25 where the 128-byte rows exist -
+// keep every element offset under 2^32: checked by the launcher)
+struct BwdScene {
+  int scene;
+  const float *pts, *gsig, *grgb, *gsdf;
+  float* gfout;
+  uint8_t* flag;
+  float* gtex;
+  size_t g_pix, g_plane, g_row;      // gradient image strides in floats (fp32 whatever the texel storage; same layout as the texels)
+};
 
-  // ---- accumulators (natural units; gains and base-2 factors applied at the flush) ----
-  constexpr int NT2 = VD ? 3 : 1;                      // 16-row tiles of the second layer's output
-  f32x4 dW1[4][2], dW2[NT2][4];
-  // Sums over the 16 points of a tile that are NOT weight gradients (bias gradients, the colour table's gradient) come
-  // out of the staged LDS tiles instead of 32 cross-lane reductions per tile: db1p of lane l = hidden unit l is the
-  // column sum of GH_T; dVacc is a 16 x 16 MFMA accumulator whose columns 0..2 are dV[row][c] = sum_pt p[row] g_rgb[c]
-  // and whose column 3 is the LAST layer's bias gradient sum_pt g_o[row] (b2, or b3 with VD) - the weight-gradient
-  // MFMAs' A operand against an indicator column.
-  float db1p = 0.0f;
-  f32x4 dVacc = {0.0f, 0.0f, 0.0f, 0.0f};
-  // biased exponents of the sticky power-of-two scales of dW2 / column 3 of dVacc and of dW1 (0: not set yet), and of the
-  // largest tile maximum each set has seen
-  int es_go = 0, es_gh = 0, et_max_go = 0, et_max_gh = 0;
-  constexpr int oR1 = VD ? kStS : kR1;                 // scratch rows of the epilogue / the feature-gradient rows
-  f32x4 dW3[3], db2v[3];                               // VD: third-layer weights, second-layer bias
-  float d_beta = 0.0f, d_alpha = 0.0f;
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    dW1[a][0] = f32x4{0, 0, 0, 0}; dW1[a][1] = f32x4{0, 0, 0, 0};
-#pragma unroll
-    for (int t2 = 0; t2 < NT2; ++t2) dW2[t2][a] = f32x4{0, 0, 0, 0};
-    if (a < 3) { dW3[a] = f32x4{0, 0, 0, 0}; db2v[a] = f32x4{0, 0, 0, 0}; }
-  }
+__device__ __forceinline__ BwdScene enter_bwd_scene(const FieldBwdParams& k, int scene) {
+  BwdScene S;
+  S.scene = scene;
+  S.gtex = k.g_texels + (size_t)scene * 3 * k.res * k.res * kC;
+  S.g_pix = k.layout ? 3 * kC : kC; S.g_plane = k.layout ? (size_t)kC : (size_t)k.res * k.res * kC; S.g_row = (size_t)k.res * S.g_pix;
+  S.pts = k.points + (size_t)scene * k.P * 3;
+  S.gsig = k.g_sigma + (size_t)scene * k.P;
+  S.grgb = k.g_rgb + (size_t)scene * k.P * 3;
+  S.gsdf = k.g_sdf ? k.g_sdf + (size_t)scene * k.P : nullptr;
+  S.gfout = k.gf_out ? k.gf_out + (size_t)scene * k.P * kC : nullptr;
+  S.flag = k.bin_flag ? k.bin_flag + (size_t)scene * k.P : nullptr;
+  return S;
+}
 
-  const int64_t n_chunks = (k.P + 63) / 64;
-  // Order of the chunks (64 consecutive points).  Plain: grid-stride.  With the ray-order hint: the rays of one image
-  // tile (a thin column of the volume: its footprint in the three planes is a few hundred KB) are taken by the waves of
-  // ONE XCD, tile after tile, so that the texels a tile gathers stay in that XCD's 4 MB of L2 instead of every XCD
-  // streaming the whole slice of the volume that two image rows cut (52 % L2 hits, 5.5 GB fetched per 8.4 M points).
-  const bool tiled = k.n_tiles > 0;
-  const int chunks_per_tile = k.tside * k.tside * k.cpr, waves_per_xcd = (int)(gridDim.x >> 3) * 4;
-  int tile = (int)(blockIdx.x & 7), cc = (int)(blockIdx.x >> 3) * 4 + wave;
-  int64_t lin = (int64_t)blockIdx.x * 4 + wave;
-  while (true) {
+// ---- step: next chunk ----
+// Order of the chunks (64 consecutive points).  Plain: grid-stride.  With the ray-order hint: the rays of one image
+// tile (a thin column of the volume: its footprint in the three planes is a few hundred KB) are taken by the waves of
+// ONE XCD, tile after tile, so that the texels a tile gathers stay in that XCD's 4 MB of L2 instead of every XCD
+// streaming the whole slice of the volume that two image rows cut (52 % L2 hits, 5.5 GB fetched per 8.4 M points).
+// next() RETURNS the chunk (-1: none left): with `bool next(int64_t& chunk)` and the variable in front of the loop the
+// chunk became loop-carried and every one of the 16 kernels spilled (profiles/r10/README.md).
+struct ChunkWalk {
+  int64_t n_chunks, lin;
+  bool tiled;
+  int chunks_per_tile, waves_per_xcd, tile, cc;
+  __device__ __forceinline__ ChunkWalk(const FieldBwdParams& k, int wave)
+      : n_chunks((k.P + 63) / 64), lin((int64_t)blockIdx.x * 4 + wave), tiled(k.n_tiles > 0),
+        chunks_per_tile(k.tside * k.tside * k.cpr), waves_per_xcd((int)(gridDim.x >> 3) * 4), tile((int)(blockIdx.x & 7)),
+        cc((int)(blockIdx.x >> 3) * 4 + wave) {}
+  __device__ __forceinline__ int64_t next(const FieldBwdParams& k) {
     int64_t chunk;
     if (!tiled) {
-      if (lin >= n_chunks) break;
+      if (lin >= n_chunks) return -1;
       chunk = lin;
       lin += (int64_t)gridDim.x * 4;
     } else {
       while (cc >= chunks_per_tile && tile < k.n_tiles) { cc -= chunks_per_tile; tile += 8; }
-      if (tile >= k.n_tiles) break;
+      if (tile >= k.n_tiles) return -1;
       const int rt = (int)fastdiv((uint32_t)cc, k.div_cpr), half = cc - rt * k.cpr;
       const int ty = (int)fastdiv((uint32_t)rt, k.div_tside), tx = rt - ty * k.tside;
       const int tile_y = (int)fastdiv((uint32_t)tile, k.div_tiles_x), tile_x = tile - tile_y * k.tiles_x;
       chunk = ((int64_t)(tile_y * k.tside + ty) * k.tw + tile_x * k.tside + tx) * k.cpr + half;
       cc += waves_per_xcd;
     }
-    const int64_t p = chunk * 64 + lane;
-    const bool valid = p < k.P;
-    const uint32_t gi = valid ? (uint32_t)p : 0u;           // offset inside the scene (scene bases above)
-    float px = 0.0f, py = 0.0f, pz = 0.0f;
-    if (valid) { px = pts_sc[gi * 3u]; py = pts_sc[gi * 3u + 1u]; pz = pts_sc[gi * 3u + 2u]; }
-    const float qx = px / k.scene_range, qy = py / k.scene_range, qz = pz / k.scene_range;
-    const bool out = (fabsf(qx) > 1.0f) || (fabsf(qy) > 1.0f) || (fabsf(qz) > 1.0f);
-    int x0, y0, z0;
-    float fx, fy, fz;
-    plane_coord(qx, P.res_m1, P.res, x0, fx);
-    plane_coord(qy, P.res_m1, P.res, y0, fy);
-    plane_coord(qz, P.res_m1, P.res, z0, fz);
-    // border clamp: zero coordinate gradient where the unnormalised coordinate is outside (0, R-1)
-    auto inside = [&](float q) { float u = ((q + 1.0f) / 2.0f) * P.res_m1; return (u > 0.0f && u < P.res_m1) ? 1 : 0; };
-    int flags = (out ? 1 : 0) | (valid ? 2 : 0) | (inside(qx) << 2) | (inside(qy) << 3) | (inside(qz) << 4);
-    if (!valid) { x0 = y0 = z0 = 0; fx = fy = fz = 0.0f; }
-    const int xi = (int)((uint32_t)x0 | ((uint32_t)y0 << 10) | ((uint32_t)z0 << 20));
-    // a point contributes only if it is valid and inside the cube (sigma and its gradient are masked
-    // by (1-outside); rgb of an outside point still has a gradient path to the colour head, exactly
-    // like the reference, so only INVALID points are dropped from the work mask)
-    const uint64_t live = __ballot(valid);
-    // does anything flow into the chunk's points?  ONE coalesced look at the upstream gradients per chunk (lane = point)
-    // instead of a dependent, four-fold redundant load in front of every tile's gather (field backward 1.785 -> 1.768 ms
-    // per 8.4 M points, profiles/r5/bwd_ab_moments_peek_prio.log)
-    uint64_t nzmask;
-    {
-      bool nz = false;
-      if (valid) {
-        nz = __builtin_nontemporal_load(gsig_sc + gi) != 0.0f || __builtin_nontemporal_load(grgb_sc + gi * 3u) != 0.0f ||
-             __builtin_nontemporal_load(grgb_sc + gi * 3u + 1u) != 0.0f || __builtin_nontemporal_load(grgb_sc + gi * 3u + 2u) != 0.0f ||
-             (gsdf_sc && __builtin_nontemporal_load(gsdf_sc + gi) != 0.0f);
-      }
-      nzmask = k.g_sem ? ~0ull : __ballot(nz);
+    return chunk;
+  }
+};
+
+// ---- step: point set-up and flags (lane = point of the chunk) ----
+struct ChunkPoints {
+  int64_t chunk;
+  bool valid;
+  uint32_t gi;                       // offset inside the scene (scene bases above)
+  float fx, fy, fz;
+  int xi;                            // x0 | y0 << 10 | z0 << 20
+  int flags;                         // 1 outside the cube, 2 valid, 4 / 8 / 16 coordinate x / y / z inside (0, R-1)
+  uint64_t live;
+};
+
+__device__ __forceinline__ ChunkPoints chunk_points(const FieldBwdParams& k, const FieldParams& P, const BwdScene& S, int64_t chunk,
+                                                    int lane) {
+  ChunkPoints C;
+  C.chunk = chunk;
+  const int64_t p = chunk * 64 + lane;
+  const bool valid = p < k.P;
+  const uint32_t gi = valid ? (uint32_t)p : 0u;
+  float px = 0.0f, py = 0.0f, pz = 0.0f;
+  if (valid) { px = S.pts[gi * 3u]; py = S.pts[gi * 3u + 1u]; pz = S.pts[gi * 3u + 2u]; }
+  const float qx = px / k.scene_range, qy = py / k.scene_range, qz = pz / k.scene_range;
+  const bool out = (fabsf(qx) > 1.0f) || (fabsf(qy) > 1.0f) || (fabsf(qz) > 1.0f);
+  int x0, y0, z0;
+  float fx, fy, fz;
+  plane_coord(qx, P.res_m1, P.res, x0, fx);
+  plane_coord(qy, P.res_m1, P.res, y0, fy);
+  plane_coord(qz, P.res_m1, P.res, z0, fz);
+  // border clamp: zero coordinate gradient where the unnormalised coordinate is outside (0, R-1)
+  auto inside = [&](float q) { float u = ((q + 1.0f) / 2.0f) * P.res_m1; return (u > 0.0f && u < P.res_m1) ? 1 : 0; };
+  C.flags = (out ? 1 : 0) | (valid ? 2 : 0) | (inside(qx) << 2) | (inside(qy) << 3) | (inside(qz) << 4);
+  if (!valid) { x0 = y0 = z0 = 0; fx = fy = fz = 0.0f; }
+  C.xi = (int)((uint32_t)x0 | ((uint32_t)y0 << 10) | ((uint32_t)z0 << 20));
+  C.valid = valid; C.gi = gi; C.fx = fx; C.fy = fy; C.fz = fz;
+  // a point contributes only if it is valid and inside the cube (sigma and its gradient are masked
+  // by (1-outside); rgb of an outside point still has a gradient path to the colour head, exactly
+  // like the reference, so only INVALID points are dropped from the work mask)
+  C.live = __ballot(valid);
+  return C;
+}
+
+// ---- step: the upstream-gradient peek ----
+// does anything flow into the chunk's points?  ONE coalesced look at the upstream gradients per chunk (lane = point)
+// instead of a dependent, four-fold redundant load in front of every tile's gather (field backward 1.785 -> 1.768 ms
+// per 8.4 M points, profiles/r5/bwd_ab_moments_peek_prio.log)
+__device__ __forceinline__ uint64_t upstream_peek(const FieldBwdParams& k, const BwdScene& S, const ChunkPoints& C) {
+  bool nz = false;
+  if (C.valid) {
+    const uint32_t gi = C.gi;
+    nz = __builtin_nontemporal_load(S.gsig + gi) != 0.0f || __builtin_nontemporal_load(S.grgb + gi * 3u) != 0.0f ||
+         __builtin_nontemporal_load(S.grgb + gi * 3u + 1u) != 0.0f || __builtin_nontemporal_load(S.grgb + gi * 3u + 2u) != 0.0f ||
+         (S.gsdf && __builtin_nontemporal_load(S.gsdf + gi) != 0.0f);
+  }
+  return k.g_sem ? ~0ull : __ballot(nz);
+}
+
+// one 16-point tile of a chunk: this lane's point in both layouts
+struct BwdTile {
+  int t, srcL;
+  float cfx, cfy, cfz;
+  uint32_t cxi;
+  int flL, flM;
+  int64_t ptM;                       // this lane's point in MFMA layout
+};
+
+__device__ __forceinline__ BwdTile tile_lanes(const ChunkPoints& C, int t, const BwdLane& L) {
+  BwdTile T;
+  const int srcL = 16 * t + L.lp, srcM = 16 * t + L.j;
+  T.t = t; T.srcL = srcL;
+  T.cfx = __shfl(C.fx, srcL, 64); T.cfy = __shfl(C.fy, srcL, 64); T.cfz = __shfl(C.fz, srcL, 64);
+  T.cxi = (uint32_t)__shfl(C.xi, srcL, 64);
+  T.flL = __shfl(C.flags, srcL, 64); T.flM = __shfl(C.flags, srcM, 64);
+  T.ptM = C.chunk * 64 + srcM;
+  return T;
+}
+
+// nothing flows into the tile (rays the renderer skipped, samples of zero weight, padding): every gradient of the tile is
+// exactly zero - no gather, no MLP, no rows for the scatter
+template <bool COORD>
+__device__ __forceinline__ void zero_tile_outputs(const FieldBwdParams& k, const BwdScene& S, const ChunkPoints& C, const BwdTile& T,
+                                                  const BwdLane& L) {
+  if (k.bin_flag && L.g == 0 && T.ptM < k.P) k.bin_flag[(size_t)S.scene * k.P + T.ptM] = 0;
+  if (COORD && k.g_points && L.lq == 0 && (T.flL & 2)) {
+    float* gp = k.g_points + ((size_t)S.scene * k.P + C.chunk * 64 + T.srcL) * 3;
+    gp[0] = 0.0f; gp[1] = 0.0f; gp[2] = 0.0f;
+  }
+}
+
+// column of feature slot group q / g in the [point][channel] LDS tiles: fp32 texels: a lane owns channels
+// {4q..4q+3, 16+4q..16+4q+3}; 16-bit texels: {8q..8q+7} (load_texel8): the first four slots at kColA * q, the other four
+// kColB further
+template <int TEX> struct FeatCols { static constexpr int kColA = TEX == 0 ? 4 : 8, kColB = TEX == 0 ? 16 : 4; };
+
+// ---- step: gather plus L -> M transposition (through the fp32 tile F_T [16][36] at `ft`) ----
+template <int TEX>
+__device__ __forceinline__ void gather_features(const FieldParams& P, const BwdTile& T, const BwdLane& L, float* ft, float (&feat)[8]) {
+  constexpr int kColA = FeatCols<TEX>::kColA, kColB = FeatCols<TEX>::kColB;
+  float featL[8];
+  {
+    TileTex<TEX> tex;
+    tile_issue<TEX>(P, L.lq, T.cxi, tex);
+    tile_bilinear<TEX>(tex, T.cfx, T.cfy, T.cfz, featL);        // sum of the three planes (the /3 lives in W1F)
+  }
+  f32x4* wr = reinterpret_cast<f32x4*>(ft + L.lp * 36 + L.lq * kColA);
+  wr[0] = f32x4{featL[0], featL[1], featL[2], featL[3]};
+  wr[kColB / 4] = f32x4{featL[4], featL[5], featL[6], featL[7]};
+  wave_lds_fence();
+  const f32x4* rd = reinterpret_cast<const f32x4*>(ft + L.j * 36 + L.g * kColA);
+  const f32x4 lo = rd[0], hi = rd[kColB / 4];
+  feat[0] = lo.x; feat[1] = lo.y; feat[2] = lo.z; feat[3] = lo.w;
+  feat[4] = hi.x; feat[5] = hi.y; feat[6] = hi.z; feat[7] = hi.w;
+}
+
+// hidden pre-activations -> softplus in base 2 (= softplus / ln2), accumulator layout
+__device__ __forceinline__ void softplus2_tile(f32x4 (&sp)[4]) {
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float h = sp[nt][r];
+      float s2 = __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(h));
+      sp[nt][r] = __builtin_amdgcn_fmed3f(s2, h, 128.0f);     // == (h > thr ? h : s2) wherever the two differ in fp32 (tile_mlp)
     }
+}
+
+// ---- step: epilogue backward: upstream gradients -> g_o (rows 4g+r of point j) ----
+// SDF / density into row 0; softmax over the colour table (ATT; the table's gradient dV on the matrix pipe, through the
+// scratch rows at `rows`) or sigmoid into the colour rows.  dVacc is a 16 x 16 MFMA accumulator whose columns 0..2 are
+// dV[row][c] = sum_pt p[row] g_rgb[c] (column 3 belongs to the decoder back end).
+template <bool ATT>
+__device__ __forceinline__ f32x4 epilogue_bwd(const FieldBwdParams& k, const FieldParams& P, const BwdScene& S, const BwdTile& T,
+                                              const BwdLane& L, const f32x4& o, float alpha_v, float* rows, f32x4& dVacc,
+                                              float& d_beta, float& d_alpha) {
+  const int j = L.j, g = L.g, A = k.A;
+  const bool pv = (T.flM & 2) != 0;
+  const float keep = (T.flM & 1) ? 0.0f : 1.0f;          // 1 - outside
+  const uint32_t ptU = (uint32_t)T.ptM;
+  const float gsig = pv ? S.gsig[ptU] : 0.0f;
+  float grgb[3] = {0.0f, 0.0f, 0.0f};
+  if (pv) { grgb[0] = S.grgb[ptU * 3u]; grgb[1] = S.grgb[ptU * 3u + 1u]; grgb[2] = S.grgb[ptU * 3u + 2u]; }
+  f32x4 go = {0.0f, 0.0f, 0.0f, 0.0f};
+  const float sdf = bcast_row0(o.x);
+  float g_d = (pv && S.gsdf) ? S.gsdf[ptU] : 0.0f;
+  if (k.use_sdf) {
+    // sigma = (1/alpha) * cdf(-d) * keep,  cdf(x) = 0.5 + 0.5 sign(x) (1 - exp(-|x|/beta))
+    const float ad = fabsf(sdf);
+    const float e = __builtin_amdgcn_exp2f(ad * P.neg_log2e_over_beta);
+    const float sgn = (sdf < 0.0f) ? 1.0f : ((sdf > 0.0f) ? -1.0f : 0.0f);   // sign(-d)
+    const float cdf = 0.5f + 0.5f * sgn * (1.0f - e);
+    g_d += (sdf != 0.0f) ? gsig * (-(P.inv_alpha * keep) * (0.5f / P.beta) * e) : 0.0f;   // torch.sign(0) == 0
+    if (g == 0) {
+      d_beta += gsig * (P.inv_alpha * keep) * (-0.5f * sgn * ad * e / (P.beta * P.beta));
+      d_alpha += gsig * (-(P.inv_alpha * cdf * keep) / alpha_v);
+    }
+  } else {
+    const float dd = sdf - 1.0f;
+    g_d += gsig * keep * (1.0f / (1.0f + __expf(-dd)));
+  }
+  if constexpr (ATT) {
+    const size_t giM = (size_t)S.scene * k.P + (pv ? T.ptM : 0);
+    float m = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { int row = 4 * g + r; m = (row >= 1 && row <= A) ? fmaxf(m, o[r]) : m; }
+    m = max_xor32(max_xor16(m));
+    const f32x4* vf = reinterpret_cast<const f32x4*>(P.vf) + g * 4;
+    float pe[4], gp[4], se = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int row = 4 * g + r;
+      bool rv = (row >= 1) && (row <= A);
+      pe[r] = rv ? __builtin_amdgcn_exp2f(o[r] - m) : 0.0f;
+      se += pe[r];
+      f32x4 v = vf[r];
+      gp[r] = (grgb[0] * v.x + grgb[1] * v.y) + grgb[2] * v.z;
+      if (rv && pv && k.g_sem) gp[r] += k.g_sem[giM * A + (row - 1)];
+    }
+    se = sum_xor32(sum_xor16(se));
+    const float inv = 1.0f / se;
+    float dot = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { pe[r] *= inv; dot += pe[r] * gp[r]; }
+    dot = sum_xor32(sum_xor16(dot));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      go[r] = pe[r] * (gp[r] - dot);                      // d/d(feature), natural units
+    }
+    if (!k.points_only) {
+      // dV[row][c] += sum_pt p[row][pt] g_rgb[c][pt] on the matrix pipe: P_T [pt][row] and the tile's g_rgb [pt][4]
+      // go through the (free at this point) scratch rows
+      wave_lds_fence();
+      *reinterpret_cast<f32x4*>(rows + j * 20 + 4 * g) = f32x4{pe[0], pe[1], pe[2], pe[3]};
+      if (g == 0) *reinterpret_cast<f32x4*>(rows + 320 + j * 4) = f32x4{grgb[0], grgb[1], grgb[2], 0.0f};
+      wave_lds_fence();
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const int pt = 4 * ks + g;
+        const float a_p = rows[pt * 20 + j];
+        const float b_g = rows[320 + pt * 4 + (j & 3)];
+        dVacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a_p, (j < 4) ? b_g : 0.0f, dVacc, 0, 0, 0);
+      }
+      wave_lds_fence();
+    }
+  } else {
+    // rgb = 2.004 sigmoid(f) - 1.002 ; rows 1..3 live in group 0
+    if (g == 0) {
+      const float f3[3] = {o.y, o.z, o.w};
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float sgm = 1.0f / (1.0f + __builtin_amdgcn_exp2f(-f3[c]));
+        go[1 + c] = grgb[c] * 2.004f * sgm * (1.0f - sgm);
+      }
+    }
+  }
+  if (g == 0) go[0] = g_d;
+  return go;
+}
+
+// what a decoder back end hands the shell for one tile: gf^T = W1^T gh^T (rows = channels, accumulator layout == feature
+// layout M), in units of gf_inv (a power of two; 1 with fp32 MFMAs)
+struct FeatureGrad { f32x4 gf0, gf1; float gf_inv; };
+
+// ---- step: M -> L rows through LDS, pre-divided by 3 (mean of the three planes) ----
+__device__ __forceinline__ void rows_to_load_layout(float* rows, const FeatureGrad& gf, const BwdLane& L) {
+  wave_lds_fence();
+  {
+    const float third = (1.0f / 3.0f) * gf.gf_inv;
+    f32x4* wr = reinterpret_cast<f32x4*>(rows + L.j * 36 + 4 * L.g);
+    wr[0] = gf.gf0 * third;
+    wr[4] = gf.gf1 * third;
+  }
+  wave_lds_fence();
+}
+
+// ---- step: gf_out rows plus flags ----
+// hand the tile's feature-gradient rows to the follow-up kernels: the 16 rows are 2 KB of consecutive workspace,
+// written as two 16-byte stores per lane (8 lanes = one row); the binned scatter also gets a flag per point: rows
+// that are exactly zero (outside the cube, zero upstream) drop out
+__device__ __forceinline__ void store_gf_rows(const FieldBwdParams& k, const BwdScene& S, const ChunkPoints& C, int t, const float* rows,
+                                              int lane) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int pt = 8 * h + (lane >> 3), c4 = lane & 7;
+    const int64_t pidx = C.chunk * 64 + 16 * t + pt;
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(rows + pt * 36 + 4 * c4);
+    const uint64_t nzb = __ballot(gv.x != 0.0f || gv.y != 0.0f || gv.z != 0.0f || gv.w != 0.0f);
+    if (pidx < k.P) {
+      const uint32_t pu = (uint32_t)pidx;
+      *reinterpret_cast<f32x4*>(S.gfout + (pu * (uint32_t)kC + 4u * (uint32_t)c4)) = gv;
+      if (S.flag && c4 == 0) S.flag[pu] = ((nzb >> (lane & 56)) & 0xFFull) ? 1 : 0;
+    }
+  }
+}
+
+// ---- step: per-point atomic scatter of the plane gradient: one instruction = the two x-adjacent corners of one point ----
+// (64 consecutive floats = 2 full 128-B lines per wave instruction; the atomic units retire per
+//  line touched, so this is 8x cheaper than scattering in the quad load layout - tools/probes/atomic_scatter.hip)
+__device__ __forceinline__ void scatter_tile_atomics(const FieldParams& P, const BwdScene& S, const ChunkPoints& C, int t, const float* rows,
+                                                     int lane) {
+  const int lc = lane & 31, lh = lane >> 5;
 #pragma unroll 1
-    for (int t = 0; t < 4; ++t) {
-      if (((live >> (16 * t)) & 0xFFFFull) == 0) continue;
-      const int srcL = 16 * t + lp, srcM = 16 * t + j;
-      const float cfx = __shfl(fx, srcL, 64), cfy = __shfl(fy, srcL, 64), cfz = __shfl(fz, srcL, 64);
-      const uint32_t cxi = (uint32_t)__shfl(xi, srcL, 64);
-      const int flL = __shfl(flags, srcL, 64), flM = __shfl(flags, srcM, 64);
-      const int64_t ptM = chunk * 64 + srcM;                 // this lane's point in MFMA layout
-      const size_t giM = (size_t)scene * k.P + ((flM & 2) ? ptM : 0);
-      // ---------------- does anything flow into this tile? ----------------
-      // (the chunk-level peek above; the values are loaded again where they are used - held across the forward recompute
-      //  they cost the registers this kernel does not have)
-      const bool pv = (flM & 2) != 0;
-      {
-        if (((nzmask >> (16 * t)) & 0xFFFFull) == 0) {
-          // nothing (rays the renderer skipped, samples of zero weight, padding): every gradient of the tile is exactly
-          // zero - no gather, no MLP, no rows for the scatter
-          if (k.bin_flag && g == 0 && ptM < k.P) k.bin_flag[(size_t)scene * k.P + ptM] = 0;
-          if (COORD && k.g_points && lq == 0 && (flL & 2)) {
-            float* gp = k.g_points + ((size_t)scene * k.P + chunk * 64 + srcL) * 3;
-            gp[0] = 0.0f; gp[1] = 0.0f; gp[2] = 0.0f;
-          }
-          continue;
-        }
-      }
-      // ---------------- forward recompute ----------------
-      float featL[8], feat[8];
-      {
-        TileTex<TEX> T;
-        tile_issue<TEX>(P, lq, cxi, T);
-        tile_bilinear<TEX>(T, cfx, cfy, cfz, featL);        // sum of the three planes (the /3 lives in W1F)
-      }
-      {
-        f32x4* wr = reinterpret_cast<f32x4*>(st + kStF + lp * 36 + lq * kColA);
-        wr[0] = f32x4{featL[0], featL[1], featL[2], featL[3]};
-        wr[kColB / 4] = f32x4{featL[4], featL[5], featL[6], featL[7]};
-        wave_lds_fence();
-        const f32x4* rd = reinterpret_cast<const f32x4*>(st + kStF + j * 36 + g * kColA);
-        const f32x4 lo = rd[0], hi = rd[kColB / 4];
-        feat[0] = lo.x; feat[1] = lo.y; feat[2] = lo.z; feat[3] = lo.w;
-        feat[4] = hi.x; feat[5] = hi.y; feat[6] = hi.z; feat[7] = hi.w;
-      }
-      f32x4 sp[4];          // softplus in base 2 (= softplus/ln2), accumulator layout
+  for (int pt = 0; pt < 16; ++pt) {
+    const int src = 16 * t + pt;
+    const int fl = __builtin_amdgcn_readlane(C.flags, src);
+    if (!(fl & 2)) continue;
+    const float gv = rows[pt * 36 + lc];
+    if (__ballot(gv != 0.0f) == 0) continue;
+    const uint32_t pxi = (uint32_t)__builtin_amdgcn_readlane(C.xi, src);
+    const float pfx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, C.fx), src));
+    const float pfy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, C.fy), src));
+    const float pfz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, C.fz), src));
+    const uint32_t px0 = pxi & 1023u, py0 = (pxi >> 10) & 1023u, pz0 = (pxi >> 20) & 1023u;
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) sp[nt] = ldsv[(oB1F >> 2) + g * 4 + nt];
-      if constexpr (VD) {
+    for (int pl = 0; pl < 3; ++pl) {
+      const uint32_t a0 = (pl == 2) ? py0 : px0, b0 = (pl == 0) ? py0 : pz0;
+      const float fa = (pl == 2) ? pfy : pfx, fb = (pl == 0) ? pfy : pfz;
+      const float wa = lh ? fa : 1.0f - fa;
+      float* base = S.gtex + (size_t)pl * S.g_plane + ((size_t)b0 * P.res + a0 + lh) * S.g_pix + lc;
+      const float v0 = (wa * (1.0f - fb)) * gv, v1 = (wa * fb) * gv;
+      if (v0 != 0.0f) unsafeAtomicAdd(base, v0);
+      if (v1 != 0.0f) unsafeAtomicAdd(base + S.g_row, v1);
+    }
+  }
+}
+
+// ---- step: coordinate gradients in the load layout: d/d(unnormalised u_x, u_y, u_z) ----
+struct CoordGrad { float x, y, z; };
+
+template <int TEX>
+__device__ __forceinline__ CoordGrad coord_gradients(const FieldParams& P, const BwdTile& T, const BwdLane& L, const float* rows) {
+  constexpr int kColA = FeatCols<TEX>::kColA, kColB = FeatCols<TEX>::kColB;
+  const int lq = L.lq;
+  const uint32_t cxi = T.cxi;
+  const float cfx = T.cfx, cfy = T.cfy, cfz = T.cfz;
+  const bool ptv = (T.flL & 2) != 0;
+  float gcoord[3] = {0.0f, 0.0f, 0.0f};
+  float gfL[8];
+  {
+    const f32x4* rd = reinterpret_cast<const f32x4*>(rows + L.lp * 36 + lq * kColA);
+    const f32x4 lo = rd[0], hi = rd[kColB / 4];
+    gfL[0] = lo.x; gfL[1] = lo.y; gfL[2] = lo.z; gfL[3] = lo.w;
+    gfL[4] = hi.x; gfL[5] = hi.y; gfL[6] = hi.z; gfL[7] = hi.w;
+  }
+  bool any = false;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
-          f32x4 w = ldsv[(oW1F >> 2) + s * 64 + lane];
-          sp[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, feat[s], sp[0], 0, 0, 0);
-          sp[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, feat[s], sp[1], 0, 0, 0);
-          sp[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, feat[s], sp[2], 0, 0, 0);
-          sp[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, feat[s], sp[3], 0, 0, 0);
+  for (int s = 0; s < 8; ++s) any = any || (gfL[s] != 0.0f);
+  if (__ballot(any && ptv)) {
+    // second gather, ONE PLANE AT A TIME: the lines are L1/L2-hot (this wave loaded them for the forward
+    // recompute), and 32 texel registers instead of 96 keep the kernel's register peak - which is here, with all
+    // the weight-gradient accumulators live - under the 256 of two waves per SIMD without spilling
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+      const uint32_t x0 = cxi & 1023u, y0 = (cxi >> 10) & 1023u, z0 = (cxi >> 20) & 1023u;
+      const uint32_t a0 = (pl == 2) ? y0 : x0, b0 = (pl == 0) ? y0 : z0;
+      const uint32_t voff = (uint32_t)pl * P.plane_bytes + __umul24(b0 * (uint32_t)P.res + a0, P.pix_bytes) + (uint32_t)lq * 16u;
+      float tv[4][8];
+      load_texel8<TEX>(P, voff, 0, 0, tv[0]);
+      load_texel8<TEX>(P, voff, P.pix_bytes, 0, tv[1]);
+      load_texel8<TEX>(P, voff, P.row_bytes, 0, tv[2]);
+      load_texel8<TEX>(P, voff, P.row_pix_bytes, 0, tv[3]);
+      const float fa = (pl == 2) ? cfy : cfx, fb = (pl == 0) ? cfy : cfz;
+      const float ga = 1.0f - fa, gb = 1.0f - fb;
+      float dcorner[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) acc = fmaf(gfL[s], tv[c][s], acc);
+        // sum over the 4 lanes (channel chunks) of the point: one DPP quad
+        acc += dpp_f32<kDppQuadXor1>(0.0f, acc);
+        acc += dpp_f32<kDppQuadXor2>(0.0f, acc);
+        dcorner[c] = acc;
+      }
+      const float g_fa = gb * (dcorner[1] - dcorner[0]) + fb * (dcorner[3] - dcorner[2]);
+      const float g_fb = ga * (dcorner[2] - dcorner[0]) + fa * (dcorner[3] - dcorner[1]);
+      // plane 0: (x,y)  plane 1: (x,z)  plane 2: (y,z)
+      gcoord[(pl == 2) ? 1 : 0] += g_fa;
+      gcoord[(pl == 0) ? 1 : 2] += g_fb;
+      __builtin_amdgcn_sched_barrier(0);       // keep the planes' loads from being hoisted together again
+    }
+  }
+  return CoordGrad{gcoord[0], gcoord[1], gcoord[2]};
+}
+
+// ---- step: g_points store (one lane per point; border clamp, scale to scene units, optional F.normalize) ----
+__device__ __forceinline__ void store_g_points(const FieldBwdParams& k, const FieldParams& P, const BwdScene& S, const ChunkPoints& C,
+                                               const BwdTile& T, const CoordGrad& gc) {
+  const int flL = T.flL;
+  const int64_t ptL = C.chunk * 64 + T.srcL;
+  const float sc = (P.res_m1 * 0.5f) / k.scene_range;
+  float* gp = k.g_points + ((size_t)S.scene * k.P + ptL) * 3;
+  float gx = ((flL >> 2) & 1) ? gc.x * sc : 0.0f;
+  float gy = ((flL >> 3) & 1) ? gc.y * sc : 0.0f;
+  float gz = ((flL >> 4) & 1) ? gc.z * sc : 0.0f;
+  if (k.normalize_points) {
+    const float nrm = fmaxf(norm3(gx, gy, gz), 1e-12f);     // F.normalize(x_grad, dim=-1)
+    gx /= nrm; gy /= nrm; gz /= nrm;
+  }
+  gp[0] = gx; gp[1] = gy; gp[2] = gz;
+}
+
+// What the two decoder back ends hold and do alike: the first layer's weight gradient, the sums that come out of staged LDS
+// tiles instead of 32 cross-lane reductions per tile (db1p of lane l = hidden unit l: the column sum of GH_T; dVacc: a
+// 16 x 16 MFMA accumulator whose columns 0..2 are the epilogue's dV and whose column 3 is the LAST layer's bias gradient
+// sum_pt g_o[row] - the weight-gradient MFMAs' A operand against an indicator column), and the block's LDS.
+struct DecoderBwdCommon {
+  f32x4 dW1[4][2];
+  float db1p;
+  f32x4 dVacc;
+  float* lds;                        // forward operand image + attention values
+  float* ldb;                        // backward operand image
+  float* st;                         // this wave's staging
+
+  __device__ __forceinline__ DecoderBwdCommon(float* lds_, float* ldb_, float* st_)
+      : db1p(0.0f), dVacc{0.0f, 0.0f, 0.0f, 0.0f}, lds(lds_), ldb(ldb_), st(st_) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) { dW1[a][0] = f32x4{0, 0, 0, 0}; dW1[a][1] = f32x4{0, 0, 0, 0}; }
+  }
+  __device__ __forceinline__ void stage_forward_image(const FieldBwdParams& k, int scene, int fwd_img) {
+    stage_field_lds(lds, k.image, k.att ? k.att + (size_t)scene * k.A * 3 : nullptr, k.A, fwd_img);
+  }
+  __device__ __forceinline__ void stage_backward_image(const FieldBwdParams& k, int bwd_img) {
+    for (int i = threadIdx.x; i < bwd_img; i += blockDim.x) ldb[i] = k.image_bwd[i];
+    __syncthreads();
+  }
+};
+
+// ================================================================================================
+// The plain decoder's back end: every contraction on the 16-bit matrix pipe with split-fp16 (hi + lo) operands.
+//
+// Weight gradients: dW[m][n] = sum_pt A[m][pt] B[n][pt] has the POINT index on K.  The f32-input MFMA that did this (48
+// per tile) runs at the fp32 vector rate on gfx950 and blocks the VALU while it does (tools/probes/mfma_valu_overlap.hip):
+// 1.5 k of the 7.6 k cycles of a tile.  Now: every operand as fp16 hi + lo in point-major LDS tiles [pt][unit], read back
+// through ds_read_b64_tr_b16 (a 16-lane group's 16 x 8-byte rows come back transposed: lane c gets, as element i, element
+// c & 3 of the row addressed by lane 4 i + (c >> 2) - tools/probes/tr_read.hip), with the two halves of the K = 32 slots of
+// v_mfma_f32_16x16x32_f16 holding the SAME 16 points: A' = [A_hi | A_lo] against [B_hi ; B_hi] and [B_lo ; B_lo] gives
+// (A_hi + A_lo)(B_hi + B_lo) in two MFMAs per 16 x 16 output tile (16 cycles each instead of 4 x 32).
+// Gradient operands have no natural scale, and a weight gradient is a sum over points of very different magnitude: the
+// A side is scaled by a power of two S per accumulator set (sticky: it changes - and the accumulators are rescaled,
+// exactly - only when a tile's largest entry times S leaves [2^-2, 2^14)), so that every entry is resolved to 2^-22 of
+// its TILE's largest entry whatever the loss scale; the accumulators are in units of 1/S until the flush.
+// ================================================================================================
+struct PlainDecoderBwd : DecoderBwdCommon {
+  // operand images in LDS (floats): forward image + attention values, its staged part, the backward image
+  static constexpr int kFwd = kBwdFwdFloats, kFwdImg = kLdsImageFloats, kBwdImg = kBwdImageFloats;
+  static constexpr int kWorkgroupsPerCU = 2;
+  // ---- per-wave LDS: kWaveFloats floats, two regions ----
+  //   R0 [0, 768 floats): F_T fp32 [16][36] of the load -> MFMA layout change, then, over it, the fp16 feature tiles
+  //   R1 [768, 3072 floats), one phase at a time: the epilogue's colour-table scratch (1 536 B) with the fp16 g_o tiles
+  //      behind it and the fp16 activation tiles from 4 608 B on (written by the forward recompute, read by phase A);
+  //      then the fp16 gh tiles and GH_T fp32 [16][68] (phase B); then the feature-gradient rows [16][36] of the hand-off
+  static constexpr int kWaveFloats = 3072;
+  static constexpr int kF = 0, kRows = 768;                                        // floats
+  static constexpr int kPitchF = 96, kPitchH = 144, kPitchO = 32;                  // bytes: row pitch of the [pt][32] / [pt][64] / [pt][16] fp16 tiles
+  static constexpr int kF16Hi = 0, kF16Lo = 16 * kPitchF;                          // bytes, R0: 3 072 B
+  static constexpr int kGH16Hi = kRows * 4, kGH16Lo = kGH16Hi + 16 * kPitchH;      // bytes, phase B
+  static constexpr int kGHT = (kGH16Lo + 16 * kPitchH) / 4;                        // floats, phase B: GH_T fp32 [16][68]
+  static constexpr int kGO16Hi = kRows * 4 + 1536, kGO16Lo = kGO16Hi + 16 * kPitchO;   // bytes, phase A
+  static constexpr int kS16Hi = kRows * 4 + 4608, kS16Lo = kS16Hi + 16 * kPitchH;      // bytes, phase A
+  static_assert(kF16Lo + 16 * kPitchF <= kRows * 4 && kF + 16 * 36 <= kRows, "plain decoder backward: R0 of the per-wave LDS");
+  static_assert(kGO16Lo + 16 * kPitchO <= kS16Hi && (320 + 64) * 4 <= 1536, "plain decoder backward: phase A tiles overlap");
+  static_assert(kGHT + 16 * 68 <= kWaveFloats && kS16Lo + 16 * kPitchH <= kWaveFloats * 4, "plain decoder backward: per-wave LDS");
+
+  // ---- accumulators over all tiles of the wave (natural units; gains and base-2 factors applied at the flush) ----
+  f32x4 dW2[4];
+  // biased exponents of the sticky power-of-two scales of dW2 / column 3 of dVacc and of dW1 (0: not set yet), and of the
+  // largest tile maximum each set has seen
+  int es_go, es_gh, et_max_go, et_max_gh;
+
+  struct Fwd { f32x4 sp[4]; f32x4 o; };    // softplus in base 2 (accumulator layout) and the output rows
+
+  __device__ __forceinline__ PlainDecoderBwd(float* lds_, float* ldb_, float* st_)
+      : DecoderBwdCommon(lds_, ldb_, st_), es_go(0), es_gh(0), et_max_go(0), et_max_gh(0) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) dW2[a] = f32x4{0, 0, 0, 0};
+  }
+
+  // the block's operand images of the scene (all threads; ends with a barrier)
+  __device__ __forceinline__ void enter_scene(const FieldBwdParams& k, int scene) {
+    stage_forward_image(k, scene, kFwdImg);
+    // the forward recompute runs on the split-fp16 fragments (they overlay the fp32 ones, biases stay)
+    __syncthreads();
+    for (int i = threadIdx.x; i < kB1F; i += blockDim.x) lds[i] = k.image[kW1H + i];
+    stage_backward_image(k, kBwdImg);
+  }
+
+  // forward recompute: feature tile (M layout) -> sp, o; leaves the fp16 feature and activation tiles for phases B and A
+  // (the tile's point data is the other back end's need: it looks up the ray of every point)
+  template <int TEX>
+  __device__ __forceinline__ Fwd forward(const FieldBwdParams& k, const BwdTile&, const BwdLane& L, const float (&feat)[8]) {
+    constexpr int kColA = FeatCols<TEX>::kColA, kColB = FeatCols<TEX>::kColB;
+    typedef unsigned long long u64;
+    typedef u64 u64x2 __attribute__((ext_vector_type(2)));
+    const int lane = L.lane, j = L.j, g = L.g;
+    const f32x4* ldsv = reinterpret_cast<const f32x4*>(lds);
+    const u32x4* ldsu = reinterpret_cast<const u32x4*>(lds);
+    Fwd f;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) f.sp[nt] = ldsv[(kB1F >> 2) + g * 4 + nt];
+    // split-fp16 operands (hi + lo, 22 significand bits), fp32 accumulation - as the renderer's tile_mlp<PREC = 1>:
+    // the f32-input MFMA runs at the fp32 VECTOR rate and two waves share the SIMD's matrix pipe, which made the
+    // 144 fp32 MFMAs of a tile half of this kernel's time
+    f16x8 fh, fl;
+    split_f16x8(feat, fh, fl);
+    if (!k.points_only) {
+      // the feature tile in fp16 hi / lo, point-major, over the fp32 tile it was just read from (R0): B operand of dW1
+      wave_lds_fence();
+      char* f16 = reinterpret_cast<char*>(st) + j * kPitchF + 2 * kColA * g;
+      const u64x2 h2 = __builtin_bit_cast(u64x2, fh), l2 = __builtin_bit_cast(u64x2, fl);
+      *reinterpret_cast<u64*>(f16 + kF16Hi) = h2[0]; *reinterpret_cast<u64*>(f16 + kF16Hi + 2 * kColB) = h2[1];
+      *reinterpret_cast<u64*>(f16 + kF16Lo) = l2[0]; *reinterpret_cast<u64*>(f16 + kF16Lo + 2 * kColB) = l2[1];
+    }
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const f16x8 wh = __builtin_bit_cast(f16x8, ldsu[(kW1H_lds >> 2) + (nt * 2 + 0) * 64 + lane]);
+      const f16x8 wl = __builtin_bit_cast(f16x8, ldsu[(kW1H_lds >> 2) + (nt * 2 + 1) * 64 + lane]);
+      f.sp[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, fh, f.sp[nt], 0, 0, 0);
+      f.sp[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, fl, f.sp[nt], 0, 0, 0);
+      f.sp[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, fh, f.sp[nt], 0, 0, 0);
+    }
+    softplus2_tile(f.sp);
+    f.o = ldsv[(kB2F >> 2) + g];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const f16x8 wh = __builtin_bit_cast(f16x8, ldsu[(kW2H_lds >> 2) + (kk * 2 + 0) * 64 + lane]);
+      const f16x8 wl = __builtin_bit_cast(f16x8, ldsu[(kW2H_lds >> 2) + (kk * 2 + 1) * 64 + lane]);
+      const float x8[8] = {f.sp[2 * kk][0], f.sp[2 * kk][1], f.sp[2 * kk][2], f.sp[2 * kk][3],
+                           f.sp[2 * kk + 1][0], f.sp[2 * kk + 1][1], f.sp[2 * kk + 1][2], f.sp[2 * kk + 1][3]};
+      f16x8 sh, sl;
+      split_f16x8(x8, sh, sl);
+      if (!k.points_only) {
+        // the activations' fp16 halves are the B operand of dW2 (phase A): hidden units {32 kk + 4 g + r, 32 kk + 16 + 4 g + r}
+        if (kk == 0) wave_lds_fence();
+        const u64x2 h2 = __builtin_bit_cast(u64x2, sh), l2 = __builtin_bit_cast(u64x2, sl);
+        char* s16 = reinterpret_cast<char*>(st) + j * kPitchH + 2 * (32 * kk + 4 * g);
+        *reinterpret_cast<u64*>(s16 + kS16Hi) = h2[0]; *reinterpret_cast<u64*>(s16 + kS16Hi + 32) = h2[1];
+        *reinterpret_cast<u64*>(s16 + kS16Lo) = l2[0]; *reinterpret_cast<u64*>(s16 + kS16Lo + 32) = l2[1];
+      }
+      f.o = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, sh, f.o, 0, 0, 0);
+      f.o = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, sl, f.o, 0, 0, 0);
+      f.o = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, sh, f.o, 0, 0, 0);
+    }
+    return f;
+  }
+
+  // backward: g_o -> gh = (W2^T g_o^T) * sigmoid(h) -> gf^T = W1^T gh^T, with dW2 / the bias column (phase A) and dW1 / db1
+  // (phase B) accumulated on the way
+  __device__ __forceinline__ FeatureGrad backward(const FieldBwdParams& k, const BwdLane& L, const f32x4& go, const Fwd& f) {
+    typedef unsigned long long u64;
+    typedef u64 u64x2 __attribute__((ext_vector_type(2)));
+    const int lane = L.lane, j = L.j, g = L.g;
+    // lane (g, j) addresses row 8 (g & 1) + (j >> 2) [+ 4 for the second read], columns 4 (j & 3) .. + 3 of a tile and
+    // receives points 8 (g & 1) .. + 7 of column j; lanes g >= 2 (K slots 16 .. 31) take the A side from the lo tile
+    const int rowb = 8 * (g & 1) + (j >> 2), colb = 8 * (j & 3), a_lo = g >> 1;
+    const char* wb = reinterpret_cast<const char*>(st);
+    // ---------------- gs^T = W2^T g_o^T ; gh = gs * sigmoid(h) ----------------
+    // The split-fp16 operands resolve 2^-24 absolute (split_f16x8), and an upstream gradient has no natural scale
+    // (a mean-squared-error loss over 10^4 pixels hands down 1e-6): every point's column is scaled by a power of
+    // two into [1, 2) before the split and the fp32 accumulator is scaled back - exact, and the result then carries
+    // fp32-like precision relative to the column's largest entry whatever the loss scale.
+    f16x8 go_h, go_l;
+    float go_inv = 1.0f, am_go = 0.0f;
+    {
+      float am = fmaxf(fmaxf(fabsf(go[0]), fabsf(go[1])), fmaxf(fabsf(go[2]), fabsf(go[3])));
+      am = max_xor32(max_xor16(am));                       // over the 16 rows of point j
+      am_go = am;
+      float sc;
+      pow2_normaliser(am, sc, go_inv);
+      const float x8[8] = {go[0] * sc, go[1] * sc, go[2] * sc, go[3] * sc, 0.0f, 0.0f, 0.0f, 0.0f};
+      split_f16x8(x8, go_h, go_l);
+    }
+    if (!k.points_only) {
+      // ---------------- phase A: dW2[row][hid] += sum_pt g_o[row][pt] s[hid][pt] ; column 3 of dVacc += sum_pt g_o[row][pt] ----------------
+      {
+        const float fac = sticky_scale(am_go, es_go, et_max_go);
+        if (fac != 1.0f) {
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt) dW2[nt] *= fac;
+          dVacc *= (j == 3) ? fac : 1.0f;
         }
-      } else {
-        // split-fp16 operands (hi + lo, 22 significand bits), fp32 accumulation - as the renderer's tile_mlp<PREC = 1>:
-        // the f32-input MFMA runs at the fp32 VECTOR rate and two waves share the SIMD's matrix pipe, which made the
-        // 144 fp32 MFMAs of a tile half of this kernel's time
-        f16x8 fh, fl;
-        split_f16x8(feat, fh, fl);
-        if (!k.points_only) {
-          // the feature tile in fp16 hi / lo, point-major, over the fp32 tile it was just read from (R0): B operand of dW1
-          wave_lds_fence();
-          char* f16 = reinterpret_cast<char*>(st) + j * kW16F + 2 * kColA * g;
-          typedef unsigned long long u64;
-          const auto h2 = __builtin_bit_cast(__attribute__((ext_vector_type(2))) u64, fh);
-          const auto l2 = __builtin_bit_cast(__attribute__((ext_vector_type(2))) u64, fl);
-          *reinterpret_cast<u64*>(f16 + kF16Hi) = h2[0]; *reinterpret_cast<u64*>(f16 + kF16Hi + 2 * kColB) = h2[1];
-          *reinterpret_cast<u64*>(f16 + kF16Lo) = l2[0]; *reinterpret_cast<u64*>(f16 + kF16Lo + 2 * kColB) = l2[1];
-        }
+      }
+      {
+        typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
+        const uint32_t r_go = ratio_f16x2(es_go, go_inv);
+        const f16x4v rr = __builtin_bit_cast(f16x4v, (__attribute__((ext_vector_type(2))) uint32_t){r_go, r_go});
+        const f16x4v gh4 = __builtin_shufflevector(go_h, go_h, 0, 1, 2, 3) * rr, gl4 = __builtin_shufflevector(go_l, go_l, 0, 1, 2, 3) * rr;
+        char* t16 = reinterpret_cast<char*>(st) + j * kPitchO + 8 * g;                 // rows 4 g + r of point j
+        *reinterpret_cast<u64*>(t16 + kGO16Hi) = __builtin_bit_cast(u64, gh4);
+        *reinterpret_cast<u64*>(t16 + kGO16Lo) = __builtin_bit_cast(u64, gl4);
+      }
+      wave_lds_fence();
+      {
+        const f16x8 a = lds_read_tr16x2(wb + (a_lo ? kGO16Lo : kGO16Hi) + rowb * kPitchO + colb, 4 * kPitchO);
+        const _Float16 one = (j == 3) ? (_Float16)1.0f : (_Float16)0.0f;
+        const f16x8 ind = {one, one, one, one, one, one, one, one};
+        dVacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, ind, dVacc, 0, 0, 0);       // (g_o hi + g_o lo) . 1
+        const char* ps = wb + rowb * kPitchH + colb;
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-          const f16x8 wh = __builtin_bit_cast(f16x8, ldsu[(kW1H_lds >> 2) + (nt * 2 + 0) * 64 + lane]);
-          const f16x8 wl = __builtin_bit_cast(f16x8, ldsu[(kW1H_lds >> 2) + (nt * 2 + 1) * 64 + lane]);
-          sp[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, fh, sp[nt], 0, 0, 0);
-          sp[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, fl, sp[nt], 0, 0, 0);
-          sp[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, fh, sp[nt], 0, 0, 0);
+          const f16x8 bh = lds_read_tr16x2(ps + kS16Hi + 32 * nt, 4 * kPitchH);
+          const f16x8 bl = lds_read_tr16x2(ps + kS16Lo + 32 * nt, 4 * kPitchH);
+          dW2[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bh, dW2[nt], 0, 0, 0);
+          dW2[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bl, dW2[nt], 0, 0, 0);
         }
       }
+    }
+    f32x4 gh[4];
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
+    for (int mt = 0; mt < 4; ++mt) {
+      f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+      // K = the 16 output rows, in the low half of the K = 32 slots (see decoder_pack_bwd_kernel)
+      const u32x4* wq = reinterpret_cast<const u32x4*>(ldb + kBwdW2T);
+      const f16x8 wh = __builtin_bit_cast(f16x8, wq[(mt * 2 + 0) * 64 + lane]);
+      const f16x8 wl = __builtin_bit_cast(f16x8, wq[(mt * 2 + 1) * 64 + lane]);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, go_h, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, go_l, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, go_h, acc, 0, 0, 0);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float h = sp[nt][r];
-          float s2 = __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(h));
-          sp[nt][r] = __builtin_amdgcn_fmed3f(s2, h, 128.0f);     // == (h > thr ? h : s2) wherever the two differ in fp32 (tile_mlp)
-        }
-      f32x4 o;
-      f32x4 o2[3], yv[3];          // VD: second-layer outputs (48 rows) and the third layer's input
-      int ray_j = 0;
-      if constexpr (VD) {
-        ray_j = (flM & 2) ? (int)(ptM / k.spr) : 0;
-#pragma unroll
-        for (int t2 = 0; t2 < 3; ++t2) o2[t2] = ldsv[(kVdB2 >> 2) + t2 * 4 + g];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int t2 = 0; t2 < 3; ++t2) {
-            const f32x4 w = ldsv[(kVdW2 >> 2) + (t2 * 4 + nt) * 64 + lane];
-            o2[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, sp[nt][0], o2[t2], 0, 0, 0);
-            o2[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, sp[nt][1], o2[t2], 0, 0, 0);
-            o2[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, sp[nt][2], o2[t2], 0, 0, 0);
-            o2[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, sp[nt][3], o2[t2], 0, 0, 0);
-          }
-        f32x4 oa = ldsv[(kVdB3 >> 2) + g], ob = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int t2 = 0; t2 < 3; ++t2) {
-          const f32x4 xr = *reinterpret_cast<const f32x4*>(xray_scene + (size_t)ray_j * kRayFeatPad + 16 * t2 + 4 * g);
-          const f32x4 w = ldsv[(kVdW3 >> 2) + t2 * 64 + lane];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float v = o2[t2][r] + xr[r];
-            yv[t2][r] = (v > 0.0f) ? v : v * 0.2f;
-            o2[t2][r] = v;                                  // keep the pre-activation for leaky_relu'
-          }
-          if (t2 == 0 && g == 0) yv[0][0] = o2[0][0];          // distance row passes through (padded xr[0] == 0)
-          oa = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, yv[t2][0], oa, 0, 0, 0);
-          ob = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, yv[t2][1], ob, 0, 0, 0);
-          oa = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, yv[t2][2], oa, 0, 0, 0);
-          ob = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, yv[t2][3], ob, 0, 0, 0);
-        }
-        o = oa + ob;
-      } else {
-        o = ldsv[(kB2F >> 2) + g];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const f16x8 wh = __builtin_bit_cast(f16x8, ldsu[(kW2H_lds >> 2) + (kk * 2 + 0) * 64 + lane]);
-          const f16x8 wl = __builtin_bit_cast(f16x8, ldsu[(kW2H_lds >> 2) + (kk * 2 + 1) * 64 + lane]);
-          const float x8[8] = {sp[2 * kk][0], sp[2 * kk][1], sp[2 * kk][2], sp[2 * kk][3],
-                               sp[2 * kk + 1][0], sp[2 * kk + 1][1], sp[2 * kk + 1][2], sp[2 * kk + 1][3]};
-          f16x8 sh, sl;
-          split_f16x8(x8, sh, sl);
-          if (!k.points_only) {
-            // the activations' fp16 halves are the B operand of dW2 (phase A): hidden units {32 kk + 4 g + r, 32 kk + 16 + 4 g + r}
-            typedef unsigned long long u64;
-            typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-            if (kk == 0) wave_lds_fence();
-            const u64x2 h2 = __builtin_bit_cast(u64x2, sh), l2 = __builtin_bit_cast(u64x2, sl);
-            char* s16 = reinterpret_cast<char*>(st) + j * kW16H + 2 * (32 * kk + 4 * g);
-            *reinterpret_cast<u64*>(s16 + kS16Hi) = h2[0]; *reinterpret_cast<u64*>(s16 + kS16Hi + 32) = h2[1];
-            *reinterpret_cast<u64*>(s16 + kS16Lo) = l2[0]; *reinterpret_cast<u64*>(s16 + kS16Lo + 32) = l2[1];
-          }
-          o = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, sh, o, 0, 0, 0);
-          o = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, sl, o, 0, 0, 0);
-          o = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, sh, o, 0, 0, 0);
-        }
+      for (int r = 0; r < 4; ++r) {
+        const float sig = 1.0f - __builtin_amdgcn_exp2f(-f.sp[mt][r]);   // sigmoid(h) = 1 - exp(-softplus(h))
+        gh[mt][r] = (acc[r] * go_inv) * sig;
       }
+    }
 
-      // ---------------- epilogue backward: upstream gradients -> g_o (rows 4g+r of point j) ----------------
-      const float keep = (flM & 1) ? 0.0f : 1.0f;          // 1 - outside
-      const uint32_t ptU = (uint32_t)ptM;
-      const float gsig = pv ? gsig_sc[ptU] : 0.0f;
-      float grgb[3] = {0.0f, 0.0f, 0.0f};
-      if (pv) { grgb[0] = grgb_sc[ptU * 3u]; grgb[1] = grgb_sc[ptU * 3u + 1u]; grgb[2] = grgb_sc[ptU * 3u + 2u]; }
-      f32x4 go = {0.0f, 0.0f, 0.0f, 0.0f};
-      const float sdf = bcast_row0(o.x);
-      float g_d = (pv && gsdf_sc) ? gsdf_sc[ptU] : 0.0f;
-      if (k.use_sdf) {
-        // sigma = (1/alpha) * cdf(-d) * keep,  cdf(x) = 0.5 + 0.5 sign(x) (1 - exp(-|x|/beta))
-        const float ad = fabsf(sdf);
-        const float e = __builtin_amdgcn_exp2f(ad * P.neg_log2e_over_beta);
-        const float sgn = (sdf < 0.0f) ? 1.0f : ((sdf > 0.0f) ? -1.0f : 0.0f);   // sign(-d)
-        const float cdf = 0.5f + 0.5f * sgn * (1.0f - e);
-        g_d += (sdf != 0.0f) ? gsig * (-(P.inv_alpha * keep) * (0.5f / P.beta) * e) : 0.0f;   // torch.sign(0) == 0
-        if (g == 0) {
-          d_beta += gsig * (P.inv_alpha * keep) * (-0.5f * sgn * ad * e / (P.beta * P.beta));
-          d_alpha += gsig * (-(P.inv_alpha * cdf * keep) / alpha_v);
-        }
-      } else {
-        const float dd = sdf - 1.0f;
-        g_d += gsig * keep * (1.0f / (1.0f + __expf(-dd)));
+    // ---------------- gf^T = W1^T gh^T  (rows = channels, accumulator layout == feature layout M) ----------------
+    FeatureGrad out{{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}, 1.0f};
+    const u32x4* ldbu = reinterpret_cast<const u32x4*>(ldb + kBwdW1T);
+    float am = 0.0f, sc;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) am = fmaxf(am, fabsf(gh[mt][r]));
+    am = max_xor32(max_xor16(am));                       // over the 64 hidden units of point j
+    pow2_normaliser(am, sc, out.gf_inv);
+    uint32_t r_gh = 0u;
+    if (!k.points_only) {
+      // phase B staging (R1 is free: the colour-table MFMAs are done): GH_T fp32 for the bias column sums, and below
+      // the tile-scaled fp16 halves of gh as the A operand of dW1
+      const float fac = sticky_scale(am, es_gh, et_max_gh);
+      if (fac != 1.0f) {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) { dW1[nt][0] *= fac; dW1[nt][1] *= fac; }
       }
-      if constexpr (ATT) {
-        float m = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { int row = 4 * g + r; m = (row >= 1 && row <= A) ? fmaxf(m, o[r]) : m; }
-        m = max_xor32(max_xor16(m));
-        const f32x4* vf = reinterpret_cast<const f32x4*>(P.vf) + g * 4;
-        float pe[4], gp[4], se = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int row = 4 * g + r;
-          bool rv = (row >= 1) && (row <= A);
-          pe[r] = rv ? __builtin_amdgcn_exp2f(o[r] - m) : 0.0f;
-          se += pe[r];
-          f32x4 v = vf[r];
-          gp[r] = (grgb[0] * v.x + grgb[1] * v.y) + grgb[2] * v.z;
-          if (rv && pv && k.g_sem) gp[r] += k.g_sem[giM * A + (row - 1)];
-        }
-        se = sum_xor32(sum_xor16(se));
-        const float inv = 1.0f / se;
-        float dot = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { pe[r] *= inv; dot += pe[r] * gp[r]; }
-        dot = sum_xor32(sum_xor16(dot));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          go[r] = pe[r] * (gp[r] - dot);                      // d/d(feature), natural units
-        }
-        if (!k.points_only) {
-          // dV[row][c] += sum_pt p[row][pt] g_rgb[c][pt] on the matrix pipe: P_T [pt][row] and the tile's g_rgb [pt][4]
-          // go through the (free at this point) S_T rows
-          wave_lds_fence();
-          *reinterpret_cast<f32x4*>(st + oR1 + j * 20 + 4 * g) = f32x4{pe[0], pe[1], pe[2], pe[3]};
-          if (g == 0) *reinterpret_cast<f32x4*>(st + oR1 + 320 + j * 4) = f32x4{grgb[0], grgb[1], grgb[2], 0.0f};
-          wave_lds_fence();
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) {
-            const int pt = 4 * ks + g;
-            const float a_p = st[oR1 + pt * 20 + j];
-            const float b_g = st[oR1 + 320 + pt * 4 + (j & 3)];
-            dVacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a_p, (j < 4) ? b_g : 0.0f, dVacc, 0, 0, 0);
-          }
-          wave_lds_fence();
-        }
-      } else {
-        // rgb = 2.004 sigmoid(f) - 1.002 ; rows 1..3 live in group 0
-        if (g == 0) {
-          const float f3[3] = {o.y, o.z, o.w};
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            float sgm = 1.0f / (1.0f + __builtin_amdgcn_exp2f(-f3[c]));
-            go[1 + c] = grgb[c] * 2.004f * sgm * (1.0f - sgm);
-          }
-        }
-      }
-      if (g == 0) go[0] = g_d;
-
-      // ---------------- VD: gy^T = W3'^T g_o^T ; g_o2 = gy * leaky_relu'(x_ray + f) ----------------
-      f32x4 go2[3];
-      if constexpr (VD) {
-#pragma unroll
-        for (int t2 = 0; t2 < 3; ++t2) {
-          const f32x4 w = ldbv[(kVbW3T >> 2) + t2 * 64 + lane];
-          f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, go[0], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, go[1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, go[2], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, go[3], acc, 0, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) go2[t2][r] = acc[r] * ((o2[t2][r] > 0.0f) ? 1.0f : 0.2f);
-          if (t2 == 0 && g == 0) go2[0][0] = acc[0];                     // distance row: identity
-          db2v[t2] += go2[t2];
-        }
-        // gradient of the per-ray feature: sum over the samples of the ray
-        if (gxray_scene) {
-          const int r0 = __builtin_amdgcn_readfirstlane(ray_j);
-          const bool uniform = __all(ray_j == r0);
-#pragma unroll
-          for (int t2 = 0; t2 < 3; ++t2)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int kk = 16 * t2 + 4 * g + r;
-              float v = go2[t2][r];
-              if (uniform) v = row_allreduce_sum(v);
-              if (kk >= 1 && kk <= 32 && v != 0.0f && (!uniform || j == 0))
-                unsafeAtomicAdd(gxray_scene + (size_t)ray_j * kRayFeatPad + kk, v);
-            }
-        }
-      }
-      // ---------------- gs^T = W2^T g_o^T ; gh = gs * sigmoid(h) ----------------
-      // The split-fp16 operands resolve 2^-24 absolute (split_f16x8), and an upstream gradient has no natural scale
-      // (a mean-squared-error loss over 10^4 pixels hands down 1e-6): every point's column is scaled by a power of
-      // two into [1, 2) before the split and the fp32 accumulator is scaled back - exact, and the result then carries
-      // fp32-like precision relative to the column's largest entry whatever the loss scale.
-      f16x8 go_h, go_l;
-      float go_inv = 1.0f, am_go = 0.0f;
-      if constexpr (!VD) {
-        float am = fmaxf(fmaxf(fabsf(go[0]), fabsf(go[1])), fmaxf(fabsf(go[2]), fabsf(go[3])));
-        am = max_xor32(max_xor16(am));                       // over the 16 rows of point j
-        am_go = am;
-        float sc;
-        pow2_normaliser(am, sc, go_inv);
-        const float x8[8] = {go[0] * sc, go[1] * sc, go[2] * sc, go[3] * sc, 0.0f, 0.0f, 0.0f, 0.0f};
-        split_f16x8(x8, go_h, go_l);
-      }
-      if constexpr (!VD) {
-        if (!k.points_only) {
-          // ---------------- phase A: dW2[row][hid] += sum_pt g_o[row][pt] s[hid][pt] ; column 3 of dVacc += sum_pt g_o[row][pt] ----------------
-          typedef unsigned long long u64;
-          const int rowb = 8 * (g & 1) + (j >> 2), colb = 8 * (j & 3), a_lo = g >> 1;
-          const char* wb = reinterpret_cast<const char*>(st);
-          {
-            const float fac = sticky_scale(am_go, es_go, et_max_go);
-            if (fac != 1.0f) {
-#pragma unroll
-              for (int nt = 0; nt < 4; ++nt) dW2[0][nt] *= fac;
-              dVacc *= (j == 3) ? fac : 1.0f;
-            }
-          }
-          {
-            typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-            const uint32_t r_go = ratio_f16x2(es_go, go_inv);
-            const f16x4v rr = __builtin_bit_cast(f16x4v, (__attribute__((ext_vector_type(2))) uint32_t){r_go, r_go});
-            const f16x4v gh4 = __builtin_shufflevector(go_h, go_h, 0, 1, 2, 3) * rr, gl4 = __builtin_shufflevector(go_l, go_l, 0, 1, 2, 3) * rr;
-            char* t16 = reinterpret_cast<char*>(st) + j * kW16O + 8 * g;                 // rows 4 g + r of point j
-            *reinterpret_cast<u64*>(t16 + kGO16Hi) = __builtin_bit_cast(u64, gh4);
-            *reinterpret_cast<u64*>(t16 + kGO16Lo) = __builtin_bit_cast(u64, gl4);
-          }
-          wave_lds_fence();
-          {
-            const f16x8 a = lds_read_tr16x2(wb + (a_lo ? kGO16Lo : kGO16Hi) + rowb * kW16O + colb, 4 * kW16O);
-            const _Float16 one = (j == 3) ? (_Float16)1.0f : (_Float16)0.0f;
-            const f16x8 ind = {one, one, one, one, one, one, one, one};
-            dVacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, ind, dVacc, 0, 0, 0);       // (g_o hi + g_o lo) . 1
-            const char* ps = wb + rowb * kW16H + colb;
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-              const f16x8 bh = lds_read_tr16x2(ps + kS16Hi + 32 * nt, 4 * kW16H);
-              const f16x8 bl = lds_read_tr16x2(ps + kS16Lo + 32 * nt, 4 * kW16H);
-              dW2[0][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bh, dW2[0][nt], 0, 0, 0);
-              dW2[0][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bl, dW2[0][nt], 0, 0, 0);
-            }
-          }
-        }
-      }
-      f32x4 gh[4];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (VD) {
-#pragma unroll
-          for (int t2 = 0; t2 < 3; ++t2) {
-            const f32x4 w = ldbv[(kVbW2T >> 2) + (mt * 3 + t2) * 64 + lane];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, go2[t2][0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, go2[t2][1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, go2[t2][2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, go2[t2][3], acc, 0, 0, 0);
-          }
-        } else {
-          // K = the 16 output rows, in the low half of the K = 32 slots (see decoder_pack_bwd_kernel)
-          const u32x4* wq = reinterpret_cast<const u32x4*>(ldb + kBwdW2T);
-          const f16x8 wh = __builtin_bit_cast(f16x8, wq[(mt * 2 + 0) * 64 + lane]);
-          const f16x8 wl = __builtin_bit_cast(f16x8, wq[(mt * 2 + 1) * 64 + lane]);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, go_h, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, go_l, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, go_h, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float sig = 1.0f - __builtin_amdgcn_exp2f(-sp[mt][r]);   // sigmoid(h) = 1 - exp(-softplus(h))
-          gh[mt][r] = (VD ? acc[r] : acc[r] * go_inv) * sig;
-        }
-      }
-
-      // ---------------- stage transposed operands: GO_T [pt][row], S_T [pt][hid], GH_T [pt][hid] ----------------
-      if constexpr (VD) {
-      if (!k.points_only) {
+      r_gh = ratio_f16x2(es_gh, out.gf_inv);
       wave_lds_fence();
-      *reinterpret_cast<f32x4*>(st + kStGO + j * 20 + 4 * g) = go;
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) *reinterpret_cast<f32x4*>(st + kGHT + j * 68 + 16 * nt + 4 * g) = gh[nt];
+    }
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const float x8[8] = {gh[2 * kk][0] * sc, gh[2 * kk][1] * sc, gh[2 * kk][2] * sc, gh[2 * kk][3] * sc,
+                           gh[2 * kk + 1][0] * sc, gh[2 * kk + 1][1] * sc, gh[2 * kk + 1][2] * sc, gh[2 * kk + 1][3] * sc};
+      f16x8 xh, xl;
+      split_f16x8(x8, xh, xl);
+      if (!k.points_only) {
+        // hidden units {32 kk + 4 g + r, 32 kk + 16 + 4 g + r} of point j
+        const f16x8 rr = __builtin_bit_cast(f16x8, u32x4{r_gh, r_gh, r_gh, r_gh});
+        const u64x2 h2 = __builtin_bit_cast(u64x2, xh * rr), l2 = __builtin_bit_cast(u64x2, xl * rr);
+        char* t16 = reinterpret_cast<char*>(st) + j * kPitchH + 2 * (32 * kk + 4 * g);
+        *reinterpret_cast<u64*>(t16 + kGH16Hi) = h2[0]; *reinterpret_cast<u64*>(t16 + kGH16Hi + 32) = h2[1];
+        *reinterpret_cast<u64*>(t16 + kGH16Lo) = l2[0]; *reinterpret_cast<u64*>(t16 + kGH16Lo + 32) = l2[1];
+      }
+      const f16x8 ah = __builtin_bit_cast(f16x8, ldbu[((0 * 2 + kk) * 2 + 0) * 64 + lane]);
+      const f16x8 al = __builtin_bit_cast(f16x8, ldbu[((0 * 2 + kk) * 2 + 1) * 64 + lane]);
+      const f16x8 bh = __builtin_bit_cast(f16x8, ldbu[((1 * 2 + kk) * 2 + 0) * 64 + lane]);
+      const f16x8 bl = __builtin_bit_cast(f16x8, ldbu[((1 * 2 + kk) * 2 + 1) * 64 + lane]);
+      out.gf0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xh, out.gf0, 0, 0, 0);
+      out.gf1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh, xh, out.gf1, 0, 0, 0);
+      out.gf0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xl, out.gf0, 0, 0, 0);
+      out.gf1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh, xl, out.gf1, 0, 0, 0);
+      out.gf0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, xh, out.gf0, 0, 0, 0);
+      out.gf1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl, xh, out.gf1, 0, 0, 0);
+    }
+    if (!k.points_only) {
+      // ---------------- phase B: db1 += column sums of GH_T ; dW1[hid][ch] += sum_pt gh[hid][pt] f[ch][pt] ----------------
+      wave_lds_fence();
+      {
+        float cs = 0.0f;
+#pragma unroll
+        for (int pt = 0; pt < 16; ++pt) cs += st[kGHT + pt * 68 + lane];
+        db1p += cs;
+      }
+      {
+        const char* pf = wb + rowb * kPitchF + colb;
+        f16x8 bfh[2], bfl[2];
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) {
+          bfh[n2] = lds_read_tr16x2(pf + kF16Hi + 32 * n2, 4 * kPitchF);
+          bfl[n2] = lds_read_tr16x2(pf + kF16Lo + 32 * n2, 4 * kPitchF);
+        }
+        const char* pa = wb + (a_lo ? kGH16Lo : kGH16Hi) + rowb * kPitchH + colb;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+          const f16x8 a = lds_read_tr16x2(pa + 32 * nt, 4 * kPitchH);
+#pragma unroll
+          for (int n2 = 0; n2 < 2; ++n2) {
+            dW1[nt][n2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bfh[n2], dW1[nt][n2], 0, 0, 0);
+            dW1[nt][n2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bfl[n2], dW1[nt][n2], 0, 0, 0);
+          }
+        }
+      }
+    }
+    return out;
+  }
+
+  // flush: g_w1, g_w2, g_b1, g_b2 (the accumulators are in units of 1 / their sticky scale)
+  __device__ __forceinline__ void flush(const FieldBwdParams& k, const BwdLane& L) {
+    const int lane = L.lane, j = L.j, g = L.g;
+    const int n_out = k.A > 0 ? 1 + k.A : 4;
+    const float g1 = 0.17677669529663687f, g2 = 0.125f;
+    const float un_gh = (es_gh == 0) ? 1.0f : bits2f((uint32_t)(254 - es_gh) << 23);
+    const float un_go = (es_go == 0) ? 1.0f : bits2f((uint32_t)(254 - es_go) << 23);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        // dW1[hid = 16nt+4g+r][ch = 16*n2 + j] ; feat was the SUM of three planes -> /3
+        atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * kC + j], dW1[nt][0][r] * (g1 / 3.0f) * un_gh);
+        atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * kC + 16 + j], dW1[nt][1][r] * (g1 / 3.0f) * un_gh);
+        // dW2[row = 4g+r][hid = 16nt + j] ; s = sp2 * ln2
+        const int row = 4 * g + r;
+        if (row < n_out) atomicAdd(&k.g_w2[row * kHidden + 16 * nt + j], dW2[nt][r] * (g2 * kLn2) * un_go);
+      }
+    }
+    atomicAdd(&k.g_b1[lane], db1p);                                   // one hidden unit per lane (see db1p above)
+    if (j == 3) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 4 * g + r;                                    // column 3 of dVacc: the bias gradient of the row
+        if (row < n_out) atomicAdd(&k.g_b2[row], dVacc[r] * un_go);
+      }
+    }
+  }
+};
+
+// ================================================================================================
+// The view-direction decoder's back end: three layers (hidden 64 -> 33 second-layer rows + the per-ray feature ->
+// leaky_relu -> the mapper's `output` Linear(32, n3)), every contraction on v_mfma_f32_16x16x4_f32:
+//
+//   gy^T [48x16] = W3'^T [48x16] g_o^T [16x16]     12 MFMA   (operands in accumulator layout)
+//   gs^T [64x16] = W2^T  [64x48] g_o2^T [48x16]    48 MFMA
+//   gf^T [32x16] = W1^T  [32x64] gh^T  [64x16]     32 MFMA
+//   dW3 / dW2 / dW1 / bias columns: points along K, operands staged in LDS as fp32 tiles [pt][unit]
+// ================================================================================================
+struct ViewdirDecoderBwd : DecoderBwdCommon {
+  static constexpr int kFwd = kVdFieldLdsFloats, kFwdImg = kVdImageFloats, kBwdImg = kVbImageFloats;
+  static constexpr int kWorkgroupsPerCU = 1;         // 512 VGPRs per lane: the accumulators of three layers
+  // ---- per-wave LDS (floats): F_T [16][36], GO_T [16][20], S_T [16][68], GH_T [16][68], Y_T [16][52] (third-layer
+  // input), GO2_T [16][52] (second-layer output gradient).  S_T is free outside the staging block: the epilogue's
+  // colour-table scratch and the feature-gradient rows [16][36] of the hand-off live there (kRows) ----
+  static constexpr int kF = 0, kGO = kF + 16 * 36, kS = kGO + 16 * 20, kGH = kS + 16 * 68, kY = kGH + 16 * 68, kGO2 = kY + 16 * 52;
+  static constexpr int kWaveFloats = kGO2 + 16 * 52;
+  static constexpr int kRows = kS;
+  static_assert(kF + 16 * 36 <= kGO && kRows + 16 * 36 <= kGH && kRows + 320 + 16 * 4 <= kGH,
+                "view-direction decoder backward: the feature tile, the gradient rows and the colour-table scratch in their tiles");
+
+  // ---- accumulators (natural units; gains applied at the flush) ----
+  f32x4 dW2[3][4];                   // three 16-row tiles of the second layer's output
+  f32x4 dW3[3], db2v[3];             // third-layer weights, second-layer bias
+  const float* xray_scene;           // the scene's per-ray features and their gradient (null: not wanted)
+  float* gxray_scene;
+
+  // softplus in base 2, the output rows, the second layer's pre-activations (48 rows) and the third layer's input
+  struct Fwd { f32x4 sp[4]; f32x4 o; f32x4 o2[3], yv[3]; int ray_j; };
+
+  __device__ __forceinline__ ViewdirDecoderBwd(float* lds_, float* ldb_, float* st_)
+      : DecoderBwdCommon(lds_, ldb_, st_), xray_scene(nullptr), gxray_scene(nullptr) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+#pragma unroll
+      for (int t2 = 0; t2 < 3; ++t2) dW2[t2][a] = f32x4{0, 0, 0, 0};
+      if (a < 3) { dW3[a] = f32x4{0, 0, 0, 0}; db2v[a] = f32x4{0, 0, 0, 0}; }
+    }
+  }
+
+  // the block's operand images of the scene (all threads; ends with a barrier) and the scene's ray features
+  __device__ __forceinline__ void enter_scene(const FieldBwdParams& k, int scene) {
+    stage_forward_image(k, scene, kFwdImg);
+    stage_backward_image(k, kBwdImg);
+    xray_scene = k.xray + (size_t)scene * (size_t)(k.P / k.spr) * kRayFeatPad;
+    gxray_scene = k.g_xray ? k.g_xray + (size_t)scene * (size_t)(k.P / k.spr) * kRayFeatPad : nullptr;
+  }
+
+  template <int TEX>
+  __device__ __forceinline__ Fwd forward(const FieldBwdParams& k, const BwdTile& T, const BwdLane& L, const float (&feat)[8]) {
+    const int lane = L.lane, g = L.g;
+    const f32x4* ldsv = reinterpret_cast<const f32x4*>(lds);
+    Fwd f;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) f.sp[nt] = ldsv[(kVdB1F >> 2) + g * 4 + nt];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      f32x4 w = ldsv[(kVdW1F >> 2) + s * 64 + lane];
+      f.sp[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, feat[s], f.sp[0], 0, 0, 0);
+      f.sp[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, feat[s], f.sp[1], 0, 0, 0);
+      f.sp[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, feat[s], f.sp[2], 0, 0, 0);
+      f.sp[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, feat[s], f.sp[3], 0, 0, 0);
+    }
+    softplus2_tile(f.sp);
+    f.ray_j = (T.flM & 2) ? (int)(T.ptM / k.spr) : 0;
+#pragma unroll
+    for (int t2 = 0; t2 < 3; ++t2) f.o2[t2] = ldsv[(kVdB2 >> 2) + t2 * 4 + g];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int t2 = 0; t2 < 3; ++t2) {
+        const f32x4 w = ldsv[(kVdW2 >> 2) + (t2 * 4 + nt) * 64 + lane];
+        f.o2[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, f.sp[nt][0], f.o2[t2], 0, 0, 0);
+        f.o2[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, f.sp[nt][1], f.o2[t2], 0, 0, 0);
+        f.o2[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, f.sp[nt][2], f.o2[t2], 0, 0, 0);
+        f.o2[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, f.sp[nt][3], f.o2[t2], 0, 0, 0);
+      }
+    f32x4 oa = ldsv[(kVdB3 >> 2) + g], ob = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int t2 = 0; t2 < 3; ++t2) {
+      const f32x4 xr = *reinterpret_cast<const f32x4*>(xray_scene + (size_t)f.ray_j * kRayFeatPad + 16 * t2 + 4 * g);
+      const f32x4 w = ldsv[(kVdW3 >> 2) + t2 * 64 + lane];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = f.o2[t2][r] + xr[r];
+        f.yv[t2][r] = (v > 0.0f) ? v : v * 0.2f;
+        f.o2[t2][r] = v;                                  // keep the pre-activation for leaky_relu'
+      }
+      if (t2 == 0 && g == 0) f.yv[0][0] = f.o2[0][0];          // distance row passes through (padded xr[0] == 0)
+      oa = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, f.yv[t2][0], oa, 0, 0, 0);
+      ob = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, f.yv[t2][1], ob, 0, 0, 0);
+      oa = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, f.yv[t2][2], oa, 0, 0, 0);
+      ob = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, f.yv[t2][3], ob, 0, 0, 0);
+    }
+    f.o = oa + ob;
+    return f;
+  }
+
+  __device__ __forceinline__ FeatureGrad backward(const FieldBwdParams& k, const BwdLane& L, const f32x4& go, const Fwd& f) {
+    const int lane = L.lane, j = L.j, g = L.g;
+    const f32x4* ldbv = reinterpret_cast<const f32x4*>(ldb);
+    // ---------------- gy^T = W3'^T g_o^T ; g_o2 = gy * leaky_relu'(x_ray + f) ----------------
+    f32x4 go2[3];
+#pragma unroll
+    for (int t2 = 0; t2 < 3; ++t2) {
+      const f32x4 w = ldbv[(kVbW3T >> 2) + t2 * 64 + lane];
+      f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, go[0], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, go[1], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, go[2], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, go[3], acc, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) go2[t2][r] = acc[r] * ((f.o2[t2][r] > 0.0f) ? 1.0f : 0.2f);
+      if (t2 == 0 && g == 0) go2[0][0] = acc[0];                     // distance row: identity
+      db2v[t2] += go2[t2];
+    }
+    // gradient of the per-ray feature: sum over the samples of the ray
+    if (gxray_scene) {
+      const int ray_j = f.ray_j;
+      const int r0 = __builtin_amdgcn_readfirstlane(ray_j);
+      const bool uniform = __all(ray_j == r0);
+#pragma unroll
+      for (int t2 = 0; t2 < 3; ++t2)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int kk = 16 * t2 + 4 * g + r;
+          float v = go2[t2][r];
+          if (uniform) v = row_allreduce_sum(v);
+          if (kk >= 1 && kk <= 32 && v != 0.0f && (!uniform || j == 0))
+            unsafeAtomicAdd(gxray_scene + (size_t)ray_j * kRayFeatPad + kk, v);
+        }
+    }
+    // ---------------- gs^T = W2^T g_o2^T ; gh = gs * sigmoid(h) ----------------
+    f32x4 gh[4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int t2 = 0; t2 < 3; ++t2) {
+        const f32x4 w = ldbv[(kVbW2T >> 2) + (mt * 3 + t2) * 64 + lane];
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, go2[t2][0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, go2[t2][1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, go2[t2][2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, go2[t2][3], acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float sig = 1.0f - __builtin_amdgcn_exp2f(-f.sp[mt][r]);   // sigmoid(h) = 1 - exp(-softplus(h))
+        gh[mt][r] = acc[r] * sig;
+      }
+    }
+
+    if (!k.points_only) {
+      // ---------------- stage transposed operands: GO_T [pt][row], S_T [pt][hid], GH_T [pt][hid], Y_T, GO2_T ----------------
+      wave_lds_fence();
+      *reinterpret_cast<f32x4*>(st + kGO + j * 20 + 4 * g) = go;
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) {
-        *reinterpret_cast<f32x4*>(st + kStS + j * 68 + 16 * nt + 4 * g) = sp[nt];
-        *reinterpret_cast<f32x4*>(st + kStGH + j * 68 + 16 * nt + 4 * g) = gh[nt];
+        *reinterpret_cast<f32x4*>(st + kS + j * 68 + 16 * nt + 4 * g) = f.sp[nt];
+        *reinterpret_cast<f32x4*>(st + kGH + j * 68 + 16 * nt + 4 * g) = gh[nt];
       }
-      if constexpr (VD) {
 #pragma unroll
-        for (int t2 = 0; t2 < 3; ++t2) {
-          *reinterpret_cast<f32x4*>(st + kStY + j * 52 + 16 * t2 + 4 * g) = yv[t2];
-          *reinterpret_cast<f32x4*>(st + kStGO2 + j * 52 + 16 * t2 + 4 * g) = go2[t2];
-        }
+      for (int t2 = 0; t2 < 3; ++t2) {
+        *reinterpret_cast<f32x4*>(st + kY + j * 52 + 16 * t2 + 4 * g) = f.yv[t2];
+        *reinterpret_cast<f32x4*>(st + kGO2 + j * 52 + 16 * t2 + 4 * g) = go2[t2];
       }
       wave_lds_fence();
       {
         // db1[hid = lane] += sum_pt gh[hid][pt]: the column sum of GH_T
         float cs = 0.0f;
 #pragma unroll
-        for (int pt = 0; pt < 16; ++pt) cs += st[kStGH + pt * 68 + lane];
+        for (int pt = 0; pt < 16; ++pt) cs += st[kGH + pt * 68 + lane];
         db1p += cs;
       }
-      // dW2[row][hid] += sum_pt g_o[row][pt] s[hid][pt] ; dW1[hid][ch] += sum_pt gh[hid][pt] f[ch][pt]
+      // dW3[row][kk] += sum_pt g_o[row][pt] y[kk][pt] ; dW2[kk][hid] += sum_pt g_o2[kk][pt] s[hid][pt] ;
+      // dW1[hid][ch] += sum_pt gh[hid][pt] f[ch][pt]
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         const int pt = 4 * ks + g;
-        const float a_go = st[kStGO + pt * 20 + j];
+        const float a_go = st[kGO + pt * 20 + j];
         dVacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a_go, (j == 3) ? 1.0f : 0.0f, dVacc, 0, 0, 0);   // column 3: sum_pt g_o[row]
-        const float b_f0 = st[kStF + pt * 36 + j], b_f1 = st[kStF + pt * 36 + 16 + j];
-        if constexpr (VD) {
+        const float b_f0 = st[kF + pt * 36 + j], b_f1 = st[kF + pt * 36 + 16 + j];
 #pragma unroll
-          for (int t2 = 0; t2 < 3; ++t2)
-            dW3[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_go, st[kStY + pt * 52 + 16 * t2 + j], dW3[t2], 0, 0, 0);
-        }
+        for (int t2 = 0; t2 < 3; ++t2)
+          dW3[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_go, st[kY + pt * 52 + 16 * t2 + j], dW3[t2], 0, 0, 0);
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-          const float b_s = st[kStS + pt * 68 + 16 * nt + j];
-          if constexpr (VD) {
+          const float b_s = st[kS + pt * 68 + 16 * nt + j];
 #pragma unroll
-            for (int t2 = 0; t2 < 3; ++t2)
-              dW2[t2][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(st[kStGO2 + pt * 52 + 16 * t2 + j], b_s, dW2[t2][nt], 0, 0, 0);
-          } else {
-            dW2[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_go, b_s, dW2[0][nt], 0, 0, 0);
-          }
-          const float a_gh = st[kStGH + pt * 68 + 16 * nt + j];
+          for (int t2 = 0; t2 < 3; ++t2)
+            dW2[t2][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(st[kGO2 + pt * 52 + 16 * t2 + j], b_s, dW2[t2][nt], 0, 0, 0);
+          const float a_gh = st[kGH + pt * 68 + 16 * nt + j];
           dW1[nt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_gh, b_f0, dW1[nt][0], 0, 0, 0);
           dW1[nt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_gh, b_f1, dW1[nt][1], 0, 0, 0);
         }
       }
-      }
-      }
-
-      // ---------------- gf^T = W1^T gh^T  (rows = channels, accumulator layout == feature layout M) ----------------
-      f32x4 gf0 = {0.0f, 0.0f, 0.0f, 0.0f}, gf1 = {0.0f, 0.0f, 0.0f, 0.0f};
-      float gf_inv = 1.0f;
-      if constexpr (!VD) {
-        const u32x4* ldbu = reinterpret_cast<const u32x4*>(ldb + kBwdW1T);
-        float am = 0.0f, sc;
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) am = fmaxf(am, fabsf(gh[mt][r]));
-        am = max_xor32(max_xor16(am));                       // over the 64 hidden units of point j
-        pow2_normaliser(am, sc, gf_inv);
-        typedef unsigned long long u64;
-        typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-        uint32_t r_gh = 0u;
-        if (!k.points_only) {
-          // phase B staging (R1 is free: the colour-table MFMAs are done): GH_T fp32 for the bias column sums, and below
-          // the tile-scaled fp16 halves of gh as the A operand of dW1
-          const float fac = sticky_scale(am, es_gh, et_max_gh);
-          if (fac != 1.0f) {
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) { dW1[nt][0] *= fac; dW1[nt][1] *= fac; }
-          }
-          r_gh = ratio_f16x2(es_gh, gf_inv);
-          wave_lds_fence();
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) *reinterpret_cast<f32x4*>(st + kGHT + j * 68 + 16 * nt + 4 * g) = gh[nt];
-        }
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const float x8[8] = {gh[2 * kk][0] * sc, gh[2 * kk][1] * sc, gh[2 * kk][2] * sc, gh[2 * kk][3] * sc,
-                               gh[2 * kk + 1][0] * sc, gh[2 * kk + 1][1] * sc, gh[2 * kk + 1][2] * sc, gh[2 * kk + 1][3] * sc};
-          f16x8 xh, xl;
-          split_f16x8(x8, xh, xl);
-          if (!k.points_only) {
-            // hidden units {32 kk + 4 g + r, 32 kk + 16 + 4 g + r} of point j
-            const f16x8 rr = __builtin_bit_cast(f16x8, u32x4{r_gh, r_gh, r_gh, r_gh});
-            const u64x2 h2 = __builtin_bit_cast(u64x2, xh * rr), l2 = __builtin_bit_cast(u64x2, xl * rr);
-            char* t16 = reinterpret_cast<char*>(st) + j * kW16H + 2 * (32 * kk + 4 * g);
-            *reinterpret_cast<u64*>(t16 + kGH16Hi) = h2[0]; *reinterpret_cast<u64*>(t16 + kGH16Hi + 32) = h2[1];
-            *reinterpret_cast<u64*>(t16 + kGH16Lo) = l2[0]; *reinterpret_cast<u64*>(t16 + kGH16Lo + 32) = l2[1];
-          }
-          const f16x8 ah = __builtin_bit_cast(f16x8, ldbu[((0 * 2 + kk) * 2 + 0) * 64 + lane]);
-          const f16x8 al = __builtin_bit_cast(f16x8, ldbu[((0 * 2 + kk) * 2 + 1) * 64 + lane]);
-          const f16x8 bh = __builtin_bit_cast(f16x8, ldbu[((1 * 2 + kk) * 2 + 0) * 64 + lane]);
-          const f16x8 bl = __builtin_bit_cast(f16x8, ldbu[((1 * 2 + kk) * 2 + 1) * 64 + lane]);
-          gf0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xh, gf0, 0, 0, 0);
-          gf1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh, xh, gf1, 0, 0, 0);
-          gf0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xl, gf0, 0, 0, 0);
-          gf1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh, xl, gf1, 0, 0, 0);
-          gf0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, xh, gf0, 0, 0, 0);
-          gf1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl, xh, gf1, 0, 0, 0);
-        }
-        if (!k.points_only) {
-          // lane (g, j) addresses row 8 (g & 1) + (j >> 2) [+ 4 for the second read], columns 4 (j & 3) .. + 3 of a tile and
-          // receives points 8 (g & 1) .. + 7 of column j; lanes g >= 2 (K slots 16 .. 31) take the A side from the lo tile
-          const int rowb = 8 * (g & 1) + (j >> 2), colb = 8 * (j & 3), a_lo = g >> 1;
-          const char* wb = reinterpret_cast<const char*>(st);
-          // ---------------- phase B: db1 += column sums of GH_T ; dW1[hid][ch] += sum_pt gh[hid][pt] f[ch][pt] ----------------
-          wave_lds_fence();
-          {
-            float cs = 0.0f;
-#pragma unroll
-            for (int pt = 0; pt < 16; ++pt) cs += st[kGHT + pt * 68 + lane];
-            db1p += cs;
-          }
-          {
-            const char* pf = wb + rowb * kW16F + colb;
-            f16x8 bfh[2], bfl[2];
-#pragma unroll
-            for (int n2 = 0; n2 < 2; ++n2) {
-              bfh[n2] = lds_read_tr16x2(pf + kF16Hi + 32 * n2, 4 * kW16F);
-              bfl[n2] = lds_read_tr16x2(pf + kF16Lo + 32 * n2, 4 * kW16F);
-            }
-            const char* pa = wb + (a_lo ? kGH16Lo : kGH16Hi) + rowb * kW16H + colb;
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-              const f16x8 a = lds_read_tr16x2(pa + 32 * nt, 4 * kW16H);
-#pragma unroll
-              for (int n2 = 0; n2 < 2; ++n2) {
-                dW1[nt][n2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bfh[n2], dW1[nt][n2], 0, 0, 0);
-                dW1[nt][n2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bfl[n2], dW1[nt][n2], 0, 0, 0);
-              }
-            }
-          }
-        }
-      }
-      if constexpr (VD) {
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          const f32x4 wa = ldbv[(oW1T >> 2) + (0 * 4 + nt) * 64 + lane];
-          const f32x4 wb = ldbv[(oW1T >> 2) + (1 * 4 + nt) * 64 + lane];
-          gf0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.x, gh[nt][0], gf0, 0, 0, 0);
-          gf1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.x, gh[nt][0], gf1, 0, 0, 0);
-          gf0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.y, gh[nt][1], gf0, 0, 0, 0);
-          gf1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.y, gh[nt][1], gf1, 0, 0, 0);
-          gf0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.z, gh[nt][2], gf0, 0, 0, 0);
-          gf1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.z, gh[nt][2], gf1, 0, 0, 0);
-          gf0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.w, gh[nt][3], gf0, 0, 0, 0);
-          gf1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.w, gh[nt][3], gf1, 0, 0, 0);
-        }
-      }
-      // M -> L through LDS (rows at oR1), pre-divided by 3 (mean of the three planes)
-      wave_lds_fence();
-      {
-        const float third = (1.0f / 3.0f) * gf_inv;           // gf_inv: power of two (1 with the fp32 MFMAs of VD)
-        f32x4* wr = reinterpret_cast<f32x4*>(st + oR1 + j * 36 + 4 * g);
-        wr[0] = gf0 * third;
-        wr[4] = gf1 * third;
-      }
-      wave_lds_fence();
-      // ---------------- plane gradient scatter: one instruction = the two x-adjacent corners of one point ----------------
-      // (64 consecutive floats = 2 full 128-B lines per wave instruction; the atomic units retire per
-      //  line touched, so this is 8x cheaper than scattering in the quad load layout - tools/probes/atomic_scatter.hip)
-      if (k.gf_out) {
-        // hand the tile's feature-gradient rows to the follow-up kernels: the 16 rows are 2 KB of consecutive workspace,
-        // written as two 16-byte stores per lane (8 lanes = one row); the binned scatter also gets a flag per point: rows
-        // that are exactly zero (outside the cube, zero upstream) drop out
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int pt = 8 * h + (lane >> 3), c4 = lane & 7;
-          const int64_t pidx = chunk * 64 + 16 * t + pt;
-          const f32x4 gv = *reinterpret_cast<const f32x4*>(st + oR1 + pt * 36 + 4 * c4);
-          const uint64_t nzb = __ballot(gv.x != 0.0f || gv.y != 0.0f || gv.z != 0.0f || gv.w != 0.0f);
-          if (pidx < k.P) {
-            const uint32_t pu = (uint32_t)pidx;
-            *reinterpret_cast<f32x4*>(gfout_sc + (pu * (uint32_t)kC + 4u * (uint32_t)c4)) = gv;
-            if (flag_sc && c4 == 0) flag_sc[pu] = ((nzb >> (lane & 56)) & 0xFFull) ? 1 : 0;
-          }
-        }
-      }
-      if (!k.points_only && !k.bin_flag) {
-        const int lc = lane & 31, lh = lane >> 5;
-#pragma unroll 1
-        for (int pt = 0; pt < 16; ++pt) {
-          const int src = 16 * t + pt;
-          const int fl = __builtin_amdgcn_readlane(flags, src);
-          if (!(fl & 2)) continue;
-          const float gv = st[oR1 + pt * 36 + lc];
-          if (__ballot(gv != 0.0f) == 0) continue;
-          const uint32_t pxi = (uint32_t)__builtin_amdgcn_readlane(xi, src);
-          const float pfx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, fx), src));
-          const float pfy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, fy), src));
-          const float pfz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, fz), src));
-          const uint32_t px0 = pxi & 1023u, py0 = (pxi >> 10) & 1023u, pz0 = (pxi >> 20) & 1023u;
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl) {
-            const uint32_t a0 = (pl == 2) ? py0 : px0, b0 = (pl == 0) ? py0 : pz0;
-            const float fa = (pl == 2) ? pfy : pfx, fb = (pl == 0) ? pfy : pfz;
-            const float wa = lh ? fa : 1.0f - fa;
-            float* base = gtex_scene + (size_t)pl * g_plane + ((size_t)b0 * P.res + a0 + lh) * g_pix + lc;
-            const float v0 = (wa * (1.0f - fb)) * gv, v1 = (wa * fb) * gv;
-            if (v0 != 0.0f) unsafeAtomicAdd(base, v0);
-            if (v1 != 0.0f) unsafeAtomicAdd(base + g_row, v1);
-          }
-        }
-      }
-      // ---------------- coordinate gradients in the load layout ----------------
-      const bool ptv = (flL & 2) != 0;
-      float gcoord[3] = {0.0f, 0.0f, 0.0f};           // d/d(unnormalised u_x, u_y, u_z)
-      if (COORD) {
-        float gfL[8];
-        {
-          const f32x4* rd = reinterpret_cast<const f32x4*>(st + oR1 + lp * 36 + lq * kColA);
-          const f32x4 lo = rd[0], hi = rd[kColB / 4];
-          gfL[0] = lo.x; gfL[1] = lo.y; gfL[2] = lo.z; gfL[3] = lo.w;
-          gfL[4] = hi.x; gfL[5] = hi.y; gfL[6] = hi.z; gfL[7] = hi.w;
-        }
-        bool any = false;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) any = any || (gfL[s] != 0.0f);
-        if (__ballot(any && ptv)) {
-          // second gather, ONE PLANE AT A TIME: the lines are L1/L2-hot (this wave loaded them for the forward
-          // recompute), and 32 texel registers instead of 96 keep the kernel's register peak - which is here, with all
-          // the weight-gradient accumulators live - under the 256 of two waves per SIMD without spilling
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl) {
-            const uint32_t x0 = cxi & 1023u, y0 = (cxi >> 10) & 1023u, z0 = (cxi >> 20) & 1023u;
-            const uint32_t a0 = (pl == 2) ? y0 : x0, b0 = (pl == 0) ? y0 : z0;
-            const uint32_t voff = (uint32_t)pl * P.plane_bytes + __umul24(b0 * (uint32_t)P.res + a0, P.pix_bytes) + (uint32_t)lq * 16u;
-            float tv[4][8];
-            load_texel8<TEX>(P, voff, 0, 0, tv[0]);
-            load_texel8<TEX>(P, voff, P.pix_bytes, 0, tv[1]);
-            load_texel8<TEX>(P, voff, P.row_bytes, 0, tv[2]);
-            load_texel8<TEX>(P, voff, P.row_pix_bytes, 0, tv[3]);
-            const float fa = (pl == 2) ? cfy : cfx, fb = (pl == 0) ? cfy : cfz;
-            const float ga = 1.0f - fa, gb = 1.0f - fb;
-            float dcorner[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              float acc = 0.0f;
-#pragma unroll
-              for (int s = 0; s < 8; ++s) acc = fmaf(gfL[s], tv[c][s], acc);
-              // sum over the 4 lanes (channel chunks) of the point: one DPP quad
-              acc += dpp_f32<kDppQuadXor1>(0.0f, acc);
-              acc += dpp_f32<kDppQuadXor2>(0.0f, acc);
-              dcorner[c] = acc;
-            }
-            const float g_fa = gb * (dcorner[1] - dcorner[0]) + fb * (dcorner[3] - dcorner[2]);
-            const float g_fb = ga * (dcorner[2] - dcorner[0]) + fa * (dcorner[3] - dcorner[1]);
-            // plane 0: (x,y)  plane 1: (x,z)  plane 2: (y,z)
-            gcoord[(pl == 2) ? 1 : 0] += g_fa;
-            gcoord[(pl == 0) ? 1 : 2] += g_fb;
-            __builtin_amdgcn_sched_barrier(0);       // keep the planes' loads from being hoisted together again
-          }
-        }
-      }
-      if (COORD && k.g_points && lq == 0 && ptv) {
-        const int64_t ptL = chunk * 64 + srcL;
-        const float sc = (P.res_m1 * 0.5f) / k.scene_range;
-        float* gp = k.g_points + ((size_t)scene * k.P + ptL) * 3;
-        float gx = ((flL >> 2) & 1) ? gcoord[0] * sc : 0.0f;
-        float gy = ((flL >> 3) & 1) ? gcoord[1] * sc : 0.0f;
-        float gz = ((flL >> 4) & 1) ? gcoord[2] * sc : 0.0f;
-        if (k.normalize_points) {
-          const float nrm = fmaxf(norm3(gx, gy, gz), 1e-12f);     // F.normalize(x_grad, dim=-1)
-          gx /= nrm; gy /= nrm; gz /= nrm;
-        }
-        gp[0] = gx; gp[1] = gy; gp[2] = gz;
-      }
-      wave_lds_fence();
     }
+
+    // ---------------- gf^T = W1^T gh^T  (rows = channels, accumulator layout == feature layout M) ----------------
+    FeatureGrad out{{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}, 1.0f};
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const f32x4 wa = ldbv[(kVbW1T >> 2) + (0 * 4 + nt) * 64 + lane];
+      const f32x4 wb = ldbv[(kVbW1T >> 2) + (1 * 4 + nt) * 64 + lane];
+      out.gf0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.x, gh[nt][0], out.gf0, 0, 0, 0);
+      out.gf1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.x, gh[nt][0], out.gf1, 0, 0, 0);
+      out.gf0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.y, gh[nt][1], out.gf0, 0, 0, 0);
+      out.gf1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.y, gh[nt][1], out.gf1, 0, 0, 0);
+      out.gf0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.z, gh[nt][2], out.gf0, 0, 0, 0);
+      out.gf1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.z, gh[nt][2], out.gf1, 0, 0, 0);
+      out.gf0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.w, gh[nt][3], out.gf0, 0, 0, 0);
+      out.gf1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.w, gh[nt][3], out.gf1, 0, 0, 0);
+    }
+    return out;
   }
 
-  // ---------------- flush the per-wave accumulators ----------------
-  if (k.points_only) return;
-  // reduce over the 16 points of a row where the accumulator is per point (biases, V, beta, alpha)
-  const float g1 = 0.17677669529663687f, g2 = 0.125f;
-  // the plain decoder's weight-gradient accumulators are in units of 1 / (their sticky scale)
-  const float un_gh = (VD || es_gh == 0) ? 1.0f : bits2f((uint32_t)(254 - es_gh) << 23);
-  const float un_go = (VD || es_go == 0) ? 1.0f : bits2f((uint32_t)(254 - es_go) << 23);
+  // flush: g_w1, g_w2 (33 rows), g_b1, g_b2 (33 rows), g_w3, g_b3
+  __device__ __forceinline__ void flush(const FieldBwdParams& k, const BwdLane& L) {
+    const int lane = L.lane, j = L.j, g = L.g;
+    const int n3 = k.A > 0 ? k.A : 3;
+    const float g1 = 0.17677669529663687f, g2 = 0.125f;
 #pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
+    for (int nt = 0; nt < 4; ++nt) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      // dW1[hid = 16nt+4g+r][ch = 16*n2 + j] ; feat was the SUM of three planes -> /3
-      atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * kC + j], dW1[nt][0][r] * (g1 / 3.0f) * un_gh);
-      atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * kC + 16 + j], dW1[nt][1][r] * (g1 / 3.0f) * un_gh);
-      // dW2[row = 4g+r][hid = 16nt + j] ; s = sp2 * ln2
-      const int row = 4 * g + r;
-      if constexpr (VD) {
+      for (int r = 0; r < 4; ++r) {
+        // dW1[hid = 16nt+4g+r][ch = 16*n2 + j] ; feat was the SUM of three planes -> /3
+        atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * kC + j], dW1[nt][0][r] * (g1 / 3.0f));
+        atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * kC + 16 + j], dW1[nt][1][r] * (g1 / 3.0f));
+        // dW2[row = 16 t2 + 4g+r][hid = 16nt + j] ; s = sp2 * ln2
+        const int row = 4 * g + r;
 #pragma unroll
         for (int t2 = 0; t2 < 3; ++t2)
           if (16 * t2 + row < 33) atomicAdd(&k.g_w2[(16 * t2 + row) * kHidden + 16 * nt + j], dW2[t2][nt][r] * (g2 * kLn2));
-      } else {
-        if (row < n_out) atomicAdd(&k.g_w2[row * kHidden + 16 * nt + j], dW2[0][nt][r] * (g2 * kLn2) * un_go);
       }
     }
-  }
-  atomicAdd(&k.g_b1[lane], db1p);                                   // one hidden unit per lane (see db1p above)
+    atomicAdd(&k.g_b1[lane], db1p);                                   // one hidden unit per lane (see db1p above)
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    // dVacc: columns j < 3 hold dV[row][c = j], column 3 the last layer's bias gradient of the row
-    const int row = 4 * g + r;
-    const float v = dVacc[r];
-    if (j < 3) {
-      if (ATT && row >= 1 && row <= A) atomicAdd(&k.g_att[((size_t)scene * A + (row - 1)) * 3 + j], v);
-    } else if (j == 3) {
-      if (VD) {
-        // last layer = the mapper's `output` Linear(32, n3): its bias gradient
-        if (row >= 1 && row <= (A > 0 ? A : 3)) atomicAdd(&k.g_b3[row - 1], v);
-      } else if (row < n_out) {
-        atomicAdd(&k.g_b2[row], v * un_go);
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = 4 * g + r;
-    if constexpr (VD) {
+    for (int r = 0; r < 4; ++r) {
+      const int row = 4 * g + r;
+      // column 3 of dVacc: the bias gradient of the last layer = the mapper's `output` Linear(32, n3)
+      if (j == 3 && row >= 1 && row <= n3) atomicAdd(&k.g_b3[row - 1], dVacc[r]);
       // dW3 = the weight gradient of the mapper's `output` layer
-      const int n3 = A > 0 ? A : 3;
 #pragma unroll
       for (int t2 = 0; t2 < 3; ++t2) {
         const int kk = 16 * t2 + j;
@@ -963,6 +1135,76 @@ __global__ __launch_bounds__(256, VD ? 1 : 2) void field_query_bwd_kernel(FieldB
         float b2v = row_allreduce_sum(db2v[t2][r]);
         if (j == 0 && 16 * t2 + row < 33) atomicAdd(&k.g_b2[16 * t2 + row], b2v);
       }
+    }
+  }
+};
+
+// VD selects the back end: here and nowhere else
+template <bool VD> using FieldDecoderBwd = std::conditional_t<VD, ViewdirDecoderBwd, PlainDecoderBwd>;
+
+// TEX: texel storage of the planes (0 fp32, 1 bf16, 2 fp16).  With 16-bit storage the forward recompute gathers the
+// rounded texels and the gradient image stays fp32: it is the gradient w.r.t. the rounded planes, handed to the
+// producer unchanged (straight-through rounding), which is what a bf16 / fp16 plane tensor gives under autograd.
+template <bool ATT, bool COORD, bool VD = false, int TEX = 0>
+__global__ __launch_bounds__(256, FieldDecoderBwd<VD>::kWorkgroupsPerCU) void field_query_bwd_kernel(FieldBwdParams k) {
+  using Dec = FieldDecoderBwd<VD>;
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  float* lds = dyn;                                   // forward operand image + attention values
+  float* ldb = dyn + Dec::kFwd;                       // backward operand image
+  const int scene = blockIdx.y;
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  const BwdLane L{lane, lane & 15, lane >> 4, lane >> 2, lane & 3};
+  float* st = ldb + Dec::kBwdImg + wave * Dec::kWaveFloats;
+  Dec dec(lds, ldb, st);
+  dec.enter_scene(k, scene);
+  float* rows = st + Dec::kRows;                      // scratch rows of the epilogue / the feature-gradient rows
+  const char* tex_scene = reinterpret_cast<const char*>(k.texels) + (size_t)scene * 3 * k.res * k.res * (TEX == 0 ? 128 : 64);
+  FieldParams P = make_field_params(tex_scene, k.res, TEX, k.A, k.use_sdf, k.beta, k.alpha, lds, Dec::kFwdImg, k.layout);
+  const BwdScene S = enter_bwd_scene(k, scene);
+  const float alpha_v = k.use_sdf ? k.alpha[0] : 1.0f;
+  float d_beta = 0.0f, d_alpha = 0.0f;
+
+  ChunkWalk walk(k, wave);
+  while (true) {
+    const int64_t chunk = walk.next(k);
+    if (chunk < 0) break;
+    const ChunkPoints C = chunk_points(k, P, S, chunk, lane);
+    const uint64_t nzmask = upstream_peek(k, S, C);
+#pragma unroll 1
+    for (int t = 0; t < 4; ++t) {
+      if (((C.live >> (16 * t)) & 0xFFFFull) == 0) continue;
+      const BwdTile T = tile_lanes(C, t, L);
+      // does anything flow into this tile?  (the chunk-level peek; the values are loaded again where they are used - held
+      // across the forward recompute they cost the registers this kernel does not have)
+      if (((nzmask >> (16 * t)) & 0xFFFFull) == 0) {
+        zero_tile_outputs<COORD>(k, S, C, T, L);
+        continue;
+      }
+      float feat[8];
+      gather_features<TEX>(P, T, L, st + Dec::kF, feat);
+      const typename Dec::Fwd f = dec.template forward<TEX>(k, T, L, feat);
+      const f32x4 go = epilogue_bwd<ATT>(k, P, S, T, L, f.o, alpha_v, rows, dec.dVacc, d_beta, d_alpha);
+      const FeatureGrad gf = dec.backward(k, L, go, f);
+      rows_to_load_layout(rows, gf, L);
+      if (k.gf_out) store_gf_rows(k, S, C, t, rows, lane);
+      if (!k.points_only && !k.bin_flag) scatter_tile_atomics(P, S, C, t, rows, lane);
+      if constexpr (COORD) {
+        const CoordGrad gc = coord_gradients<TEX>(P, T, L, rows);
+        if (k.g_points && L.lq == 0 && (T.flL & 2)) store_g_points(k, P, S, C, T, gc);
+      }
+      wave_lds_fence();
+    }
+  }
+
+  // ---------------- flush the per-wave accumulators ----------------
+  if (k.points_only) return;
+  dec.flush(k, L);
+  if constexpr (ATT) {
+    // columns j < 3 of dVacc hold dV[row][c = j]
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 4 * L.g + r;
+      if (L.j < 3 && row >= 1 && row <= k.A) atomicAdd(&k.g_att[((size_t)scene * k.A + (row - 1)) * 3 + L.j], dec.dVacc[r]);
     }
   }
   if (k.use_sdf) {
@@ -1308,26 +1550,49 @@ static inline size_t bin_max_items(int n_scenes, int64_t P, int res) {
 
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-extern "C" size_t nfi_field_bwd_workspace_bytes(const nfi_field_bwd_args* a) {
-  if (!a) return 0;
-  size_t img = align256((a->ray_features ? kVbImageFloats : kBwdImageFloats) * sizeof(float));
-  const size_t bp = (size_t)a->n_scenes * (size_t)a->points_per_scene;
-  const bool binned = a->scatter_mode == 1 && !a->points_only;
-  if (binned) img += align256(bp * kC * sizeof(float));                          // per-point feature-gradient rows
-  if (!binned) return img;
-  const int g = bin_groups(a->points_per_scene), t = bin_tile_side(a->plane_res, g), tps = (a->plane_res + t - 1) / t;
-  const size_t nb = (size_t)a->n_scenes * g * 3 * tps * tps;
-  return img + align256(3 * bp * sizeof(int4)) + align256(2 * nb * sizeof(int) + 64) +
-         align256(bin_max_items(a->n_scenes, a->points_per_scene, a->plane_res) * sizeof(int4)) + align256(bp);
+// The workspace of one nfi_field_query_bwd call: byte offsets of its regions and the total.  Behind the backward operand
+// image come, for the binned scatter only, the feature-gradient rows, the sorted entries, the bucket counters
+// (count[nb], n_items + the reduce's cursor padded to 64 B, cursor[nb]), the work items and the per-point flags.
+struct FieldBwdCarve {
+  bool binned;
+  int groups, tile, tps;             // binned scatter: point groups per scene, tile side, tiles per plane side
+  size_t nb, max_items;              // buckets over all scenes, upper bound of the work items
+  size_t gf, entries, counts, items, flag, total;
+};
+
+static FieldBwdCarve field_bwd_carve(const nfi_field_bwd_args* a) {
+  FieldBwdCarve c;
+  memset(&c, 0, sizeof(c));
+  c.binned = a->scatter_mode == 1 && !a->points_only;
+  size_t at = align256((a->ray_features ? kVbImageFloats : kBwdImageFloats) * sizeof(float));      // operand image at 0
+  if (c.binned) {
+    const size_t n_pts = (size_t)a->n_scenes * (size_t)a->points_per_scene;
+    c.groups = bin_groups(a->points_per_scene);
+    c.tile = bin_tile_side(a->plane_res, c.groups);
+    c.tps = (a->plane_res + c.tile - 1) / c.tile;
+    c.nb = (size_t)a->n_scenes * c.groups * 3 * c.tps * c.tps;
+    c.max_items = bin_max_items(a->n_scenes, a->points_per_scene, a->plane_res);
+    c.gf = at; at += align256(n_pts * kC * sizeof(float));
+    c.entries = at; at += align256(3 * n_pts * sizeof(int4));
+    c.counts = at; at += align256(2 * c.nb * sizeof(int) + 64);
+    c.items = at; at += align256(c.max_items * sizeof(int4));
+    c.flag = at; at += align256(n_pts);
+  }
+  c.total = at;
+  return c;
 }
+
+extern "C" size_t nfi_field_bwd_workspace_bytes(const nfi_field_bwd_args* a) { return a ? field_bwd_carve(a).total : 0; }
 
 extern "C" size_t nfi_decoder_bwd_image_floats(void) { return (size_t)kBwdImageFloats; }
 extern "C" size_t nfi_decoder_bwd_image_floats_viewdir(void) { return (size_t)kVbImageFloats; }
 
 template <bool ATT, bool COORD, bool VD, int TEX>
-static int launch_field_bwd(dim3 grid, size_t shmem, hipStream_t s, const FieldBwdParams& k) {
+static int launch_field_bwd(dim3 grid, hipStream_t s, const FieldBwdParams& k) {
   constexpr auto kernel = &field_query_bwd_kernel<ATT, COORD, VD, TEX>;
-  // shmem depends on VD only, a template argument: one constant per instantiation
+  using Dec = FieldDecoderBwd<VD>;
+  // the two operand images and four waves' staging: it depends on the decoder only
+  constexpr size_t shmem = (size_t)(Dec::kFwd + Dec::kBwdImg + 4 * Dec::kWaveFloats) * sizeof(float);
   const int rc = ensure_dynamic_lds<kernel>(shmem, "field_query_bwd");
   if (rc) return rc;
   hipLaunchKernelGGL(kernel, grid, dim3(256), shmem, s, k);
@@ -1361,7 +1626,7 @@ static int field_bwd_check_call(const nfi_field_bwd_args* a) {
 }
 
 // which field_query_bwd_kernel instantiation a (validated) call gets: its launcher and its canonical name
-struct FieldBwdLaunch { int (*launch)(dim3, size_t, hipStream_t, const FieldBwdParams&); const char* name; };
+struct FieldBwdLaunch { int (*launch)(dim3, hipStream_t, const FieldBwdParams&); const char* name; };
 static constexpr char kFieldBwdFamily[] = "field_query_bwd_kernel";
 template <bool ATT, bool COORD, bool VD, int TEX>
 static FieldBwdLaunch field_bwd_launch() { return {&launch_field_bwd<ATT, COORD, VD, TEX>, KernelName<kFieldBwdFamily, ATT, COORD, VD, TEX>::value.s}; }
@@ -1389,50 +1654,41 @@ extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t str
   const bool vd = a->ray_features != nullptr;
   hipStream_t s = (hipStream_t)stream;
   const int n_out = a->n_attention > 0 ? 1 + a->n_attention : 4;
-  float* image_bwd = reinterpret_cast<float*>(a->workspace);
+  const FieldBwdCarve ws = field_bwd_carve(a);
+  char* const w = reinterpret_cast<char*>(a->workspace);
+  float* image_bwd = reinterpret_cast<float*>(w);
   if (vd)
     hipLaunchKernelGGL(decoder_pack_bwd_vd_kernel, dim3(1), dim3(256), 0, s, a->w1, a->w2, a->w3,
                        a->n_attention > 0 ? a->n_attention : 3, image_bwd);
   else
     hipLaunchKernelGGL(decoder_pack_bwd_kernel, dim3(1), dim3(256), 0, s, a->w1, a->w2, n_out, image_bwd);
-  FieldBwdParams k{a->points, a->points_per_scene, reinterpret_cast<const float*>(a->texels), a->plane_res,
-                   a->decoder_image, image_bwd, a->n_attention, a->attention_values, a->use_sdf, a->beta, a->alpha,
-                   a->scene_range, a->g_sigma, a->g_rgb, a->g_sdf, a->g_semantics, a->g_texels, a->g_points,
-                   a->g_w1, a->g_b1, a->g_w2, a->g_b2, a->g_attention_values, a->g_beta, a->g_alpha,
-                   a->points_only, a->normalize_g_points,
-                   a->ray_features, a->samples_per_ray, a->g_ray_features, a->g_w3, a->g_b3, nullptr, nullptr, a->texel_layout,
-                   0, 0, 0, 0, 0, FastDiv{0u, 0u}, FastDiv{0u, 0u}, FastDiv{0u, 0u}};
-  // workspace behind the operand image: feature-gradient rows (binned scatter and / or coordinate gradients), then the
-  // counting-sort arrays of the binned scatter
-  const bool binned = a->scatter_mode == 1 && !a->points_only;
-  const size_t n_pts = (size_t)a->n_scenes * (size_t)a->points_per_scene;
-  char* w = reinterpret_cast<char*>(a->workspace) + align256((vd ? kVbImageFloats : kBwdImageFloats) * sizeof(float));
-  float* gf = nullptr;
-  if (binned) { gf = reinterpret_cast<float*>(w); w += align256(n_pts * kC * sizeof(float)); }
-  k.gf_out = gf;
+  FieldBwdParams k{};                // (no ray-order hint, atomic scatter: zeros / null)
+  k.points = a->points; k.P = a->points_per_scene;
+  k.texels = reinterpret_cast<const float*>(a->texels); k.res = a->plane_res; k.layout = a->texel_layout;
+  k.image = a->decoder_image; k.image_bwd = image_bwd; k.A = a->n_attention; k.att = a->attention_values;
+  k.use_sdf = a->use_sdf; k.beta = a->beta; k.alpha = a->alpha; k.scene_range = a->scene_range;
+  k.g_sigma = a->g_sigma; k.g_rgb = a->g_rgb; k.g_sdf = a->g_sdf; k.g_sem = a->g_semantics;
+  k.g_texels = a->g_texels; k.g_points = a->g_points;
+  k.g_w1 = a->g_w1; k.g_b1 = a->g_b1; k.g_w2 = a->g_w2; k.g_b2 = a->g_b2;
+  k.g_att = a->g_attention_values; k.g_beta = a->g_beta; k.g_alpha = a->g_alpha;
+  k.points_only = a->points_only; k.normalize_points = a->normalize_g_points;
+  k.xray = a->ray_features; k.spr = a->samples_per_ray; k.g_xray = a->g_ray_features; k.g_w3 = a->g_w3; k.g_b3 = a->g_b3;
   BinParams bp;
   memset(&bp, 0, sizeof(bp));
-  size_t max_items = 0;
-  if (binned) {
-    const int grp = bin_groups(a->points_per_scene), t = bin_tile_side(a->plane_res, grp), tps = (a->plane_res + t - 1) / t;
-    const size_t nb = (size_t)a->n_scenes * grp * 3 * tps * tps;
-    max_items = bin_max_items(a->n_scenes, a->points_per_scene, a->plane_res);
-    int4* entries = reinterpret_cast<int4*>(w); w += align256(3 * n_pts * sizeof(int4));
-    int* count = reinterpret_cast<int*>(w);                  // count[nb], n_items (+ pad to 64 B), cursor[nb]
-    int* n_items = count + nb;
-    int* cursor = n_items + 16;
-    w += align256(2 * nb * sizeof(int) + 64);
-    int4* items = reinterpret_cast<int4*>(w); w += align256(max_items * sizeof(int4));
-    uint8_t* flag = reinterpret_cast<uint8_t*>(w);
+  if (ws.binned) {
+    int* count = reinterpret_cast<int*>(w + ws.counts);      // count[nb], n_items (+ pad to 64 B), cursor[nb]
+    int* n_items = count + ws.nb;
     // count[] and n_items are zeroed; cursor[], items[] and entries[] are written by the scan / fill, flag[] by the kernel
-    if (hipMemsetAsync(count, 0, (nb + 16) * sizeof(int), s) != hipSuccess)
+    if (hipMemsetAsync(count, 0, (ws.nb + 16) * sizeof(int), s) != hipSuccess)
       return fail(NFI_ERR_LAUNCH, "field_query_bwd: memset failed");
-    k.bin_flag = flag;
+    k.gf_out = reinterpret_cast<float*>(w + ws.gf);
+    k.bin_flag = reinterpret_cast<uint8_t*>(w + ws.flag);
     bp.points = a->points; bp.P = a->points_per_scene; bp.n_scenes = a->n_scenes; bp.res = a->plane_res;
-    bp.scene_range = a->scene_range; bp.flag = flag; bp.gf = gf; bp.count = count; bp.cursor = cursor;
-    bp.entries = entries; bp.items = items; bp.n_items = n_items; bp.g_texels = a->g_texels; bp.layout = a->texel_layout;
-    bp.tile = t; bp.tps = tps; bp.bpg = 3 * tps * tps; bp.n_buckets = grp * bp.bpg;
-    bp.groups = grp; bp.group_pts = a->points_per_scene / grp; bp.next_item = n_items + 1;
+    bp.scene_range = a->scene_range; bp.flag = k.bin_flag; bp.gf = k.gf_out; bp.count = count; bp.cursor = n_items + 16;
+    bp.entries = reinterpret_cast<int4*>(w + ws.entries); bp.items = reinterpret_cast<int4*>(w + ws.items); bp.n_items = n_items;
+    bp.g_texels = a->g_texels; bp.layout = a->texel_layout;
+    bp.tile = ws.tile; bp.tps = ws.tps; bp.bpg = 3 * ws.tps * ws.tps; bp.n_buckets = ws.groups * bp.bpg;
+    bp.groups = ws.groups; bp.group_pts = a->points_per_scene / ws.groups; bp.next_item = n_items + 1;
   }
   int64_t chunks = (a->points_per_scene + 63) / 64;
   int64_t blocks = (chunks + 3) / 4;
@@ -1455,17 +1711,15 @@ extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t str
     }
   }
   dim3 grid((unsigned)blocks, (unsigned)a->n_scenes);
-  const size_t shmem = vd ? (size_t)(kVdFieldLdsFloats + kVbImageFloats + 4 * kStFloatsVd) * sizeof(float)
-                          : (size_t)(kBwdFwdFloats + kBwdImageFloats + 4 * kStFloats) * sizeof(float);
-  rc = select_field_bwd_kernel(a).launch(grid, shmem, s, k);
+  rc = select_field_bwd_kernel(a).launch(grid, s, k);
   if (rc) return rc;
-  if (binned) {
+  if (ws.binned) {
     const dim3 pgrid((unsigned)((a->points_per_scene + 1023) / 1024), (unsigned)a->n_scenes);
     hipLaunchKernelGGL(bin_count_kernel, pgrid, dim3(256), 0, s, bp);
     hipLaunchKernelGGL(bin_scan_kernel, dim3((unsigned)a->n_scenes), dim3(256), 0, s, bp);
     hipLaunchKernelGGL(bin_fill_kernel, pgrid, dim3(256), 0, s, bp);
     // persistent: the resident set of workgroups (2 per CU) takes the work items in order from the cursor
-    hipLaunchKernelGGL(bin_reduce_kernel, dim3((unsigned)std::min<size_t>(max_items, 256 * 2)), dim3(kBinThreads), 0, s, bp);
+    hipLaunchKernelGGL(bin_reduce_kernel, dim3((unsigned)std::min<size_t>(ws.max_items, 256 * 2)), dim3(kBinThreads), 0, s, bp);
   }
   return check_launch("field_query_bwd");
 }

@@ -521,3 +521,86 @@ def test_planes_to_texels_all_sizes(gpu_device):
         for dt, td in ((hops.TEXEL_F32, torch.float32), (hops.TEXEL_BF16, torch.bfloat16), (hops.TEXEL_F16, torch.float16)):
             assert torch.equal(hops.planes_to_texels(pl, dt).view(ref.shape), ref.to(td)), (R, dt)
         assert torch.equal(hops.texels_to_planes(hops.planes_to_texels(pl)), pl), R
+
+
+# ---- field backward over several chunks per wave, against float64 ----
+# B = 32 scenes of P = 8229 points: the launcher caps the grid at max(16, 512 / B) = 16 blocks per scene (the same 16 with
+# the view-direction decoder: max(16, 256 / B)), i.e. 64 waves for 129 chunks of 64 points - every wave takes two chunks,
+# wave 0 three, and chunk 128 holds 37 points.  What a wave carries from chunk to chunk (weight-gradient accumulators, the
+# plain decoder's sticky power-of-two scales) is therefore part of every parameter gradient checked here.
+_MC = dict(B=32, R=8, P=8229, A=10, spr=13)
+_mc_cache = {}
+
+
+def _multi_chunk_case(kind):
+    """kind 'large_small' / 'small_large' (plain decoder) or 'viewdir': inputs, float64 and float32 oracle gradients."""
+    if kind in _mc_cache:
+        return _mc_cache[kind]
+    B, R, P, A, spr = (_MC[k] for k in ('B', 'R', 'P', 'A', 'spr'))
+    vd = kind == 'viewdir'
+    g = torch.Generator().manual_seed(9100 + ['large_small', 'small_large', 'viewdir'].index(kind))
+    r = float(torch.tensor(0.55, dtype=torch.float32))
+    n_out = 33 if vd else 1 + A
+    t = dict(planes=torch.randn(B, 3, 32, R, R, generator=g), w1=torch.randn(64, 32, generator=g), b1=0.3 * torch.randn(64, generator=g),
+             w2=torch.randn(n_out, 64, generator=g), b2=0.3 * torch.randn(n_out, generator=g),
+             beta=torch.tensor([0.12]), alpha=torch.tensor([0.3]), attention_values=torch.rand(B, A, 3, generator=g) * 2 - 1)
+    if vd:
+        t.update(viewdir_x=torch.randn(B, P // spr, 32, generator=g), w3=torch.randn(A, 32, generator=g), b3=0.3 * torch.randn(A, generator=g))
+    x = (torch.rand(B, P, 3, generator=g) * 2 - 1) * r * 1.1          # some points outside the cube
+    # upstream gradient: a factor per chunk, and exactly zero for points 16..47 of every fifth chunk (tiles 1 and 2 are
+    # skipped between the live tiles 0 and 3).  No semantics gradient: with one the kernel skips no tile.
+    chunk = torch.arange(P) // 64
+    first, second = {'large_small': (3e4, 1e-7), 'small_large': (1e-7, 3e4), 'viewdir': (1.0, 1.0)}[kind]
+    scale = torch.where(chunk < 64, torch.tensor(first), torch.where(chunk < 128, torch.tensor(second), torch.tensor(1.0)))
+    in_chunk = torch.arange(P) % 64
+    scale = scale * (~((chunk % 5 == 0) & (in_chunk >= 16) & (in_chunk < 48))).float()
+    ups = dict(sigma=torch.randn(B, P, generator=g) * scale, rgb=torch.randn(B, P, 3, generator=g) * scale[:, None],
+               sdf=torch.randn(B, P, generator=g) * scale)
+    assert int((scale == 0).sum()) == 32 * 26 and float(scale[8192]) == 1.0
+
+    def grads(dtype):
+        leaf = lambda v: v.detach().to(dtype).requires_grad_()
+        names = ['planes', 'w1', 'b1', 'w2', 'b2', 'attention_values', 'beta', 'alpha'] + (['viewdir_x', 'w3', 'b3'] if vd else [])
+        L = {k: leaf(t[k]) for k in names}
+        L['points'] = leaf(x)
+        q = orc.field_query(L['planes'], L['w1'], L['b1'], L['w2'], L['b2'], L['points'].view(B, P // spr, spr, 3), r, True,
+                            L['beta'], L['alpha'], L['attention_values'], dict(x=L['viewdir_x'], w3=L['w3'], b3=L['b3']) if vd else None)
+        loss = sum((q[k].view(ups[k].shape) * ups[k].to(dtype)).sum() for k in ups)
+        keys = list(L)
+        return dict(zip(keys, torch.autograd.grad(loss, [L[k] for k in keys])))
+    _mc_cache[kind] = (t, x, r, ups, grads(torch.float64), grads(torch.float32))
+    return _mc_cache[kind]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('kind,want_points', [('large_small', False), ('large_small', True), ('small_large', False),
+                                              ('small_large', True), ('viewdir', True)])
+def test_field_backward_over_several_chunks_per_wave(gpu_device, kind, want_points):
+    """Every gradient of nfi_field_query_bwd against float64 autograd of the oracle where each wave walks two or three
+    chunks (see _MC), within the suite's bound for this kernel (test_field_bwd_row's: 5e-4 of the gradient's largest entry).
+    Plain decoder: the upstream gradient of a wave's first chunk is 3e4 and of its second 1e-7 times unit scale
+    ('large_small': the sticky scales are set by the large tiles and must stay while the small ones arrive) or the
+    reverse ('small_large': a rescale of accumulators that hold the small sum), the ragged last chunk at unit scale, and
+    tiles of zero upstream gradient fall between live ones.  View-direction decoder: unit scale, the same zero bands,
+    13 samples per ray, so rays straddle tiles and chunks."""
+    from nerf_from_image_amd import field_backward as fb, ops as hops
+    from parity_util import grad_close, hip_field_setup
+    dev = gpu_device
+    A, spr = _MC['A'], _MC['spr']
+    t, x, r, ups, ref, ref32 = _multi_chunk_case(kind)
+    vd = kind == 'viewdir'
+    mv = lambda v: v.to(dev)
+    texels, image = hip_field_setup(dict(A=A), t, dev)
+    vda = dict(ray_features=hops.pad_ray_features(mv(t['viewdir_x'])), samples_per_ray=spr, w3=mv(t['w3'])) if vd else None
+    got = fb.field_query_bwd(mv(x), texels, image, mv(t['w1']), mv(t['w2']), r, A, mv(t['attention_values']), True, mv(t['beta']),
+                             mv(t['alpha']), mv(ups['sigma']), mv(ups['rgb']), g_sdf=mv(ups['sdf']), viewdir=vda,
+                             want_points=want_points)
+    pairs = {'planes': hops.texel_grad_to_planes(got['g_texels']), 'w1': got['g_w1'], 'b1': got['g_b1'], 'w2': got['g_w2'],
+             'b2': got['g_b2'], 'attention_values': got['g_attention_values'], 'beta': got['g_beta'], 'alpha': got['g_alpha']}
+    if vd:
+        pairs.update(viewdir_x=got['g_ray_features'], w3=got['g_w3'], b3=got['g_b3'])
+    if want_points:
+        pairs['points'] = got['g_points']
+    what = '%s%s' % (kind, ', g_points' if want_points else '')
+    for k, v in pairs.items():
+        grad_close(v, ref[k], 5e-4, '%s: grad %s' % (what, k), ref32[k])

@@ -3,8 +3,8 @@
     python tools/probes/bwd_variants.py build        # here (no GPU): build/variants/libnfi_<name>.so
     python tools/probes/bwd_variants.py run [N]      # on the GPU box: N launches per variant, events in g_points
 
-Every variant is the product source with ONE change to how the coordinate-gradient block of field_query_bwd_kernel
-(nfi_backward_field.inc, "coordinate gradients in the load layout") is compiled:
+Every variant is the product source with ONE change to how the coordinate-gradient step of field_query_bwd_kernel
+(nfi_backward_field.inc, coord_gradients: "coordinate gradients in the load layout") is compiled:
 
     product      nerf_from_image_amd/libnfi_hip.so as built by __graft_entry__ (SLP on + tools/gfx950_pk_legalize.py)
     noslp        the round-2 product build (-fno-slp-vectorize)
@@ -27,12 +27,12 @@ CSRC = os.path.join(ROOT, 'nerf_from_image_amd', 'csrc')
 OUT = os.path.join(ROOT, 'build', 'variants')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC']
 
-G_FA = '            const float g_fa = gb * (dcorner[1] - dcorner[0]) + fb * (dcorner[3] - dcorner[2]);\n'
-G_FB = '            const float g_fb = ga * (dcorner[2] - dcorner[0]) + fa * (dcorner[3] - dcorner[1]);\n'
-NOP = ('            __builtin_amdgcn_sched_barrier(0); asm volatile("s_nop 7\\n\\ts_nop 7"); '
+G_FA = '      const float g_fa = gb * (dcorner[1] - dcorner[0]) + fb * (dcorner[3] - dcorner[2]);\n'
+G_FB = '      const float g_fb = ga * (dcorner[2] - dcorner[0]) + fa * (dcorner[3] - dcorner[1]);\n'
+NOP = ('      __builtin_amdgcn_sched_barrier(0); asm volatile("s_nop 7\\n\\ts_nop 7"); '
        '__builtin_amdgcn_sched_barrier(0);\n')
-QUAD1 = '              acc += dpp_f32<kDppQuadXor1>(0.0f, acc);\n'
-QUAD2 = '              acc += dpp_f32<kDppQuadXor2>(0.0f, acc);\n'
+QUAD1 = '        acc += dpp_f32<kDppQuadXor1>(0.0f, acc);\n'
+QUAD2 = '        acc += dpp_f32<kDppQuadXor2>(0.0f, acc);\n'
 
 
 def patch(src, name):
@@ -42,43 +42,43 @@ def patch(src, name):
     if name == 'slp_nop_dpp':
         return src.replace(G_FA, NOP + G_FA)
     if name == 'slp_waitcnt':
-        w = ('            __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); '
+        w = ('      __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); '
              '__builtin_amdgcn_sched_barrier(0);\n')
         return src.replace(G_FA, w + G_FA)
     if name == 'slp_nop_mul':
-        new = ('            float d10 = dcorner[1] - dcorner[0], d32 = dcorner[3] - dcorner[2], d20 = dcorner[2] - dcorner[0], '
+        new = ('      float d10 = dcorner[1] - dcorner[0], d32 = dcorner[3] - dcorner[2], d20 = dcorner[2] - dcorner[0], '
                'd31 = dcorner[3] - dcorner[1];\n'
-               '            asm volatile("" : "+v"(d10), "+v"(d32), "+v"(d20), "+v"(d31));\n' + NOP +
-               '            const float g_fa = gb * d10 + fb * d32;\n'
-               '            const float g_fb = ga * d20 + fa * d31;\n')
+               '      asm volatile("" : "+v"(d10), "+v"(d32), "+v"(d20), "+v"(d31));\n' + NOP +
+               '      const float g_fa = gb * d10 + fb * d32;\n'
+               '      const float g_fb = ga * d20 + fa * d31;\n')
         return src.replace(G_FA + G_FB, new)
     if name in ('slp_nop_only', 'slp_nop1', 'slp_nop2'):
         # the same packed code as `slp` (nothing hidden from the vectoriser), only wait states between the differences
         # and the products
         nop = {'slp_nop_only': NOP, 'slp_nop1': NOP.replace('s_nop 7\\n\\ts_nop 7', 's_nop 0'),
                'slp_nop2': NOP.replace('s_nop 7\\n\\ts_nop 7', 's_nop 1')}[name]
-        new = ('            const float d10 = dcorner[1] - dcorner[0], d32 = dcorner[3] - dcorner[2], d20 = dcorner[2] - dcorner[0], '
+        new = ('      const float d10 = dcorner[1] - dcorner[0], d32 = dcorner[3] - dcorner[2], d20 = dcorner[2] - dcorner[0], '
                'd31 = dcorner[3] - dcorner[1];\n' + nop +
-               '            const float g_fa = gb * d10 + fb * d32;\n'
-               '            const float g_fb = ga * d20 + fa * d31;\n')
+               '      const float g_fa = gb * d10 + fb * d32;\n'
+               '      const float g_fb = ga * d20 + fa * d31;\n')
         return src.replace(G_FA + G_FB, new)
     if name == 'slp_scalar':
-        new = ('            float g_fa, g_fb;\n'
-               '            {\n'
-               '              const float d10 = dcorner[1] - dcorner[0], d32 = dcorner[3] - dcorner[2], d20 = dcorner[2] - dcorner[0], '
+        new = ('      float g_fa, g_fb;\n'
+               '      {\n'
+               '        const float d10 = dcorner[1] - dcorner[0], d32 = dcorner[3] - dcorner[2], d20 = dcorner[2] - dcorner[0], '
                'd31 = dcorner[3] - dcorner[1];\n'
-               '              float p0, p1, p2, p3;\n'
-               '              asm volatile("v_mul_f32 %0, %1, %2" : "=v"(p0) : "v"(gb), "v"(d10));\n'
-               '              asm volatile("v_mul_f32 %0, %1, %2" : "=v"(p1) : "v"(fb), "v"(d32));\n'
-               '              asm volatile("v_mul_f32 %0, %1, %2" : "=v"(p2) : "v"(ga), "v"(d20));\n'
-               '              asm volatile("v_mul_f32 %0, %1, %2" : "=v"(p3) : "v"(fa), "v"(d31));\n'
-               '              asm volatile("v_add_f32 %0, %1, %2" : "=v"(g_fa) : "v"(p0), "v"(p1));\n'
-               '              asm volatile("v_add_f32 %0, %1, %2" : "=v"(g_fb) : "v"(p2), "v"(p3));\n'
-               '            }\n')
+               '        float p0, p1, p2, p3;\n'
+               '        asm volatile("v_mul_f32 %0, %1, %2" : "=v"(p0) : "v"(gb), "v"(d10));\n'
+               '        asm volatile("v_mul_f32 %0, %1, %2" : "=v"(p1) : "v"(fb), "v"(d32));\n'
+               '        asm volatile("v_mul_f32 %0, %1, %2" : "=v"(p2) : "v"(ga), "v"(d20));\n'
+               '        asm volatile("v_mul_f32 %0, %1, %2" : "=v"(p3) : "v"(fa), "v"(d31));\n'
+               '        asm volatile("v_add_f32 %0, %1, %2" : "=v"(g_fa) : "v"(p0), "v"(p1));\n'
+               '        asm volatile("v_add_f32 %0, %1, %2" : "=v"(g_fb) : "v"(p2), "v"(p3));\n'
+               '      }\n')
         return src.replace(G_FA + G_FB, new)
     if name == 'slp_bperm':
-        s = src.replace(QUAD1, '              acc += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, acc), 0x041F));\n')
-        return s.replace(QUAD2, '              acc += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, acc), 0x081F));\n')
+        s = src.replace(QUAD1, '        acc += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, acc), 0x041F));\n')
+        return s.replace(QUAD2, '        acc += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, acc), 0x081F));\n')
     raise KeyError(name)
 
 
