@@ -607,6 +607,47 @@ typedef struct nfi_metrics_args {
 } nfi_metrics_args;
 int nfi_image_metrics(const nfi_metrics_args* a, nfi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * View-direction mapper, the per-ray trunk.  Replaces ViewDirectionMapper.__init__'s layers as forward runs them
+ * (models/generator.py:194-241: fc0 .. fc6, norm1 .. norm4, two residual joins scaled by sqrt(2)/2, LeakyReLU(0.2);
+ * EqualizedLinear gains 1/sqrt(in), models/stylegan.py:170-177) by ONE launch forward and ONE launch backward, with no
+ * per-layer tensor in memory; the closure the class returns (243-251) is part of the field / render kernels (ray_features).
+ * Exact fp32 (plain FMAs).  All parameters are the modules' RAW tensors:
+ *   fc0_w [64,3] fc0_b [64];  fc1_w .. fc4_w [64,64] (no bias);  norm1_w/_b .. norm4_w/_b [64] (nn.LayerNorm(64), biased
+ *   variance, eps 1e-5);  fc5_w [64,64] fc5_b [64];  fc6_w [32,64] fc6_b [32].
+ *   fwd: viewdir [N,3] -> feature [N,32] (fc6's output; N is any positive count).  Deterministic: no atomics.
+ *   bwd: upstream g_feature [N,32] -> the 18 parameter gradients, shaped like the parameters, raw-parameter gradients
+ *        with the gains applied, all ACCUMULATED into caller-initialised buffers as nfi_sdf_gradient_bwd does (zero them
+ *        for a plain gradient; a second call into the same buffers adds its gradient to the first's; fp32 atomics, so
+ *        the summation order over rays is not fixed), and g_viewdir [N,3] or NULL = not wanted (WRITTEN, every row).
+ *        The 18 parameter-gradient pointers are given all or none: with none (a frozen generator, only g_viewdir
+ *        wanted) the weight-gradient stages and every atomic are skipped; g_viewdir must then be given.
+ *        The forward is recomputed per ray; no workspace, nothing is stashed by the forward.
+ *   Alignment: feature and g_feature are accessed as 16-byte vectors and must be 16-byte aligned (rows of 128 B).
+ *   Forward-only fields (feature) are ignored by bwd and the g_* fields by fwd.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct nfi_viewdir_mapper_args {
+  int64_t n_rays;
+  const float* viewdir;
+  const float *fc0_w, *fc0_b;
+  const float *fc1_w, *norm1_w, *norm1_b;
+  const float *fc2_w, *norm2_w, *norm2_b;
+  const float *fc3_w, *norm3_w, *norm3_b;
+  const float *fc4_w, *norm4_w, *norm4_b;
+  const float *fc5_w, *fc5_b, *fc6_w, *fc6_b;
+  float* feature;                /* forward output */
+  const float* g_feature;        /* backward input */
+  float *g_fc0_w, *g_fc0_b;
+  float *g_fc1_w, *g_norm1_w, *g_norm1_b;
+  float *g_fc2_w, *g_norm2_w, *g_norm2_b;
+  float *g_fc3_w, *g_norm3_w, *g_norm3_b;
+  float *g_fc4_w, *g_norm4_w, *g_norm4_b;
+  float *g_fc5_w, *g_fc5_b, *g_fc6_w, *g_fc6_b;
+  float* g_viewdir;              /* [N,3] out or NULL */
+} nfi_viewdir_mapper_args;
+int nfi_viewdir_mapper_fwd(const nfi_viewdir_mapper_args* a, nfi_stream_t stream);
+int nfi_viewdir_mapper_bwd(const nfi_viewdir_mapper_args* a, nfi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -355,7 +355,10 @@ def hip_forward(self, viewdir, c, request_model_outputs=['sampler'], model_input
 
     if 'sampler' in request_model_outputs:
         vd = None
-        if self.use_viewdir and viewdir is not None:
+        if self.use_viewdir and viewdir is not None and getattr(self, 'nfi_hip_viewdir_mapper', False):
+            # attach(..., hip_viewdir_mapper=True): the per-ray MLP is one HIP node, none of its modules is called
+            vd = (hip_ray_feature(self.viewdir_mapper, viewdir), self.viewdir_mapper.output)
+        elif self.use_viewdir and viewdir is not None:
             # generator.py:468-469: the per-ray MLP stays PyTorch; only its output and its last layer are handed over
             with _capture_ray_feature(self.viewdir_mapper) as cap:
                 self.viewdir_mapper(viewdir)
@@ -366,6 +369,75 @@ def hip_forward(self, viewdir, c, request_model_outputs=['sampler'], model_input
             texel_dtype=getattr(self, 'nfi_texel_dtype', ops.TEXEL_F32), request_model_outputs=request_model_outputs,
             viewdir=vd, texel_cache=texel_cache)
     return model_outputs
+
+
+_MAPPER_LAYERS = (('fc0', True), ('fc1', False), ('norm1', True), ('fc2', False), ('norm2', True), ('fc3', False),
+                  ('norm3', True), ('fc4', False), ('norm4', True), ('fc5', True), ('fc6', True))
+
+
+def viewdir_mapper_parameters(mapper):
+    """The 18 raw parameter tensors of a ViewDirectionMapper-shaped module (generator.py:194-215) in the order of
+    ops.VIEWDIR_MAPPER_PARAMS.  TypeError, naming what is missing, for a module of another shape."""
+    missing, params = [], []
+    for name, has_bias in _MAPPER_LAYERS:
+        layer = getattr(mapper, name, None)
+        if layer is None or getattr(layer, 'weight', None) is None:
+            missing.append(name if layer is None else name + '.weight')
+            continue
+        params.append(layer.weight)
+        bias = getattr(layer, 'bias', None)
+        if has_bias and bias is None:
+            missing.append(name + '.bias')
+        elif has_bias:
+            params.append(bias)
+        elif bias is not None:
+            missing.append(name + ' without a bias')
+    if getattr(mapper, 'output', None) is None:
+        missing.append('output')
+    if not missing:
+        for (pname, shape), t in zip(ops.VIEWDIR_MAPPER_PARAMS, params):
+            if tuple(t.shape) != shape:
+                missing.append('%s of shape %s (it is %s)' % (pname, list(shape), list(t.shape)))
+    if missing:
+        raise TypeError('hip_viewdir_mapper: %s is not a ViewDirectionMapper (models/generator.py:189-253); it lacks %s'
+                        % (type(mapper).__name__, ', '.join(missing)))
+    return params
+
+
+def hip_ray_feature(mapper, viewdir):
+    """ViewDirectionMapper.fc6's output for viewdir [...,1,3] as ONE autograd node over the HIP trunk kernels
+    (generator.py:223-239): [...,1,32].  Inputs: viewdir and the 18 parameter tensors; g_viewdir is computed only when
+    viewdir asks for a gradient."""
+    params = viewdir_mapper_parameters(mapper)
+    assert viewdir.shape[-2] == 1, viewdir.shape          # generator.py:241
+
+    def fwd(v, *ps):
+        return ops.viewdir_mapper_fwd(v, ps)
+
+    def bwd(inputs, outputs, grads, needs):
+        # (a frozen mapper - the inversion loop - asks for the direction gradient alone: no weight-gradient work)
+        g = ops.viewdir_mapper_bwd(inputs[0], inputs[1:], grads[0], want_viewdir=needs[0], want_params=any(needs[1:]))
+        return (g['g_viewdir'],) + tuple(g['g_' + n] for n, _ in ops.VIEWDIR_MAPPER_PARAMS)
+    return differentiable('viewdir_mapper', fwd, viewdir, *params, bwd=bwd)
+
+
+def _hip_mapper_forward(self, viewdir):
+    """ViewDirectionMapper.forward with the trunk on the HIP node.  Returns a closure of the class's meaning (generator.py:
+    243-251: the ray feature is added to the per-sample features of its ray, activation, then the `output` layer), so
+    the reference's own sampler keeps working.  The ray feature is an attribute of the closure; wrapped_forward, which
+    never sees the closure the class's forward keeps to itself, hangs a dict on the module for the duration of its call
+    and finds the feature there - a direct call of the mapper leaves nothing on the module."""
+    x = hip_ray_feature(self, viewdir)
+    if '_nfi_capture' in self.__dict__:
+        self.__dict__['_nfi_capture']['x'] = x
+
+    def closure(features):
+        assert features.shape[-1] == x.shape[-1], (tuple(x.shape), tuple(features.shape))
+        per_ray = features.reshape(*x.shape[:-2], -1, x.shape[-1])
+        y = torch.nn.functional.leaky_relu(x + per_ray, 0.2)
+        return self.output(y.reshape(features.shape))
+    closure.ray_feature = x
+    return closure
 
 
 class _capture_ray_feature:
@@ -406,6 +478,7 @@ def wrapped_forward(self, viewdir, c, request_model_outputs=['sampler'], model_i
     captured = {}
     hook = self.synthesis_network.register_forward_hook(lambda mod, inp, out: captured.__setitem__('planes', out))
     use_vd = bool(self.use_viewdir) and viewdir is not None
+    hip_vd = use_vd and getattr(self, 'nfi_hip_viewdir_mapper', False)
     import contextlib
     from . import handoff
     with contextlib.ExitStack() as stack:
@@ -413,7 +486,11 @@ def wrapped_forward(self, viewdir, c, request_model_outputs=['sampler'], model_i
         if 'path_length' in req:
             # differentiated twice (generator.py:484-499): the fused hand-off node is first-order only
             stack.enter_context(handoff.unfused(self.synthesis_network))
-        cap = stack.enter_context(_capture_ray_feature(self.viewdir_mapper)) if use_vd else None
+        cap = stack.enter_context(_capture_ray_feature(self.viewdir_mapper)) if use_vd and not hip_vd else None
+        if hip_vd:
+            # the mapper's forward was replaced at attach time (_hip_mapper_forward): it puts its HIP node's output here
+            cap = self.viewdir_mapper.__dict__['_nfi_capture'] = {}
+            stack.callback(self.viewdir_mapper.__dict__.pop, '_nfi_capture', None)
         model_outputs = self._nfi_original_forward(viewdir, c, req, model_inputs)
     planes = captured.get('planes')
     if planes is not None:
@@ -456,8 +533,13 @@ def bake(model, model_input, model_inputs={}):
     return baked
 
 
-def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_handoff=False):
+def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_handoff=False, hip_viewdir_mapper=False):
     """Gives a reference-style Generator the HIP sampler.  Returns the same module.
+
+    hip_viewdir_mapper (use_viewdir models only, off by default): the per-ray trunk of model.viewdir_mapper (fc0 .. fc6,
+    norm1 .. norm4; generator.py:223-239) runs as one HIP autograd node instead of its PyTorch modules, which are then
+    not called; a mapper of another shape raises TypeError here.  The mapper instance gets a new ``forward`` that still
+    returns the class's closure.
 
     fused_handoff: also fuse the tail of the last synthesis block (upsample + torgb + add, stylegan.py:424-433) into
     the HIP kernel that writes texels directly (nerf_from_image_amd.handoff): no NCHW <-> channel-last pass remains.
@@ -473,6 +555,15 @@ def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_hando
         raise AttributeError('attach(): module lacks %s' % missing)
     model.nfi_texel_dtype = texel_dtype
     model.nfi_hip_regularisers = bool(hip_regularisers)
+    if hip_viewdir_mapper:
+        if not getattr(model, 'use_viewdir', False) or not hasattr(model, 'viewdir_mapper'):
+            raise TypeError('attach(hip_viewdir_mapper=True): the model has no view-direction mapper (use_viewdir is off)')
+        viewdir_mapper_parameters(model.viewdir_mapper)          # TypeError for a mapper of another shape
+        model.viewdir_mapper.forward = types.MethodType(_hip_mapper_forward, model.viewdir_mapper)
+    elif getattr(getattr(model, 'viewdir_mapper', None), '__dict__', {}).get('forward') is not None and \
+            getattr(model.viewdir_mapper.__dict__['forward'], '__func__', None) is _hip_mapper_forward:
+        del model.viewdir_mapper.__dict__['forward']             # switched off again: the class's own forward
+    model.nfi_hip_viewdir_mapper = bool(hip_viewdir_mapper)
     if fused_handoff:
         from . import handoff
         handoff.fuse_last_block(model.synthesis_network)

@@ -5,6 +5,8 @@ its inputs, allocates the outputs as torch tensors, and passes raw device
 pointers plus ``torch.cuda.current_stream()`` to libnfi_hip.so.  Nothing here
 computes on the CPU and nothing falls back to ATen ops.
 """
+import math
+
 import torch
 
 from . import _lib
@@ -824,4 +826,88 @@ def torgb_texels_bwd(g_out, x, styles, weight, previous_image=None, want_weight=
     with torch.cuda.device(dev):
         _lib.call_struct('nfi_torgb_texels_bwd', 'nfi_torgb_args', _stream(x), n_scenes=B, in_channels=Cin, resolution=R,
                          x=x, styles=styles, weight=weight, previous_image=prev, g_texels=g, **out)
+    return out
+
+
+# --------------------------------------------------------------------------- #
+# view-direction mapper: the per-ray trunk (models/generator.py:194-241)
+# --------------------------------------------------------------------------- #
+# the 18 parameter tensors in the order of nfi_viewdir_mapper_args, with their shapes
+VIEWDIR_MAPPER_PARAMS = (('fc0_w', (64, 3)), ('fc0_b', (64,)),
+                         ('fc1_w', (64, 64)), ('norm1_w', (64,)), ('norm1_b', (64,)),
+                         ('fc2_w', (64, 64)), ('norm2_w', (64,)), ('norm2_b', (64,)),
+                         ('fc3_w', (64, 64)), ('norm3_w', (64,)), ('norm3_b', (64,)),
+                         ('fc4_w', (64, 64)), ('norm4_w', (64,)), ('norm4_b', (64,)),
+                         ('fc5_w', (64, 64)), ('fc5_b', (64,)), ('fc6_w', (32, 64)), ('fc6_b', (32,)))
+
+
+def _viewdir_mapper_inputs(viewdir, params):
+    viewdir = _f32c(viewdir, 'viewdir')
+    if viewdir.dim() < 1 or viewdir.shape[-1] != 3 or viewdir.numel() == 0:
+        raise ValueError('viewdir must be a non-empty [...,3] tensor, got %s' % (tuple(viewdir.shape),))
+    if len(params) != len(VIEWDIR_MAPPER_PARAMS):
+        raise ValueError('viewdir_mapper: %d parameter tensors expected (%s), got %d' % (
+            len(VIEWDIR_MAPPER_PARAMS), ', '.join(n for n, _ in VIEWDIR_MAPPER_PARAMS), len(params)))
+    kw = {}
+    for (name, shape), t in zip(VIEWDIR_MAPPER_PARAMS, params):
+        t = _f32c(t, name)
+        if tuple(t.shape) != shape:
+            raise ValueError('viewdir_mapper: %s must be %s, got %s' % (name, list(shape), tuple(t.shape)))
+        kw[name] = t
+    return viewdir, kw
+
+
+def viewdir_mapper_fwd(viewdir, params):
+    """viewdir [...,3], params: the 18 raw tensors in VIEWDIR_MAPPER_PARAMS order -> ViewDirectionMapper.fc6's output
+    [...,32], one launch."""
+    viewdir, kw = _viewdir_mapper_inputs(viewdir, params)
+    feature = torch.empty(viewdir.shape[:-1] + (32,), dtype=torch.float32, device=viewdir.device)
+    with torch.cuda.device(viewdir.device):
+        _lib.call_struct('nfi_viewdir_mapper_fwd', 'nfi_viewdir_mapper_args', _stream(viewdir), n_rays=viewdir.numel() // 3,
+                         viewdir=viewdir, feature=feature, **kw)
+    return feature
+
+
+def viewdir_mapper_bwd(viewdir, params, g_feature, want_viewdir=True, into=None, want_params=True):
+    """Backward of viewdir_mapper_fwd, one launch.  Returns dict('g_' + name for the 18 parameters, shaped like them, and
+    'g_viewdir' [...,3] or None).  into: such a dict from an earlier call - the parameter gradients of this call are
+    then ADDED to its tensors (the accumulate contract of the C entry); otherwise fresh zeroed tensors are filled.
+    want_params=False (a frozen mapper): only g_viewdir is computed, the parameter entries are None."""
+    viewdir, kw = _viewdir_mapper_inputs(viewdir, params)
+    g_feature = _f32c(g_feature, 'g_feature')
+    if g_feature.data_ptr() % 16:
+        g_feature = g_feature.clone()              # the kernel reads rows as 16-byte vectors (a view at an odd storage offset)
+    if not want_params:
+        if not want_viewdir or into is not None:
+            raise ValueError('viewdir_mapper_bwd: want_params=False computes g_viewdir only')
+        if tuple(g_feature.shape) != tuple(viewdir.shape[:-1]) + (32,):
+            raise ValueError('g_feature must be %s, got %s' % (tuple(viewdir.shape[:-1]) + (32,), tuple(g_feature.shape)))
+        g_viewdir = torch.empty_like(viewdir)
+        with torch.cuda.device(viewdir.device):
+            _lib.call_struct('nfi_viewdir_mapper_bwd', 'nfi_viewdir_mapper_args', _stream(viewdir), n_rays=viewdir.numel() // 3,
+                             viewdir=viewdir, g_feature=g_feature, g_viewdir=g_viewdir, **kw)
+        out = {'g_' + name: None for name, _ in VIEWDIR_MAPPER_PARAMS}
+        out['g_viewdir'] = g_viewdir
+        return out
+    if tuple(g_feature.shape) != tuple(viewdir.shape[:-1]) + (32,):
+        raise ValueError('g_feature must be %s, got %s' % (tuple(viewdir.shape[:-1]) + (32,), tuple(g_feature.shape)))
+    dev = viewdir.device
+    out = {}
+    if into is None:
+        # one zero-fill for the 18 buffers: they are views of one flat tensor (23 392 floats)
+        sizes = [math.prod(shape) for _, shape in VIEWDIR_MAPPER_PARAMS]
+        flat = torch.zeros((sum(sizes),), dtype=torch.float32, device=dev)
+        for (name, shape), part in zip(VIEWDIR_MAPPER_PARAMS, flat.split(sizes)):
+            out['g_' + name] = part.view(shape)
+    else:
+        for name, shape in VIEWDIR_MAPPER_PARAMS:
+            t = into['g_' + name]
+            if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError('viewdir_mapper_bwd: into[g_%s] must be a contiguous float32 GPU tensor %s' % (name, list(shape)))
+            out['g_' + name] = t
+    g_viewdir = torch.empty_like(viewdir) if want_viewdir else None
+    with torch.cuda.device(dev):
+        _lib.call_struct('nfi_viewdir_mapper_bwd', 'nfi_viewdir_mapper_args', _stream(viewdir), n_rays=viewdir.numel() // 3,
+                         viewdir=viewdir, g_feature=g_feature, g_viewdir=g_viewdir, **kw, **out)
+    out['g_viewdir'] = g_viewdir
     return out
