@@ -1455,6 +1455,29 @@ struct RayQueue {
     if (dry) return n_rays;
     return ray_at(q_cur, pos_next++);
   }
+  // fetch() in two halves, for a caller that has something to do while the atomic is under way (skip_miss_run):
+  // positions already claimed are handed out first and claimed() says whether there are any; claim_issue() starts the
+  // atomic if the next fetch() would start with one and returns its raw per-lane result; claim_finish() takes the claim
+  // over and is fetch().  The counter's offset goes through an opaque vector register: on a wave-uniform address the
+  // atomic optimiser rewrites the add so that its result is read back on the spot.
+  __device__ __forceinline__ bool claimed() const { return pos_next != pos_end; }
+  __device__ __forceinline__ uint32_t take() { return ray_at(q_cur, pos_next++); }      // only if claimed()
+  __device__ __forceinline__ uint32_t claim_issue() const {
+    uint32_t raw = 0, off = k.xcd_blocks ? q_cur * 16 : 0;
+    asm volatile("" : "+v"(off));
+    if (k.xcd_blocks && (claimed() || dry)) return raw;
+    if (lane == 0) raw = atomicAdd((k.xcd_blocks ? k.xcd_counter : k.counter) + off, k.xcd_blocks ? batch : 1u);
+    return raw;
+  }
+  __device__ __forceinline__ uint32_t claim_finish(uint32_t raw) {
+    const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)raw);
+    if (!k.xcd_blocks) return base;
+    if (!claimed() && !dry) {
+      if ((base >> (2 * bsh)) * 8u + q_cur < n_blocks) { pos_next = base; pos_end = base + batch; }
+      else q_cur = (q_cur + 1) & 7u;     // this queue is empty: fetch() goes stealing, from the next XCD's on
+    }
+    return fetch();
+  }
   // position of the single queue -> ray id.  Tile order: consecutive positions walk 8x8 pixel tiles, so the few thousand
   // rays in flight at any time cover a compact image region (a compact part of the three planes) instead of a band of
   // scanlines - better L2/Infinity-Cache reuse of the gather stream.  (A ray id of the per-XCD queues passes through.)
@@ -1595,6 +1618,70 @@ __device__ __forceinline__ void zero_stash_row(const RenderKernelParams& k, uint
   }
 }
 
+// everything a ray gets whose line stays outside the (inflated) scene cube: every sample has sigma == 0
+template <bool EXTRA, bool NRM, bool TAPS>
+__device__ __forceinline__ void put_missed_ray(const RenderKernelParams& k, uint32_t ray, int S, int lane, float bg) {
+  if (lane == 0) store_pixel(k, ray, bg, bg, bg, 0.0f, 0.0f);
+  if constexpr (EXTRA) zero_missed_maps<NRM>(k, ray, lane, bg);
+  if constexpr (TAPS) {
+    if (k.stash) zero_stash_row(k, ray, S, lane);
+  }
+}
+
+// The hit bytes of two rays through the scalar data path (the dwords that hold them, through a constant-address-space
+// view: the array is written by an earlier kernel and never by this one): ONE wait, and on lgkmcnt - not behind every
+// store the wave has in flight on the in-order vmcnt.  Both rays are wave-uniform.  Returns hit[ra] | hit[rb] << 8.
+__device__ __forceinline__ uint32_t hit_bytes_scalar(const RenderKernelParams& k, uint32_t ra, uint32_t rb) {
+  typedef __attribute__((address_space(4))) const uint32_t const_u32;
+  // (readfirstlane: where the compiler takes the ray index for divergent, the loads would become vector loads)
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(k.hit) + (uint32_t)__builtin_amdgcn_readfirstlane((int)ra),
+                  pb = reinterpret_cast<uintptr_t>(k.hit) + (uint32_t)__builtin_amdgcn_readfirstlane((int)rb);
+  uint32_t wa = *reinterpret_cast<const_u32*>(pa & ~(uintptr_t)3), wb = *reinterpret_cast<const_u32*>(pb & ~(uintptr_t)3);
+  asm volatile("" : "+s"(wa), "+s"(wb));       // both loads in front of the one wait: the compiler would sink the second
+  return ((wa >> ((uint32_t)(pa & 3) * 8u)) & 0xffu) | (((wb >> ((uint32_t)(pb & 3) * 8u)) & 0xffu) << 8);
+}
+
+// A run of missed rays.  Misses come in runs (the corners and edges of the pixel blocks), in which all waves of an XCD
+// turn over positions at once and nothing hides what a turn waits for - so a turn here is as little as a missed ray
+// needs: its hit byte.  Called with `cur` known to miss and `nxt` the position behind it, as yet untouched.  The
+// positions this wave has claimed (at most two at fetch_batch = 2) are tested behind ONE wait; if they all miss, the next
+// claim's atomic goes out before their background values are stored - nothing else of this wave is in flight then - and
+// the loop turns on the new pair.  The wave never holds more positions than render_fwd_kernel's pipeline does, and it
+// takes them in the same order.  Returns with `cur` the first position that hits, its inputs being loaded by `load`
+// (one exposed input latency per run), and `nxt` the position behind it - or with both >= n_rays: no work left.
+template <bool EXTRA, bool NRM, bool TAPS, class Load>
+__device__ __forceinline__ void skip_miss_run(RayQueue& queue, const RenderKernelParams& k, int S, int lane, float bg,
+                                              uint32_t& cur, uint32_t& nxt, Load&& load) {
+  put_missed_ray<EXTRA, NRM, TAPS>(k, queue.ray_of(cur), S, lane, bg);
+  uint32_t a = nxt;
+  while (a < queue.n_rays) {
+    const bool two = queue.claimed();
+    const uint32_t b = two ? queue.take() : a;
+    const uint32_t ra = queue.ray_of(a), rb = queue.ray_of(b);
+    const uint32_t hits = hit_bytes_scalar(k, ra, rb);
+    uint32_t claim;
+    bool ends = true;
+    if (hits & 2u) {
+      cur = a; load(ra);
+      if (two) { nxt = b; return; }
+      claim = queue.claim_issue();
+    } else if (two && (hits & 0x200u)) {
+      put_missed_ray<EXTRA, NRM, TAPS>(k, ra, S, lane, bg);
+      cur = b; load(rb);
+      claim = queue.claim_issue();
+    } else {
+      claim = queue.claim_issue();
+      put_missed_ray<EXTRA, NRM, TAPS>(k, ra, S, lane, bg);
+      if (two) put_missed_ray<EXTRA, NRM, TAPS>(k, rb, S, lane, bg);
+      ends = false;
+    }
+    const uint32_t got = queue.claim_finish(claim);       // (the one place of this helper that fetch()'s code is at)
+    if (ends) { nxt = got; return; }
+    a = got;
+  }
+  cur = nxt = a;
+}
+
 // Persistent kernel, S <= 64 samples per pass: one wave per ray, rays handed out by a RayQueue (scene-major, so the chip
 // works on one scene's 25 MB of texels at a time).  The ray index two steps ahead is being fetched and the next ray's
 // inputs are loaded (RayInputs) while the current ray is marched.
@@ -1659,143 +1746,145 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
   unsigned long long pc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tk0 = PROF ? __builtin_readcyclecounter() : 0;
   if (cur < n_rays) load_inputs(queue.ray_of(cur), in);
+  // A ray that misses the cube never enters the loop below: it and the missed ones behind it are dealt with here, before
+  // the first ray and behind every marched one, and `in` is loaded afresh for the ray that ends the run.  (Behind the
+  // loop's turn and not in front of it: a second way back to the loop's head cost 14-23 vector registers.  The hit byte
+  // through a scalar register: this branch writes the queue's wave-uniform state, and under a condition that sits in a
+  // vector register the compiler moves that state, the ray index and with it the texel descriptor to vector registers.)
+  auto skip_run = [&]() {
+    if (k.skip_missed && cur < n_rays && !((uint32_t)__builtin_amdgcn_readfirstlane((int)in.hit) & 2))
+      skip_miss_run<EXTRA, NRM, TAPS>(queue, k, S, lane, bg, cur, nxt, [&](uint32_t r) { load_inputs(r, in); });
+  };
+  skip_run();
   while (cur < n_rays) {
     if (nxt < n_rays) load_inputs(queue.ray_of(nxt), pre);
     const uint32_t ray = queue.ray_of(cur);
     const uint32_t hitb = in.hit;
     // the ray's five results: stored after the work fetch at the end of the iteration (see there)
     float out_r = bg, out_g = bg, out_b = bg, out_d = 0.0f, out_m = 0.0f;
-    if (k.skip_missed && !(hitb & 2)) {
-      // the ray's line stays outside the (inflated) scene cube: every sample has sigma == 0
-      if constexpr (EXTRA) zero_missed_maps<NRM>(k, ray, lane, bg);
-      if constexpr (TAPS) {
-        if (k.stash) zero_stash_row(k, ray, S, lane);
-      }
-    } else {
-      unsigned long long t0 = PROF ? __builtin_readcyclecounter() : 0;
-      const int scene = (int)fastdiv(ray, k.div_scene_rays);
-      if (scene != cur_scene) {
-        cur_scene = scene;
-        enter_scene<TEX>(P, k, vf, scene, lane);
-      }
-      const float ox = in.ox, oy = in.oy, oz = in.oz, dx = in.dx, dy = in.dy, dz = in.dz;
-      float near = in.near, far = in.far;
-      finish_planes((hitb & 1) != 0, fill_near, fill_far, near, far);
-      const float dnorm = norm3(dx, dy, dz);
-      const size_t rs = (size_t)ray * (size_t)k.tap_stride;      // row of this ray in the per-sample tap / stash arrays
+    unsigned long long t0 = PROF ? __builtin_readcyclecounter() : 0;
+    const int scene = (int)fastdiv(ray, k.div_scene_rays);
+    if (scene != cur_scene) {
+      cur_scene = scene;
+      enter_scene<TEX>(P, k, vf, scene, lane);
+    }
+    const float ox = in.ox, oy = in.oy, oz = in.oz, dx = in.dx, dy = in.dy, dz = in.dz;
+    float near = in.near, far = in.far;
+    finish_planes((hitb & 1) != 0, fill_near, fill_far, near, far);
+    const float dnorm = norm3(dx, dy, dz);
+    const size_t rs = (size_t)ray * (size_t)k.tap_stride;      // row of this ray in the per-sample tap / stash arrays
 
-      // ---- coarse pass ----
-      float tc = 0.0f;
-      if (valid) tc = stratified_depth(near, far, lane, S, in.noise, k.noise_c != nullptr);
-      MergeIn c;
-      float ncx = 0.0f, ncy = 0.0f, ncz = 0.0f, nfx = 0.0f, nfy = 0.0f, nfz = 0.0f;     // NRM: the samples' unit normals
-      unsigned long long t1 = PROF ? __builtin_readcyclecounter() : 0;
-      {
-        SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM>(P, k.scene_range, lane, ox + dx * tc, oy + dy * tc, oz + dz * tc,
-                                                                      valid, semT, nullptr, &slab.srt[0][0], PROF ? pc : nullptr,
-                                                                      k.xray, (int)ray);
-        c.t = tc; c.sigma = q.sigma; c.r = q.r; c.g = q.g; c.b = q.b;
-        if constexpr (NRM) { ncx = q.nx; ncy = q.ny; ncz = q.nz; }
-      }
-      int n = S;
-      int rank_c = lane, rank_f = 0;
-      unsigned long long t2 = PROF ? __builtin_readcyclecounter() : 0, t3 = t2, t4 = t2, t5 = t2;
-      if (k.fine) {
-        // ---- hierarchical resampling + fine pass ----
-        ResampleTaps rt;
-        float tf = resample_ray(slab, c.sigma, tc, S, dnorm, in.u, lane, TERM ? &rt : nullptr);
-        MergeIn f;
-        if (PROF) { asm volatile("" :: "v"(tf)); t3 = __builtin_readcyclecounter(); }
-        if constexpr (TERM) {
-          // depth of the first coarse sample in front of which the coarse transmittance is already below eps
-          const uint64_t dm = __ballot(valid && rt.T < k.term_eps);
-          float t_dead = INFINITY;
-          if (dm) t_dead = bits2f((uint32_t)__builtin_amdgcn_readlane((int)f2bits(tc), (int)__builtin_ctzll(dm)));
-          // compaction: live fine samples to the low lanes, dropped ones behind them (they keep their depth)
-          const bool live = valid && tf <= t_dead;
-          const uint64_t lm = __ballot(live);
-          const int nl = __builtin_popcountll(lm);
-          const int nb = __builtin_popcountll(lm & ((1ull << lane) - 1ull));
-          const int pos = live ? nb : nl + (lane - nb);
-          wave_lds_fence();
-          slab.cdf[pos] = tf;
-          wave_lds_fence();
-          tf = slab.cdf[lane];
-          wave_lds_fence();
-          const bool vl = lane < nl;
-          SampleOut q = field_wave<TEX, ATT, true, PREC, VD>(P, k.scene_range, lane, ox + dx * tf, oy + dy * tf, oz + dz * tf, vl,
-                                                             nullptr, nullptr, &slab.srt[0][0], nullptr, k.xray, (int)ray);
-          f.t = tf; f.sigma = vl ? q.sigma : 0.0f; f.r = vl ? q.r : 0.0f; f.g = vl ? q.g : 0.0f; f.b = vl ? q.b : 0.0f;
-        } else {
-          SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM>(P, k.scene_range, lane, ox + dx * tf, oy + dy * tf, oz + dz * tf,
-                                                                        valid, semT ? semT + 64 : nullptr, nullptr, &slab.srt[0][0],
-                                                                        PROF ? pc : nullptr, k.xray, (int)ray);
-          f.t = tf; f.sigma = q.sigma; f.r = q.r; f.g = q.g; f.b = q.b;
-          if constexpr (NRM) { nfx = q.nx; nfy = q.ny; nfz = q.nz; }
-        }
-        if constexpr (TAPS) {
-          if (valid) store_sample_tap(k.t_fine, k.sigma_fine, k.rgb_fine, rs + lane, tf, f.sigma, f.r, f.g, f.b);
-        }
-        n = 2 * S;
-        if (PROF) t4 = __builtin_readcyclecounter();
-        merge_pair_scatter(slab, c, f, S, lane, rank_c, rank_f);
-        if (PROF) t5 = __builtin_readcyclecounter();
-      } else {
-        if (valid) { slab.srt[0][lane] = c.t; slab.srt[1][lane] = c.sigma; slab.srt[2][lane] = c.r; slab.srt[3][lane] = c.g; slab.srt[4][lane] = c.b; }
+    // ---- coarse pass ----
+    float tc = 0.0f;
+    if (valid) tc = stratified_depth(near, far, lane, S, in.noise, k.noise_c != nullptr);
+    MergeIn c;
+    float ncx = 0.0f, ncy = 0.0f, ncz = 0.0f, nfx = 0.0f, nfy = 0.0f, nfz = 0.0f;     // NRM: the samples' unit normals
+    unsigned long long t1 = PROF ? __builtin_readcyclecounter() : 0;
+    {
+      SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM>(P, k.scene_range, lane, ox + dx * tc, oy + dy * tc, oz + dz * tc,
+                                                                    valid, semT, nullptr, &slab.srt[0][0], PROF ? pc : nullptr,
+                                                                    k.xray, (int)ray);
+      c.t = tc; c.sigma = q.sigma; c.r = q.r; c.g = q.g; c.b = q.b;
+      if constexpr (NRM) { ncx = q.nx; ncy = q.ny; ncz = q.nz; }
+    }
+    int n = S;
+    int rank_c = lane, rank_f = 0;
+    unsigned long long t2 = PROF ? __builtin_readcyclecounter() : 0, t3 = t2, t4 = t2, t5 = t2;
+    if (k.fine) {
+      // ---- hierarchical resampling + fine pass ----
+      ResampleTaps rt;
+      float tf = resample_ray(slab, c.sigma, tc, S, dnorm, in.u, lane, TERM ? &rt : nullptr);
+      MergeIn f;
+      if (PROF) { asm volatile("" :: "v"(tf)); t3 = __builtin_readcyclecounter(); }
+      if constexpr (TERM) {
+        // depth of the first coarse sample in front of which the coarse transmittance is already below eps
+        const uint64_t dm = __ballot(valid && rt.T < k.term_eps);
+        float t_dead = INFINITY;
+        if (dm) t_dead = bits2f((uint32_t)__builtin_amdgcn_readlane((int)f2bits(tc), (int)__builtin_ctzll(dm)));
+        // compaction: live fine samples to the low lanes, dropped ones behind them (they keep their depth)
+        const bool live = valid && tf <= t_dead;
+        const uint64_t lm = __ballot(live);
+        const int nl = __builtin_popcountll(lm);
+        const int nb = __builtin_popcountll(lm & ((1ull << lane) - 1ull));
+        const int pos = live ? nb : nl + (lane - nb);
         wave_lds_fence();
-      }
-      float w[2];
-      CompositeOut o = composite_slab<2>(slab, n, dnorm, k.white, lane, w);
-      out_r = o.r; out_g = o.g; out_b = o.b; out_d = o.depth; out_m = o.mask;
-      if constexpr (EXTRA) {
-        if (k.coords) composite_coords<2>(slab, w, n, lane, ox, oy, oz, dx, dy, dz, k.coords + (size_t)ray * 3);
-        float wc = 0.0f, wf = 0.0f;
-        if ((SEMP > 0 && semT) || NRM) {
-          // the merged weights back in source order (lane = sample): the cdf row is free after the merge
-          wave_lds_fence();
-          slab.cdf[lane] = w[0]; slab.cdf[64 + lane] = w[1];
-          wave_lds_fence();
-          wc = valid ? slab.cdf[rank_c] : 0.0f;
-          wf = (valid && k.fine) ? slab.cdf[rank_f] : 0.0f;
-        }
-        if constexpr (NRM) {
-          // normal_map = sum_k w_k n_k (+ 1 - mask on a white background), lib/nerf_utils.py:149-151, 159
-          const float bgn = k.white ? 1.0f - o.mask : 0.0f;
-          const float mx = wave_sum(wc * ncx + wf * nfx) + bgn, my = wave_sum(wc * ncy + wf * nfy) + bgn,
-                      mz = wave_sum(wc * ncz + wf * nfz) + bgn;
-          if (lane == 0) { float* q = k.normals + (size_t)ray * 3; q[0] = mx; q[1] = my; q[2] = mz; }
-        }
-        if constexpr (SEMP > 0) {
-          if (semT) {
-            const lds_float* sl = (const lds_float*)semT;
-            float mine = 0.0f;
-            for (int a = 0; a < k.A; ++a) {
-              const float sa = wave_sum(wc * sl[a * kSemPitch + lane] + wf * sl[a * kSemPitch + 64 + lane]);
-              if (lane == a) mine = sa;
-            }
-            if (lane < k.A) k.semantics[(size_t)ray * k.A + lane] = mine;
-          }
-        }
+        slab.cdf[pos] = tf;
+        wave_lds_fence();
+        tf = slab.cdf[lane];
+        wave_lds_fence();
+        const bool vl = lane < nl;
+        SampleOut q = field_wave<TEX, ATT, true, PREC, VD>(P, k.scene_range, lane, ox + dx * tf, oy + dy * tf, oz + dz * tf, vl,
+                                                           nullptr, nullptr, &slab.srt[0][0], nullptr, k.xray, (int)ray);
+        f.t = tf; f.sigma = vl ? q.sigma : 0.0f; f.r = vl ? q.r : 0.0f; f.g = vl ? q.g : 0.0f; f.b = vl ? q.b : 0.0f;
+      } else {
+        SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM>(P, k.scene_range, lane, ox + dx * tf, oy + dy * tf, oz + dz * tf,
+                                                                      valid, semT ? semT + 64 : nullptr, nullptr, &slab.srt[0][0],
+                                                                      PROF ? pc : nullptr, k.xray, (int)ray);
+        f.t = tf; f.sigma = q.sigma; f.r = q.r; f.g = q.g; f.b = q.b;
+        if constexpr (NRM) { nfx = q.nx; nfy = q.ny; nfz = q.nz; }
       }
       if constexpr (TAPS) {
-        if (lane == 0) {
-          if (k.near_plane) k.near_plane[ray] = near;
-          if (k.far_plane) k.far_plane[ray] = far;
-        }
-        if (valid) {
-          store_sample_tap(k.t_coarse, k.sigma_coarse, k.rgb_coarse, rs + lane, tc, c.sigma, c.r, c.g, c.b);
-          if (k.perm) {
-            k.perm[(size_t)ray * n + rank_c] = lane;
-            if (k.fine) k.perm[(size_t)ray * n + rank_f] = S + lane;
+        if (valid) store_sample_tap(k.t_fine, k.sigma_fine, k.rgb_fine, rs + lane, tf, f.sigma, f.r, f.g, f.b);
+      }
+      n = 2 * S;
+      if (PROF) t4 = __builtin_readcyclecounter();
+      merge_pair_scatter(slab, c, f, S, lane, rank_c, rank_f);
+      if (PROF) t5 = __builtin_readcyclecounter();
+    } else {
+      if (valid) { slab.srt[0][lane] = c.t; slab.srt[1][lane] = c.sigma; slab.srt[2][lane] = c.r; slab.srt[3][lane] = c.g; slab.srt[4][lane] = c.b; }
+      wave_lds_fence();
+    }
+    float w[2];
+    CompositeOut o = composite_slab<2>(slab, n, dnorm, k.white, lane, w);
+    out_r = o.r; out_g = o.g; out_b = o.b; out_d = o.depth; out_m = o.mask;
+    if constexpr (EXTRA) {
+      if (k.coords) composite_coords<2>(slab, w, n, lane, ox, oy, oz, dx, dy, dz, k.coords + (size_t)ray * 3);
+      float wc = 0.0f, wf = 0.0f;
+      if ((SEMP > 0 && semT) || NRM) {
+        // the merged weights back in source order (lane = sample): the cdf row is free after the merge
+        wave_lds_fence();
+        slab.cdf[lane] = w[0]; slab.cdf[64 + lane] = w[1];
+        wave_lds_fence();
+        wc = valid ? slab.cdf[rank_c] : 0.0f;
+        wf = (valid && k.fine) ? slab.cdf[rank_f] : 0.0f;
+      }
+      if constexpr (NRM) {
+        // normal_map = sum_k w_k n_k (+ 1 - mask on a white background), lib/nerf_utils.py:149-151, 159
+        const float bgn = k.white ? 1.0f - o.mask : 0.0f;
+        const float mx = wave_sum(wc * ncx + wf * nfx) + bgn, my = wave_sum(wc * ncy + wf * nfy) + bgn,
+                    mz = wave_sum(wc * ncz + wf * nfz) + bgn;
+        if (lane == 0) { float* q = k.normals + (size_t)ray * 3; q[0] = mx; q[1] = my; q[2] = mz; }
+      }
+      if constexpr (SEMP > 0) {
+        if (semT) {
+          const lds_float* sl = (const lds_float*)semT;
+          float mine = 0.0f;
+          for (int a = 0; a < k.A; ++a) {
+            const float sa = wave_sum(wc * sl[a * kSemPitch + lane] + wf * sl[a * kSemPitch + 64 + lane]);
+            if (lane == a) mine = sa;
           }
+          if (lane < k.A) k.semantics[(size_t)ray * k.A + lane] = mine;
         }
-        store_sorted_taps<2>(k, slab, w, ray, n, lane);
       }
-      wave_lds_fence();  // slab is reused by the next ray
-      if (PROF) {
-        unsigned long long t6 = __builtin_readcyclecounter();
-        pc[4] += t1 - t0; pc[5] += t2 - t1; pc[6] += t3 - t2; pc[7] += t4 - t3; pc[8] += t5 - t4; pc[9] += t6 - t5; pc[10] += 1;
+    }
+    if constexpr (TAPS) {
+      if (lane == 0) {
+        if (k.near_plane) k.near_plane[ray] = near;
+        if (k.far_plane) k.far_plane[ray] = far;
       }
+      if (valid) {
+        store_sample_tap(k.t_coarse, k.sigma_coarse, k.rgb_coarse, rs + lane, tc, c.sigma, c.r, c.g, c.b);
+        if (k.perm) {
+          k.perm[(size_t)ray * n + rank_c] = lane;
+          if (k.fine) k.perm[(size_t)ray * n + rank_f] = S + lane;
+        }
+      }
+      store_sorted_taps<2>(k, slab, w, ray, n, lane);
+    }
+    wave_lds_fence();  // slab is reused by the next ray
+    if (PROF) {
+      unsigned long long t6 = __builtin_readcyclecounter();
+      pc[4] += t1 - t0; pc[5] += t2 - t1; pc[6] += t3 - t2; pc[7] += t4 - t3; pc[8] += t5 - t4; pc[9] += t6 - t5; pc[10] += 1;
     }
     // The work fetch waits for its atomic's round trip - and, vmcnt being ONE in-order counter of loads and stores, for
     // every store the wave has in flight.  Here, after the ray's arithmetic and BEFORE its result stores, nothing of this
@@ -1805,6 +1894,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
     in = pre;
     cur = nxt;
     nxt = fly;
+    skip_run();
   }
   if (PROF && k.prof && lane == 0) {
     pc[11] = __builtin_readcyclecounter() - tk0;
