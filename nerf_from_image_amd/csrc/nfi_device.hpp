@@ -483,7 +483,7 @@ struct TileOut {
 //   tile_issue    - 24 x buffer_load_dwordx4 (3 planes x 4 bilinear corners x 2 half-lines); the lane
 //                   owns 16-byte chunk q of each half-line
 //   tile_bilinear - consumes the 96 texel registers into the lane's 8 interpolated features
-//   tile_mlp      - decoder MLP on MFMA + density / colour epilogue (MFMA lane layout)
+//   tile_mlp      - decoder MLP on MFMA (MFMA lane layout), up to its raw outputs
 template <int TEX>
 struct TileTex {
   float v[3][4][8];
@@ -743,8 +743,10 @@ __device__ __forceinline__ void pin_deriv_sums(float (&feat)[8], float (&dfeat)[
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// density / colour epilogue on the decoder outputs o (lane (g,j): rows 4g..4g+3 of point j; row 0 =
-// distance/density, rows 1.. = colour logits pre-scaled by log2e)
+// density / colour epilogue PER TILE on the decoder outputs o (lane (g,j): rows 4g..4g+3 of point j; row 0 =
+// distance/density, rows 1.. = colour logits pre-scaled by log2e) - the form the kernels without room for the output
+// table or not timed with it keep (field_wave<..., OTAB = false>); in the plain render kernels with attention
+// sample_epilogue below does this once per 64 samples
 // SEMP: where the softmax probabilities of a point go.  0: sem[n] is a global row [A] (the sampler closure's
 // 'semantics' output); < 0: the same table with unorm16 entries, pitch -SEMP (tile_epilogue); > 0: sem[n] addresses the
 // point's column of a per-wave LDS table [A][SEMP] (attribute-major, the
@@ -827,13 +829,142 @@ __device__ __forceinline__ void tile_epilogue(const FieldParams& P, int lane, co
   }
 }
 
-// Decoder MLP + density / colour epilogue for N tiles at once (N = 2 in the renderer: the two tiles'
-// MFMA chains, softplus blocks and cross-lane reductions are independent, so a wave has twice the
-// instruction-level parallelism against the dependent latencies that dominate this phase, and the
-// operand fragments are read from LDS once for both).
-// Returns (in every lane of the four groups) the decoder outputs for point j of each tile.
-//   outside[n]: 1.0f if the point is outside the scene cube.
-//   sem[n]: if non-null, softmax probabilities are written to sem[n][A] (global) for this point.
+// ---- decoder output table + the epilogue in the sample layout -------------------------------------------------------
+// field_wave parks every live tile's decoder outputs o in a per-wave LDS table and runs the epilogue ONCE per call with
+// lane = sample: 64 points at once with every lane busy, where tile_epilogue computes sigma identically in the four
+// channel groups, spreads 10 useful softmax rows over 16 (group, register) slots and pays five cross-row reductions per
+// tile.  Row-major [row][kOutPitch], row = decoder output row, column = sample 16 t + j.  A tile's four ds_write_b32
+// (lane (g, j) -> rows 4 g + r) fall into banks 16 g + j + const because 4 * kOutPitch = 16 (mod 32 and 64): conflict-free; the
+// sample-layout reads of one row are 64 consecutive dwords: conflict-free.  Rows 0 .. 15 with attention (row 15 is
+// written and never read), rows 0 .. 3 (group 0's) without.
+constexpr int kOutPitch = 64 + 4;
+constexpr int kOutLastRow = 14;       // the largest row the epilogue reads: NFI_MAX_ATTENTION (asserted in nfi_kernels.hip)
+template <bool ATT>
+constexpr int kOutTabFloats = (ATT ? 16 : 4) * kOutPitch;
+
+// tile t's outputs -> the table (MFMA layout: lane (g, j) holds rows 4 g .. 4 g + 3 of point j)
+template <bool ATT>
+__device__ __forceinline__ void park_tile_outputs(float* otab, int lane, int t, const f32x4& o) {
+  const int g = lane >> 4, j = lane & 15;
+  // explicit LDS address space: ds_write, ordered with the wave's other LDS traffic (a flat store is not)
+  auto* q = (__attribute__((address_space(3))) float*)otab + (4 * g) * kOutPitch + 16 * t + j;
+  if (ATT || g == 0) {
+    q[0] = o.x; q[kOutPitch] = o.y; q[2 * kOutPitch] = o.z; q[3 * kOutPitch] = o.w;
+  }
+}
+
+// The epilogue of tile_epilogue for the lane's OWN sample, read from the table: same arithmetic, same association order -
+// per channel group g the sums over rows 4 g .. 4 g + 3 in order from +0, then (g0 + g1) + (g2 + g3), which is what
+// sum_xor16 followed by sum_xor32 computes (the float add is commutative) - so the results are the same bits.  Rows 0 and
+// 15 and whole groups beyond A are left out of the chains: their e is exactly 0 and their vf row is exactly 0
+// (enter_scene / stage_field_lds), so each would add +0 to a sum that is never -0.  A row beyond A inside a live group
+// stays in its chain behind a select, as in tile_epilogue.
+// live: the lane holds a point AND its tile went through the decoder.  Everything a lane without one returns is 0 by
+// SELECT, never by multiplication with what the table holds: a skipped tile's slots keep an earlier call's values - an
+// earlier ray's, possibly another scene's and not finite - or uninitialised LDS.
+// sem: null, or where this lane's probabilities go (see tile_epilogue for the three forms); written for live lanes only.
+template <bool ATT, int SEMP>
+__device__ __forceinline__ void sample_epilogue(const FieldParams& P, int lane, const float* otab, bool outside, bool live,
+                                                float* sem, float& o_sdf, float& o_sigma, float& o_r, float& o_g, float& o_b) {
+  const auto* tb = (const __attribute__((address_space(3))) float*)otab + lane;
+  const float sdf = tb[0];
+  const float outs = outside ? 1.0f : 0.0f;
+  float sigma, cr, cg, cb;
+  if (P.use_sdf) {
+    // sigma = (1/alpha) * (0.5 + 0.5*sign(-d)*(1 - exp(-|d|/beta))) * (1 - outside)
+    float e = __builtin_amdgcn_exp2f(fabsf(sdf) * P.neg_log2e_over_beta);
+    float sgn = (sdf < 0.0f) ? 0.5f : ((sdf > 0.0f) ? -0.5f : 0.0f);
+    float cdf = 0.5f + sgn * (1.0f - e);
+    sigma = P.inv_alpha * (cdf * (1.0f - outs));
+  } else {
+    float d = sdf - 1.0f;
+    float sp = (d > 20.0f) ? d : log1pf(__expf(d));
+    sigma = sp * (1.0f - outs);
+  }
+  if constexpr (ATT) {
+    // softmax over rows 1..A (pre-scaled by log2e); A and the group conditions are wave-uniform
+    const int A = P.n_attention;
+    float x[16], e16[16];
+    float m = -INFINITY;
+#pragma unroll
+    for (int gi = 0; gi < 4; ++gi) {
+      if (4 * gi <= A) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 4 * gi + r;
+          if (row == 0 || row > kOutLastRow) continue;
+          x[row] = tb[row * kOutPitch];
+          m = (row <= A) ? fmaxf(m, x[row]) : m;
+        }
+      }
+    }
+    // the scene's attention values: one row per decoder row, wave-uniform addresses (LDS broadcast reads)
+    const f32x4* vf = reinterpret_cast<const f32x4*>(P.vf);
+    float seg[4], srg[4], sgg[4], sbg[4];
+#pragma unroll
+    for (int gi = 0; gi < 4; ++gi) {
+      float se = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f;
+      if (4 * gi <= A) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 4 * gi + r;
+          if (row == 0 || row > kOutLastRow) continue;
+          const float e = (row <= A) ? __builtin_amdgcn_exp2f(x[row] - m) : 0.0f;
+          e16[row] = e;
+          const f32x4 v = vf[row];
+          se += e;
+          sr = fmaf(e, v.x, sr);
+          sg = fmaf(e, v.y, sg);
+          sb = fmaf(e, v.z, sb);
+        }
+      }
+      seg[gi] = se; srg[gi] = sr; sgg[gi] = sg; sbg[gi] = sb;
+    }
+    const float se = (seg[0] + seg[1]) + (seg[2] + seg[3]), sr = (srg[0] + srg[1]) + (srg[2] + srg[3]),
+                sg = (sgg[0] + sgg[1]) + (sgg[2] + sgg[3]), sb = (sbg[0] + sbg[1]) + (sbg[2] + sbg[3]);
+    float inv = __builtin_amdgcn_rcpf(se);
+    inv = inv * (2.0f - se * inv);      // one Newton step: the quotient is then within 1 ulp
+    cr = sr * inv; cg = sg * inv; cb = sb * inv;
+    if (sem && live) {
+#pragma unroll
+      for (int gi = 0; gi < 4; ++gi) {
+        if (4 * gi <= A) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = 4 * gi + r;
+            if (row == 0 || row > kOutLastRow) continue;
+            if constexpr (SEMP > 0) {
+              auto* q = (__attribute__((address_space(3))) float*)sem;
+              if (row <= A) q[(row - 1) * SEMP] = e16[row] * inv;
+            } else if constexpr (SEMP < 0) {
+              // 16-bit table (the 128 + 128 kernel: half the LDS, two workgroups per CU): unorm16, p = q / 65535,
+              // |error| <= 7.7e-6 per sample - and the composited map is a convex combination of the samples
+              auto* q = (__attribute__((address_space(3))) unsigned short*)sem;
+              const float pq = fminf(__builtin_rintf(e16[row] * inv * 65535.0f), 65535.0f);
+              if (row <= A) q[(row - 1) * (-SEMP)] = (unsigned short)(int)pq;
+            } else {
+              if (row <= A) sem[row - 1] = e16[row] * inv;
+            }
+          }
+        }
+      }
+    }
+  } else {
+    // rgb = sigmoid(f)*2.004 - 1.002, features (rows 1..3) pre-scaled by log2e
+    const float r1 = tb[kOutPitch], r2 = tb[2 * kOutPitch], r3 = tb[3 * kOutPitch];
+    cr = (1.0f / (1.0f + __builtin_amdgcn_exp2f(-r1))) * 2.004f - 1.002f;
+    cg = (1.0f / (1.0f + __builtin_amdgcn_exp2f(-r2))) * 2.004f - 1.002f;
+    cb = (1.0f / (1.0f + __builtin_amdgcn_exp2f(-r3))) * 2.004f - 1.002f;
+  }
+  o_sdf = live ? sdf : 0.0f; o_sigma = live ? sigma : 0.0f;
+  o_r = live ? cr : 0.0f; o_g = live ? cg : 0.0f; o_b = live ? cb : 0.0f;
+}
+
+// Decoder MLP for N tiles at once (N = 2 in the renderer: the two tiles' MFMA chains and softplus
+// blocks are independent, so a wave has twice the instruction-level parallelism against the
+// dependent latencies that dominate this phase, and the operand fragments are read from LDS once
+// for both).  Stops at the raw outputs o[n] (lane (g, j): rows 4g..4g+3 of point j of tile n): the
+// density / colour epilogue is field_wave's, once per call (sample_epilogue) or per tile (tile_epilogue).
 // x[0..7] -> hi = fp16(x) (round toward zero), lo = fp16(x - hi): hi + lo carries 22 significand bits for values of
 // order one.  The resolution is ABSOLUTE, 2^-24 (the fp16 subnormal spacing; subnormals are preserved by the MFMA in
 // the default kernel mode): fine for activations, whose products accumulate with O(1) terms, NOT for operands of
@@ -949,13 +1080,11 @@ __device__ __forceinline__ void normal_contraction(const FieldParams& P, int lan
 //         other waves (tools/probes/mfma_valu_overlap.hip), so this time comes straight off the kernel.
 // NRM: Gout[n][ct] receives G = W1'^T (sigmoid(h) * W2'[0]) of tile n - d(distance) / d(feature) up to the positive factors
 // the normalisation drops -, rows 16 ct + 4 g + r of point j: the operand of the normal map (field_wave).
-template <bool ATT, int N, int PREC, int SEMP = 0, bool NRM = false>
-__device__ __forceinline__ void tile_mlp(const FieldParams& P, int lane, const float (&feat)[N][8],
-                                         const float (&outside)[N], float* const (&sem)[N], TileOut (&res)[N],
+template <int N, int PREC, bool NRM = false>
+__device__ __forceinline__ void tile_mlp(const FieldParams& P, int lane, const float (&feat)[N][8], f32x4 (&o)[N],
                                          f32x4 (&Gout)[N][2]) {
   const int g = lane >> 4;
   const f32x4* ldsv = reinterpret_cast<const f32x4*>(P.lds);
-  f32x4 o[N];
   if constexpr (PREC == 1) {
     const u32x4* ldsu = reinterpret_cast<const u32x4*>(P.lds);
     f16x8 fh[N], fl[N];
@@ -1070,14 +1199,6 @@ __device__ __forceinline__ void tile_mlp(const FieldParams& P, int lane, const f
 #pragma unroll
     for (int n = 0; n < N; ++n) o[n] = o0[n] + o1[n];   // lane (j,g): outputs 4g..4g+3 of point j; row 0 = sdf/density
   }
-
-  tile_epilogue<ATT, N, SEMP>(P, lane, o, outside, sem, res);
-}
-template <bool ATT, int N, int PREC, int SEMP = 0>
-__device__ __forceinline__ void tile_mlp(const FieldParams& P, int lane, const float (&feat)[N][8],
-                                         const float (&outside)[N], float* const (&sem)[N], TileOut (&res)[N]) {
-  f32x4 unused[N][2];
-  tile_mlp<ATT, N, PREC, SEMP, false>(P, lane, feat, outside, sem, res, unused);
 }
 
 // View-direction variant of the decoder (exact fp32 MFMA): layer 1 as above, layer 2 with 33 outputs
@@ -1085,10 +1206,9 @@ __device__ __forceinline__ void tile_mlp(const FieldParams& P, int lane, const f
 // through), layer 3 over K = those 48 accumulator rows - the accumulator layout of one layer is the B
 // operand of the next, as between layers 1 and 2.  xr[n][t]: rows 16t+4g..+3 of the padded ray feature
 // of tile n's point j.  P.lds holds the nfi_decoder_pack_viewdir image.
-template <bool ATT, int N, int SEMP = 0, bool NRM = false>
+template <int N, bool NRM = false>
 __device__ __forceinline__ void tile_mlp_vd(const FieldParams& P, int lane, const float (&feat)[N][8],
-                                            const f32x4 (&xr)[N][3], const float (&outside)[N], float* const (&sem)[N],
-                                            TileOut (&res)[N], f32x4 (&Gout)[N][2]) {
+                                            const f32x4 (&xr)[N][3], f32x4 (&o)[N], f32x4 (&Gout)[N][2]) {
   const int g = lane >> 4;
   const f32x4* ldsv = reinterpret_cast<const f32x4*>(P.lds);
   f32x4 acc1[N][4];
@@ -1147,7 +1267,7 @@ __device__ __forceinline__ void tile_mlp_vd(const FieldParams& P, int lane, cons
         o2[n][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, acc1[n][nt][3], o2[n][t], 0, 0, 0);
       }
     }
-  f32x4 o[N], oB[N];
+  f32x4 oB[N];
   const f32x4 b3 = ldsv[(kVdB3 >> 2) + g];
 #pragma unroll
   for (int n = 0; n < N; ++n) { o[n] = b3; oB[n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
@@ -1171,7 +1291,6 @@ __device__ __forceinline__ void tile_mlp_vd(const FieldParams& P, int lane, cons
   }
 #pragma unroll
   for (int n = 0; n < N; ++n) o[n] = o[n] + oB[n];
-  tile_epilogue<ATT, N, SEMP>(P, lane, o, outside, sem, res);
 }
 
 struct SampleOut {
@@ -1185,8 +1304,10 @@ struct SampleOut {
 // generator.py:633) and rgb is reported as 0 (its compositing weight is exactly 0).  Without SKIP
 // (the sampler closure) outside points get the border-clamped colour/distance the reference returns.
 // sem_base: null, or global pointer to this wave's [64][A] semantics rows (written for valid points); with SEMP > 0
-// the wave's LDS table [A][SEMP] at the column of this call's point 0 (tile_epilogue).
+// the wave's LDS table [A][SEMP] at the column of this call's point 0 (sample_epilogue / tile_epilogue).
 // stage: 16 x 36 floats of LDS owned by this wave (feature-tile transpose).
+// otab (OTAB): kOutTabFloats<ATT> floats of LDS owned by this wave, the decoder output table (park_tile_outputs); dead
+// between calls.  OTAB = false: no table (otab is not touched), the per-tile epilogue.
 // prof: null, or 4 cycle accumulators {unused (stays 0), tile set-up + load issue + wait + interpolation,
 // transpose + MLP + epilogue, tiles} filled with cycle-counter deltas (profiling builds only)
 // VD: view-direction decoder; xray = padded per-ray features [rays][kRayFeatPad], ray_idx = this lane's ray.
@@ -1197,10 +1318,10 @@ struct SampleOut {
 // second, cache-hot gather behind the decoder: 0.56 x the plain rate where this is 0.72 x - profiles/r6/
 // extra_maps_render_times.log.)  The positive factors common to the three axes (the plane mean's 1/3, the base-2 scalings)
 // drop out of the normalisation.  Border-clamped coordinates carry no gradient, like grid_sample's.
-template <int TEX, bool ATT, bool SKIP, int PREC = 0, bool VD = false, int SEMP = 0, bool NRM = false>
+template <int TEX, bool ATT, bool SKIP, int PREC, bool VD, int SEMP, bool NRM, bool OTAB>
 __device__ __forceinline__ SampleOut field_wave(const FieldParams& P, float scene_range, int lane, float px, float py,
                                                 float pz, bool valid, float* sem_base, bool* outside_flag,
-                                                float* stage, unsigned long long* prof = nullptr,
+                                                float* stage, float* otab, unsigned long long* prof = nullptr,
                                                 const float* xray = nullptr, int ray_idx = 0) {
   // reference: x / scene_range, mask = any(|x| > 1)   (true division, generator.py:604-607)
   float qx = px / scene_range, qy = py / scene_range, qz = pz / scene_range;
@@ -1228,6 +1349,7 @@ __device__ __forceinline__ SampleOut field_wave(const FieldParams& P, float scen
   so.sdf = 0.0f; so.sigma = 0.0f; so.r = 0.0f; so.g = 0.0f; so.b = 0.0f;
   so.nx = 0.0f; so.ny = 0.0f; so.nz = 0.0f;
   if (tm == 0) return so;
+  const uint32_t tm_live = tm;     // (the loops below consume tm)
   const int j = lane & 15, g = lane >> 4;
 
   // Two lane layouts are used per tile (16 points):
@@ -1241,12 +1363,13 @@ __device__ __forceinline__ SampleOut field_wave(const FieldParams& P, float scen
   // chunk q of L and channel group g of M hold the same channels, so the W1 operand image is
   // independent of this choice.
   const int lp = lane >> 2, lq = lane & 3;        // L layout
-  // gather + interpolation + L->M transpose of one tile; returns the tile's flags for this lane's point
+  // gather + interpolation + L->M transpose of one tile; returns the tile's flags for this lane's point (the per-tile
+  // epilogue's; with the output table `outside` and `valid` are the sample lane's own and nothing is fetched)
   auto gather_tile = [&](int t, float (&feat)[8]) -> int {
     const int srcL = 16 * t + lp, srcM = 16 * t + j;
     const float cfx = __shfl(fx, srcL, 64), cfy = __shfl(fy, srcL, 64), cfz = __shfl(fz, srcL, 64);
     const uint32_t cxi = (uint32_t)__shfl(xi, srcL, 64);
-    const int fcur = __shfl(flags, srcM, 64);
+    const int fcur = OTAB ? 0 : __shfl(flags, srcM, 64);
     float featL[8];
     TileTex<TEX> T;
     tile_issue<TEX>(P, lq, cxi, T);
@@ -1295,9 +1418,9 @@ __device__ __forceinline__ SampleOut field_wave(const FieldParams& P, float scen
     const float sx = __shfl(gx, 4 * j, 64), sy = __shfl(gy, 4 * j, 64), sz = __shfl(gz, 4 * j, 64);
     if (g == t) { so.nx = sx; so.ny = sy; so.nz = sz; }
   };
-#pragma unroll 1
-  while (tm != 0) {
-    if constexpr (NRM) {
+  if constexpr (NRM) {
+    static_assert(!OTAB, "the normal map's one-tile-per-turn schedule runs the per-tile epilogue");
+    {
       // ---- the normal map's own schedule: ONE tile per turn; the derivative features d feature / d (x, y, z) come out of
       // the tile's (only) gather, wait in registers while the decoder runs, and meet G = d sdf / d feature behind it - one turn
       // later, between the NEXT tile's load issue and its blend, where the gather's latency would otherwise be idle ----
@@ -1369,7 +1492,7 @@ __device__ __forceinline__ SampleOut field_wave(const FieldParams& P, float scen
         __builtin_amdgcn_s_setprio(0);
         const float outs1[1] = {(f1 & 1) ? 1.0f : 0.0f};
         float* const sems1[1] = {(sem_base && (f1 & 2)) ? sem_col(t) : nullptr};
-        TileOut to1[1];
+        f32x4 o1[1];
         f32x4 G1[1][2];
         if constexpr (VD) {
           static_assert(PREC == 0, "the view-direction decoder exists in exact fp32 only");
@@ -1377,17 +1500,23 @@ __device__ __forceinline__ SampleOut field_wave(const FieldParams& P, float scen
           f32x4 xr1[1][3];
 #pragma unroll
           for (int c3 = 0; c3 < 3; ++c3) xr1[0][c3] = *reinterpret_cast<const f32x4*>(xray + (size_t)r1 * kRayFeatPad + 16 * c3 + 4 * g);
-          tile_mlp_vd<ATT, 1, SEMP, true>(P, lane, feat1, xr1, outs1, sems1, to1, G1);
+          tile_mlp_vd<1, true>(P, lane, feat1, xr1, o1, G1);
         } else {
-          tile_mlp<ATT, 1, PREC, SEMP, true>(P, lane, feat1, outs1, sems1, to1, G1);
+          tile_mlp<1, PREC, true>(P, lane, feat1, o1, G1);
+        }
+        {
+          TileOut to1[1];
+          tile_epilogue<ATT, 1, SEMP>(P, lane, o1, outs1, sems1, to1);
+          if (g == t) { so.sdf = to1[0].sdf; so.sigma = to1[0].sigma; so.r = to1[0].r; so.g = to1[0].g; so.b = to1[0].b; }
         }
         Gp1[0] = G1[0][0]; Gp1[1] = G1[0][1];
         tprev = t;
-        if (g == t) { so.sdf = to1[0].sdf; so.sigma = to1[0].sigma; so.r = to1[0].r; so.g = to1[0].g; so.b = to1[0].b; }
       }
       if (tprev >= 0) normals_of_previous();
-      return so;
     }
+  }
+#pragma unroll 1
+  while (!NRM && tm != 0) {
     unsigned long long c0 = prof ? __builtin_readcyclecounter() : 0;
     const int ta = __builtin_ctz(tm);
     tm &= tm - 1;
@@ -1410,9 +1539,11 @@ __device__ __forceinline__ SampleOut field_wave(const FieldParams& P, float scen
     }
     unsigned long long c2 = prof ? __builtin_readcyclecounter() : 0;
     __builtin_amdgcn_s_setprio(0);
+    // (the per-tile epilogue's operands, where they have always been made: ahead of the decoder)
     const float outs[2] = {(fa & 1) ? 1.0f : 0.0f, (fb & 1) ? 1.0f : 0.0f};
-    float* const sems[2] = {(sem_base && (fa & 2)) ? sem_col(ta) : nullptr, (sem_base && pair && (fb & 2)) ? sem_col(tb) : nullptr};
-    TileOut to[2];
+    float* const sems[2] = {(!OTAB && sem_base && (fa & 2)) ? sem_col(ta) : nullptr,
+                            (!OTAB && sem_base && pair && (fb & 2)) ? sem_col(tb) : nullptr};
+    f32x4 o[2];              // the decoder's raw outputs: rows 4 g .. 4 g + 3 of point j of either tile
     f32x4 Gp[2][2];          // (only the normal map's schedule above asks the decoder for d distance / d feature)
     if constexpr (VD) {
       static_assert(PREC == 0, "the view-direction decoder exists in exact fp32 only");
@@ -1423,16 +1554,42 @@ __device__ __forceinline__ SampleOut field_wave(const FieldParams& P, float scen
         xr[0][t] = *reinterpret_cast<const f32x4*>(xray + (size_t)ra * kRayFeatPad + 16 * t + 4 * g);
         xr[1][t] = *reinterpret_cast<const f32x4*>(xray + (size_t)rb * kRayFeatPad + 16 * t + 4 * g);
       }
-      tile_mlp_vd<ATT, 2, SEMP, false>(P, lane, feat, xr, outs, sems, to, Gp);
+      tile_mlp_vd<2, false>(P, lane, feat, xr, o, Gp);
     } else {
-      tile_mlp<ATT, 2, PREC, SEMP, false>(P, lane, feat, outs, sems, to, Gp);
+      tile_mlp<2, PREC, false>(P, lane, feat, o, Gp);
     }
-    if (g == ta) { so.sdf = to[0].sdf; so.sigma = to[0].sigma; so.r = to[0].r; so.g = to[0].g; so.b = to[0].b; }
-    if (pair && g == tb) { so.sdf = to[1].sdf; so.sigma = to[1].sigma; so.r = to[1].r; so.g = to[1].g; so.b = to[1].b; }
+    if constexpr (OTAB) {
+      park_tile_outputs<ATT>(otab, lane, ta, o[0]);
+      if (pair) park_tile_outputs<ATT>(otab, lane, tb, o[1]);
+      if (prof) asm volatile("" :: "v"(o[0].x), "v"(o[1].x));
+    } else {
+      // the per-tile epilogue in the MFMA layout: every kernel but the plain render kernels with attention (see there)
+      TileOut to[2];
+      tile_epilogue<ATT, 2, SEMP>(P, lane, o, outs, sems, to);
+      if (g == ta) { so.sdf = to[0].sdf; so.sigma = to[0].sigma; so.r = to[0].r; so.g = to[0].g; so.b = to[0].b; }
+      if (pair && g == tb) { so.sdf = to[1].sdf; so.sigma = to[1].sigma; so.r = to[1].r; so.g = to[1].g; so.b = to[1].b; }
+      if (prof) asm volatile("" :: "v"(so.sigma), "v"(so.r));
+    }
     if (prof) {
-      asm volatile("" :: "v"(so.sigma), "v"(so.r));
       unsigned long long c3 = __builtin_readcyclecounter();
       prof[1] += c2 - c0; prof[2] += c3 - c2; prof[3] += pair ? 2 : 1;
+    }
+  }
+  if constexpr (OTAB) {
+    // ---- one epilogue for the call's 64 samples, lane = sample ----
+    unsigned long long c4 = prof ? __builtin_readcyclecounter() : 0;
+    wave_lds_fence();
+    const bool live = valid && ((tm_live >> (lane >> 4)) & 1u);
+    float* sem_mine = nullptr;
+    if (sem_base) {
+      if constexpr (SEMP < 0) sem_mine = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(sem_base) + lane);
+      else sem_mine = sem_base + (size_t)lane * sem_pt;
+    }
+    sample_epilogue<ATT, SEMP>(P, lane, otab, out, live, sem_mine, so.sdf, so.sigma, so.r, so.g, so.b);
+    wave_lds_fence();      // the next call's tiles write the slots these reads are from
+    if (prof) {
+      asm volatile("" :: "v"(so.sigma), "v"(so.r));
+      prof[2] += __builtin_readcyclecounter() - c4;
     }
   }
   return so;

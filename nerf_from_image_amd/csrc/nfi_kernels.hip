@@ -514,6 +514,7 @@ struct FieldKernelParams {
 // PREC: 0 = exact fp32 MFMA (the sampler closure's default: bitwise an fmaf chain), 1 = split-fp16 operands as in the
 // fused renderer (render()'s differentiable path: the same decoder arithmetic in both of its paths, and what the
 // backward kernel recomputes)
+static_assert(kOutLastRow == NFI_MAX_ATTENTION, "sample_epilogue reads rows 1 .. NFI_MAX_ATTENTION of the output table");
 template <int TEX, bool ATT, bool VD = false, int PREC = 0>
 __global__ __launch_bounds__(256) void field_query_kernel(FieldKernelParams k) {
   constexpr int kImg = VD ? kVdImageFloats : kLdsImageFloats;
@@ -542,8 +543,10 @@ __global__ __launch_bounds__(256) void field_query_kernel(FieldKernelParams k) {
     if (valid) { px = k.points[gi * 3]; py = k.points[gi * 3 + 1]; pz = k.points[gi * 3 + 2]; }
     bool out;
     float* sem = k.sem ? k.sem + ((size_t)scene * k.P + chunk * 64) * k.A : nullptr;
-    SampleOut so = field_wave<TEX, ATT, false, PREC, VD>(P, k.scene_range, lane, px, py, pz, valid, sem, &out, stages[wave],
-                                                      nullptr, xray_scene, VD && valid ? (int)(p / k.spr) : 0);
+    // (the per-tile epilogue: the sample-layout one of the plain render kernels has not been timed here)
+    SampleOut so = field_wave<TEX, ATT, false, PREC, VD, 0, false, false>(P, k.scene_range, lane, px, py, pz, valid, sem, &out,
+                                                                          stages[wave], nullptr, nullptr, xray_scene,
+                                                                          VD && valid ? (int)(p / k.spr) : 0);
     if (valid) {
       k.sigma[gi] = so.sigma;
       k.rgb[gi * 3] = so.r; k.rgb[gi * 3 + 1] = so.g; k.rgb[gi * 3 + 2] = so.b;
@@ -1695,6 +1698,13 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
   __shared__ __attribute__((aligned(16))) float lds[kImg];
   __shared__ __attribute__((aligned(16))) float vfs[4][64];
   __shared__ WaveSlab slabs[4];
+  // Decoder output tables (field_wave): the slab's rows are free during the field passes, but the 464 floats beside the
+  // stage tile do not hold one - static LDS, 30 272 + 17 408 B: three workgroups per CU still fit in 160 KB.  The PLAIN
+  // kernels with attention only: they are the ones timed with it (profiles/r13); every other form keeps the per-tile
+  // epilogue - and the normal map's kernel (47 680 + 29 568 of semantics tables + 8 464 of normal operands = 85 712 B) and
+  // the view-direction decoder's map kernels (59 136 + 29 568 B) would lose their second workgroup per CU with a table.
+  constexpr bool OTAB = MODE == kRenderPlain && ATT && !VD;
+  __shared__ __attribute__((aligned(16))) float otabs[4][OTAB ? kOutTabFloats<ATT> : 4];
   if constexpr (NRM) stage_normal_operands(nfi_dyn_lds, k.image, VD ? kVdW1F : kW1F, VD ? kVdW2 : kW2F);
   ClockProbe clock;
   clock.start(k);
@@ -1703,6 +1713,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
   const int wave = threadIdx.x >> 6;
   WaveSlab& slab = slabs[wave];
   float* vf = vfs[wave];
+  float* otab = otabs[wave];
   const int S = k.S;
   const bool valid = lane < S;
   const float fill_near = ordered_key_inv(~k.reduce[0]), fill_far = ordered_key_inv(k.reduce[1]);
@@ -1781,8 +1792,8 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
     float ncx = 0.0f, ncy = 0.0f, ncz = 0.0f, nfx = 0.0f, nfy = 0.0f, nfz = 0.0f;     // NRM: the samples' unit normals
     unsigned long long t1 = PROF ? __builtin_readcyclecounter() : 0;
     {
-      SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM>(P, k.scene_range, lane, ox + dx * tc, oy + dy * tc, oz + dz * tc,
-                                                                    valid, semT, nullptr, &slab.srt[0][0], PROF ? pc : nullptr,
+      SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM, OTAB>(P, k.scene_range, lane, ox + dx * tc, oy + dy * tc, oz + dz * tc,
+                                                                    valid, semT, nullptr, &slab.srt[0][0], otab, PROF ? pc : nullptr,
                                                                     k.xray, (int)ray);
       c.t = tc; c.sigma = q.sigma; c.r = q.r; c.g = q.g; c.b = q.b;
       if constexpr (NRM) { ncx = q.nx; ncy = q.ny; ncz = q.nz; }
@@ -1813,13 +1824,14 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
         tf = slab.cdf[lane];
         wave_lds_fence();
         const bool vl = lane < nl;
-        SampleOut q = field_wave<TEX, ATT, true, PREC, VD>(P, k.scene_range, lane, ox + dx * tf, oy + dy * tf, oz + dz * tf, vl,
-                                                           nullptr, nullptr, &slab.srt[0][0], nullptr, k.xray, (int)ray);
+        SampleOut q = field_wave<TEX, ATT, true, PREC, VD, 0, false, OTAB>(P, k.scene_range, lane, ox + dx * tf, oy + dy * tf,
+                                                                           oz + dz * tf, vl, nullptr, nullptr, &slab.srt[0][0],
+                                                                           otab, nullptr, k.xray, (int)ray);
         f.t = tf; f.sigma = vl ? q.sigma : 0.0f; f.r = vl ? q.r : 0.0f; f.g = vl ? q.g : 0.0f; f.b = vl ? q.b : 0.0f;
       } else {
-        SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM>(P, k.scene_range, lane, ox + dx * tf, oy + dy * tf, oz + dz * tf,
+        SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM, OTAB>(P, k.scene_range, lane, ox + dx * tf, oy + dy * tf, oz + dz * tf,
                                                                       valid, semT ? semT + 64 : nullptr, nullptr, &slab.srt[0][0],
-                                                                      PROF ? pc : nullptr, k.xray, (int)ray);
+                                                                      otab, PROF ? pc : nullptr, k.xray, (int)ray);
         f.t = tf; f.sigma = q.sigma; f.r = q.r; f.g = q.g; f.b = q.b;
         if constexpr (NRM) { nfx = q.nx; nfy = q.ny; nfz = q.nz; }
       }
@@ -1999,9 +2011,10 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_wide_kernel(RenderKernelP
       for (int j = 0; j < 4; ++j) nrm[j][0] = nrm[j][1] = nrm[j][2] = 0.0f;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM>(P, k.scene_range, lane, ox + dx * tc[j], oy + dy * tc[j],
-                                                                      oz + dz * tc[j], val[j], sem_col(j * 64), nullptr,
-                                                                      stage, nullptr, k.xray, (int)ray);
+        // (the per-tile epilogue, here and in the fine pass: the sample-layout one has not been timed in this kernel)
+        SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM, false>(P, k.scene_range, lane, ox + dx * tc[j], oy + dy * tc[j],
+                                                                             oz + dz * tc[j], val[j], sem_col(j * 64), nullptr,
+                                                                             stage, nullptr, nullptr, k.xray, (int)ray);
         sc[j] = q.sigma; rc[j] = q.r; gc[j] = q.g; bc[j] = q.b;
         if constexpr (NRM) { nrm[j][0] = q.nx; nrm[j][1] = q.ny; nrm[j][2] = q.nz; }
       }
@@ -2051,9 +2064,9 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_wide_kernel(RenderKernelP
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM>(P, k.scene_range, lane, ox + dx * tf[j], oy + dy * tf[j],
-                                                                        oz + dz * tf[j], vfine[j], sem_col(128 + j * 64),
-                                                                        nullptr, stage, nullptr, k.xray, (int)ray);
+          SampleOut q = field_wave<TEX, ATT, true, PREC, VD, SEMP, NRM, false>(P, k.scene_range, lane, ox + dx * tf[j], oy + dy * tf[j],
+                                                                               oz + dz * tf[j], vfine[j], sem_col(128 + j * 64),
+                                                                               nullptr, stage, nullptr, nullptr, k.xray, (int)ray);
           if (TERM && !vfine[j]) { q.sigma = 0.0f; q.r = 0.0f; q.g = 0.0f; q.b = 0.0f; }
           if constexpr (NRM) { nrm[2 + j][0] = q.nx; nrm[2 + j][1] = q.ny; nrm[2 + j][2] = q.nz; }
           dep[2 + j] = tf[j]; sig[2 + j] = q.sigma; cr[2 + j] = q.r; cg[2 + j] = q.g; cb[2 + j] = q.b;
@@ -2209,8 +2222,11 @@ __global__ __launch_bounds__(256, NFI_RENDER_OCC) void render_fwd_long_kernel(Re
         const bool val = e < S;
         const float nz = (k.noise_c && val) ? k.noise_c[rs + e] : 0.0f;
         const float t = val ? stratified_depth(near, far, e, S, nz, k.noise_c != nullptr) : 0.0f;
-        SampleOut q = field_wave<TEX, ATT, true, PREC, VD>(P, k.scene_range, lane, ox + dx * t, oy + dy * t, oz + dz * t, val,
-                                                           nullptr, nullptr, slab.stage, nullptr, k.xray, (int)ray);
+        // (the per-tile epilogue: 63.8 KB of per-sample rows, all live while the field is marched - 75.3 KB with the
+        //  view-direction image - leave no room for an output table beside two workgroups per CU)
+        SampleOut q = field_wave<TEX, ATT, true, PREC, VD, 0, false, false>(P, k.scene_range, lane, ox + dx * t, oy + dy * t,
+                                                                            oz + dz * t, val, nullptr, nullptr, slab.stage,
+                                                                            nullptr, nullptr, k.xray, (int)ray);
         if (val) {
           slab.srt[0][e] = t; slab.srt[1][e] = q.sigma; slab.srt[2][e] = q.r; slab.srt[3][e] = q.g; slab.srt[4][e] = q.b;
           store_sample_tap(k.t_coarse, k.sigma_coarse, k.rgb_coarse, ts + e, t, q.sigma, q.r, q.g, q.b);
