@@ -310,6 +310,10 @@ int nfi_points_bwd(const float* g_points, const float* depth, int64_t n_rays, in
  * g_cam2world [B,4,4] (zeroed inside), g_focal [B] or NULL.  a->ray_origins/ray_directions are ignored. */
 int nfi_raygen_bwd(const nfi_raygen_args* a, const float* g_ray_origins, const float* g_ray_directions,
                    float* g_cam2world, float* g_focal, nfi_stream_t stream);
+/* The same gradients, bit-identical from launch to launch: one block per image keeps the 17 sums in float64 over the whole
+ * image, rounds once and stores (no atomic, no memset, no workspace; g_cam2world / g_focal are WRITTEN). */
+int nfi_raygen_bwd_ordered(const nfi_raygen_args* a, const float* g_ray_origins, const float* g_ray_directions,
+                           float* g_cam2world, float* g_focal, nfi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Field query backward: autograd of the sampler closure (models/generator.py:587-681), i.e.
@@ -323,7 +327,7 @@ int nfi_raygen_bwd(const nfi_raygen_args* a, const float* g_ray_origins, const f
  * ------------------------------------------------------------------------------------------ */
 typedef struct nfi_field_bwd_args {
   int n_scenes;
-  int64_t points_per_scene;          /* <= 2^30 (<= 2^25 with scatter_mode 1): the kernels address a scene's points by 32-bit offsets */
+  int64_t points_per_scene;          /* <= 2^30 (<= 2^25 with scatter_mode 1 or 2): the kernels address a scene's points by 32-bit offsets */
   const float* points;
   const void* texels; int plane_res; int texel_dtype;   /* any storage type; g_texels is fp32 (view-direction decoder: fp32 texels only) */
   const float* decoder_image;                            /* forward operand image */
@@ -350,7 +354,17 @@ typedef struct nfi_field_bwd_args {
    * 1: binned - the kernel writes the per-point feature gradient (128 B) to the workspace, the points are counting-
    * sorted by texel cell per plane (by 16x16-texel tile through global memory, by cell inside LDS), and the sorted
    * entries are reduced in registers with one set of line-coalesced atomics per run of a cell; needs
-   * nfi_field_bwd_workspace_bytes(a) of workspace (177 B per point).  Same result up to fp32 summation order. */
+   * nfi_field_bwd_workspace_bytes(a) of workspace (177 B per point).  Same result up to fp32 summation order.
+   * 2: ordered - EVERY output of the call is bit-identical from launch to launch for identical arguments on the same
+   * device and build, with the same rays_per_row (the grid, and with it the order of the parameter sums, follows the
+   * arguments).  g_texels: the rows of mode 1, one 64-bit key (cell, point) per point and plane, a stable radix sort by
+   * cell, and one half-wave per texel that adds the points of its up to four cells in ascending (cell, point) order and
+   * is the texel's only writer; the decoder, attention, beta and alpha gradients: one zeroed workspace slot per wave,
+   * summed in slot order by a finish kernel.  No float atomic meets another.  Same ACCUMULATED contract, same 2^25 limit;
+   * all scratch from nfi_field_bwd_workspace_bytes(a) of workspace (177 B per point + 13 KB per wave of the grid), no
+   * allocation, no synchronisation.  Plain decoder only: an error with ray_features (the view-direction decoder's
+   * g_ray_features are atomics over up to 8 chunks per ray) and with points_only (nothing to order).  Slower than mode 1:
+   * see DESIGN.md section 6.  Any other value is an error. */
   int scatter_mode;
   int texel_layout;              /* of texels AND g_texels */
   /* Order hint (0: none): the points are [rays][samples_per_ray] with the rays in row-major order of an image

@@ -18,7 +18,8 @@
 // before they reach the atomic units.  The coordinate gradients J^T gf stay here: their second gather hits lines this
 // wave has just loaded - a separate gather pass was measured at 1.0 ms per 4.2 M points against 0.25 ms in place.
 // The upstream gradients are loaded per tile in the MFMA layout (staging a chunk's worth through lane permutes or LDS
-// was measured: no gain).
+// was measured: no gain).  scatter_mode 2 ("ordered mode" below) replaces every one of these float atomics by a sum in a
+// fixed order: rows gathered per texel from sorted keys, one workspace slot per wave for the parameter gradients.
 
 constexpr int kBwdW2T = 0;                       // fp16 hi/lo: [4 m-tiles][2][64 lanes][4 dwords] (K slots 4..7 are zero)
 constexpr int kBwdW1T = kBwdW2T + 4 * 2 * 64 * 4;    // fp16 hi/lo: [2 m-tiles][2 k-chunks][2][64 lanes][4 dwords]
@@ -121,6 +122,9 @@ struct FieldBwdParams {
   // wide; the kernel then walks them in tside x tside-pixel tiles, every XCD (= blockIdx.x % 8) one tile at a time
   int n_tiles, tiles_x, tside, tw, cpr;
   FastDiv div_cpr, div_tside, div_tiles_x;      // the tile walk's three divisions (wave-uniform operands: scalar-ALU work)
+  // ordered mode (scatter_mode 2): the parameter-gradient pointers above are slot 0 of per-wave slots in the workspace,
+  // slot_stride floats apart (0: the caller's buffers, shared by every wave; a slot holds its wave's scene's rows of g_att only)
+  uint32_t slot_stride;
 };
 
 // ================================================================================================
@@ -857,7 +861,8 @@ struct PlainDecoderBwd : DecoderBwdCommon {
   }
 
   // flush: g_w1, g_w2, g_b1, g_b2 (the accumulators are in units of 1 / their sticky scale)
-  __device__ __forceinline__ void flush(const FieldBwdParams& k, const BwdLane& L) {
+  // (slot: this wave's offset in floats into the per-wave slots of the ordered mode; 0 otherwise)
+  __device__ __forceinline__ void flush(const FieldBwdParams& k, const BwdLane& L, uint32_t slot) {
     const int lane = L.lane, j = L.j, g = L.g;
     const int n_out = k.A > 0 ? 1 + k.A : 4;
     const float g1 = 0.17677669529663687f, g2 = 0.125f;
@@ -868,19 +873,19 @@ struct PlainDecoderBwd : DecoderBwdCommon {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         // dW1[hid = 16nt+4g+r][ch = 16*n2 + j] ; feat was the SUM of three planes -> /3
-        atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * kC + j], dW1[nt][0][r] * (g1 / 3.0f) * un_gh);
-        atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * kC + 16 + j], dW1[nt][1][r] * (g1 / 3.0f) * un_gh);
+        atomicAdd(&k.g_w1[slot + (16 * nt + 4 * g + r) * kC + j], dW1[nt][0][r] * (g1 / 3.0f) * un_gh);
+        atomicAdd(&k.g_w1[slot + (16 * nt + 4 * g + r) * kC + 16 + j], dW1[nt][1][r] * (g1 / 3.0f) * un_gh);
         // dW2[row = 4g+r][hid = 16nt + j] ; s = sp2 * ln2
         const int row = 4 * g + r;
-        if (row < n_out) atomicAdd(&k.g_w2[row * kHidden + 16 * nt + j], dW2[nt][r] * (g2 * kLn2) * un_go);
+        if (row < n_out) atomicAdd(&k.g_w2[slot + row * kHidden + 16 * nt + j], dW2[nt][r] * (g2 * kLn2) * un_go);
       }
     }
-    atomicAdd(&k.g_b1[lane], db1p);                                   // one hidden unit per lane (see db1p above)
+    atomicAdd(&k.g_b1[slot + lane], db1p);                                   // one hidden unit per lane (see db1p above)
     if (j == 3) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = 4 * g + r;                                    // column 3 of dVacc: the bias gradient of the row
-        if (row < n_out) atomicAdd(&k.g_b2[row], dVacc[r] * un_go);
+        if (row < n_out) atomicAdd(&k.g_b2[slot + row], dVacc[r] * un_go);
       }
     }
   }
@@ -1102,8 +1107,8 @@ struct ViewdirDecoderBwd : DecoderBwdCommon {
     return out;
   }
 
-  // flush: g_w1, g_w2 (33 rows), g_b1, g_b2 (33 rows), g_w3, g_b3
-  __device__ __forceinline__ void flush(const FieldBwdParams& k, const BwdLane& L) {
+  // flush: g_w1, g_w2 (33 rows), g_b1, g_b2 (33 rows), g_w3, g_b3 (no ordered mode for this decoder: no slots)
+  __device__ __forceinline__ void flush(const FieldBwdParams& k, const BwdLane& L, uint32_t) {
     const int lane = L.lane, j = L.j, g = L.g;
     const int n3 = k.A > 0 ? k.A : 3;
     const float g1 = 0.17677669529663687f, g2 = 0.125f;
@@ -1163,6 +1168,11 @@ __global__ __launch_bounds__(256, FieldDecoderBwd<VD>::kWorkgroupsPerCU) void fi
   const BwdScene S = enter_bwd_scene(k, scene);
   const float alpha_v = k.use_sdf ? k.alpha[0] : 1.0f;
   float d_beta = 0.0f, d_alpha = 0.0f;
+  // ordered mode: every wave adds into its own zeroed slot (exact), param_finish_kernel sums the slots in index order
+  // (worked out here, as ONE scalar: at the flush it would keep the block's coordinates alive through the whole walk)
+  uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(((blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * k.slot_stride));
+  uint32_t att_at = k.slot_stride ? slot : (uint32_t)(scene * k.A * 3);      // this wave's rows of g_att
+  asm volatile("" : "+s"(slot), "+s"(att_at));     // (pinned here: sunk to the flush they cost five scalar registers, not two)
 
   ChunkWalk walk(k, wave);
   while (true) {
@@ -1198,18 +1208,18 @@ __global__ __launch_bounds__(256, FieldDecoderBwd<VD>::kWorkgroupsPerCU) void fi
 
   // ---------------- flush the per-wave accumulators ----------------
   if (k.points_only) return;
-  dec.flush(k, L);
+  dec.flush(k, L, slot);
   if constexpr (ATT) {
     // columns j < 3 of dVacc hold dV[row][c = j]
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 4 * L.g + r;
-      if (L.j < 3 && row >= 1 && row <= k.A) atomicAdd(&k.g_att[((size_t)scene * k.A + (row - 1)) * 3 + L.j], dec.dVacc[r]);
+      if (L.j < 3 && row >= 1 && row <= k.A) atomicAdd(&k.g_att[att_at + (row - 1) * 3 + L.j], dec.dVacc[r]);
     }
   }
   if (k.use_sdf) {
     d_beta = wave_sum(d_beta); d_alpha = wave_sum(d_alpha);
-    if (lane == 0) { atomicAdd(k.g_beta, d_beta); atomicAdd(k.g_alpha, d_alpha); }
+    if (lane == 0) { atomicAdd(k.g_beta + slot, d_beta); atomicAdd(k.g_alpha + slot, d_alpha); }
   }
 }
 
@@ -1533,6 +1543,222 @@ __global__ __launch_bounds__(kBinThreads) void bin_reduce_kernel(BinParams k) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// ordered mode (scatter_mode 2): every gradient bit-identical from launch to launch.  No float atomic meets another
+// and no sum depends on which wave came first:
+//   g_texels : the backward kernel writes the rows and flags of the binned scatter; ord_keys makes one 64-bit key
+//              (cell ib * res + ia << 32 | point) per point and plane - unique, in point order - and a STABLE radix sort
+//              by cell (8-bit digits: hist / scan / scatter per pass, integer atomics only) turns each (scene, plane)
+//              segment into runs of a cell in ascending point order; ord_gather: one half-wave per texel and plane,
+//              lane = channel, walks the up to four cells that touch the texel in ascending cell order, a cell's run in
+//              point order in blocks of 32 entries (weights recomputed with bin_entry's arithmetic, one fma chain per
+//              block, the blocks' sums added in index order), then one load-add-store: each texel has one writer;
+//   decoder, attention, beta, alpha: a zeroed slot per wave (FieldBwdParams::slot_stride), summed by param_finish_kernel
+//              in slot order (16 contiguous parts per element, combined in part order).
+// The statement holds for a fixed grid: the slot a chunk's sums land in follows the static chunk walk.
+// ------------------------------------------------------------------------------------------------
+constexpr int kOrdTile = 2048;             // keys per sort block: one wave, 32 steps of 64 (the order inside a block is the step order)
+constexpr int kOrdDigits = 256;
+// a wave's slot (floats): g_w1 [64][32], g_b1 [64], g_w2 [<= 16][64], g_b2 [<= 16], the scene's g_att [<= 15][3], beta, alpha;
+// every region starts at a multiple of 16 (param_finish_kernel's blocks take 16 consecutive offsets)
+constexpr int kSlotW1 = 0, kSlotB1 = kSlotW1 + kHidden * kC, kSlotW2 = kSlotB1 + kHidden, kSlotB2 = kSlotW2 + 16 * kHidden;
+constexpr int kSlotAtt = kSlotB2 + 16, kSlotBeta = kSlotAtt + 48, kSlotAlpha = kSlotBeta + 1, kSlotFloats = kSlotBeta + 16;
+static_assert(kSlotB1 % 16 == 0 && kSlotW2 % 16 == 0 && kSlotB2 % 16 == 0 && kSlotAtt % 16 == 0 && kSlotBeta % 16 == 0,
+              "ordered mode: slot regions in units of 16 floats");
+
+struct OrdParams {
+  const float* points; int64_t P; int n_scenes; int res; float scene_range;
+  const uint8_t* flag; const float* gf;
+  uint64_t* keys_in; uint64_t* keys_out;       // [scenes * 3][P]: a pass reads one and writes the other
+  uint32_t* hist; int nblk;                    // [scenes * 3][256 digits][nblk sort blocks]
+  int shift;                                   // the pass's digit: key bits [32 + shift, 32 + shift + 8)
+  float* g_texels; int layout;
+};
+
+// grid (ceil(P / 256), scenes): thread = point
+__global__ __launch_bounds__(256) void ord_keys_kernel(OrdParams k) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= k.P) return;
+  const int scene = blockIdx.y;
+  const float* pt = k.points + ((size_t)scene * k.P + p) * 3;
+  int c0[3];
+  float f[3];
+  const float rm1 = (float)(k.res - 1);
+#pragma unroll
+  for (int ax = 0; ax < 3; ++ax) {
+    plane_coord(pt[ax] / k.scene_range, rm1, k.res, c0[ax], f[ax]);
+    c0[ax] = min(max(c0[ax], 0), max(k.res - 2, 0));
+  }
+#pragma unroll
+  for (int pl = 0; pl < 3; ++pl) {
+    const int ia = c0[(pl == 2) ? 1 : 0], ib = c0[(pl == 0) ? 1 : 2];      // plane 0: (x,y)  1: (x,z)  2: (y,z), as bin_entry
+    k.keys_in[(size_t)(scene * 3 + pl) * k.P + p] = ((uint64_t)(uint32_t)(ib * k.res + ia) << 32) | (uint64_t)p;
+  }
+}
+
+// grid (nblk, scenes * 3), 64 threads: digit counts of the block's kOrdTile keys
+__global__ __launch_bounds__(64) void ord_hist_kernel(OrdParams k) {
+  __shared__ uint32_t h[kOrdDigits];
+  const int lane = threadIdx.x, seg = blockIdx.y;
+  for (int d = lane; d < kOrdDigits; d += 64) h[d] = 0;
+  __syncthreads();
+  const uint64_t* keys = k.keys_in + (size_t)seg * k.P;
+  for (int step = 0; step < kOrdTile / 64; ++step) {
+    const int64_t i = (int64_t)blockIdx.x * kOrdTile + step * 64 + lane;
+    if (i < k.P) atomicAdd(&h[(uint32_t)(keys[i] >> (32 + k.shift)) & 255u], 1u);
+  }
+  __syncthreads();
+  for (int d = lane; d < kOrdDigits; d += 64) k.hist[((size_t)seg * kOrdDigits + d) * k.nblk + blockIdx.x] = h[d];
+}
+
+// grid (scenes * 3), 256 threads: exclusive scan of the segment's counts in (digit, block) order; thread = digit
+__global__ __launch_bounds__(256) void ord_scan_kernel(OrdParams k) {
+  __shared__ uint32_t tot[kOrdDigits];
+  uint32_t* row = k.hist + ((size_t)blockIdx.x * kOrdDigits + threadIdx.x) * k.nblk;
+  uint32_t sum = 0;
+  for (int b = 0; b < k.nblk; ++b) sum += row[b];
+  tot[threadIdx.x] = sum;
+  __syncthreads();
+  uint32_t at = 0;
+  for (int d = 0; d < (int)threadIdx.x; ++d) at += tot[d];
+  for (int b = 0; b < k.nblk; ++b) { const uint32_t c = row[b]; row[b] = at; at += c; }
+}
+
+// grid (nblk, scenes * 3), 64 threads: stable scatter - the block's keys in index order, 64 at a time; inside a step a key
+// goes behind the keys of the same digit in lower lanes
+__global__ __launch_bounds__(64) void ord_scatter_kernel(OrdParams k) {
+  __shared__ uint32_t off[kOrdDigits];
+  const int lane = threadIdx.x, seg = blockIdx.y;
+  for (int d = lane; d < kOrdDigits; d += 64) off[d] = k.hist[((size_t)seg * kOrdDigits + d) * k.nblk + blockIdx.x];
+  __syncthreads();
+  const uint64_t* keys = k.keys_in + (size_t)seg * k.P;
+  uint64_t* dst = k.keys_out + (size_t)seg * k.P;
+  for (int step = 0; step < kOrdTile / 64; ++step) {
+    const int64_t i = (int64_t)blockIdx.x * kOrdTile + step * 64 + lane;
+    const bool valid = i < k.P;
+    const uint64_t key = valid ? keys[i] : 0ull;
+    const uint32_t d = (uint32_t)(key >> (32 + k.shift)) & 255u;
+    uint64_t same = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const bool bit = (d >> b) & 1u;
+      const uint64_t bal = __ballot(valid && bit);
+      same &= bit ? bal : ~bal;
+    }
+    const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull)), cnt = (uint32_t)__popcll(same);
+    const uint32_t base = valid ? off[d] : 0u;
+    __syncthreads();
+    if (valid && rank + 1 == cnt) off[d] = base + cnt;       // the digit's last lane of the step
+    __syncthreads();
+    if (valid && (int64_t)base + rank < k.P) dst[base + rank] = key;
+  }
+}
+
+__device__ __forceinline__ int64_t ord_lower_bound(const uint64_t* keys, int64_t n, uint64_t v) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// grid (ceil(scenes * 3 * res^2 / 8)), 256 threads: one half-wave per texel and plane, lane = channel (keys_in: the sorted keys)
+__global__ __launch_bounds__(256) void ord_gather_kernel(OrdParams k) {
+  const int l32 = threadIdx.x & 31;
+  const int64_t h = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
+  const int rr = k.res * k.res;
+  if (h >= (int64_t)k.n_scenes * 3 * rr) return;
+  const int seg = (int)(h / rr), tex = (int)(h - (int64_t)seg * rr);
+  const int scene = seg / 3, pl = seg - scene * 3;
+  const int b = tex / k.res, a = tex - b * k.res;
+  const int ax_a = (pl == 2) ? 1 : 0, ax_b = (pl == 0) ? 1 : 2;
+  const uint64_t* keys = k.keys_in + (size_t)seg * k.P;
+  const float* pts = k.points + (size_t)scene * k.P * 3;
+  const uint8_t* flag = k.flag + (size_t)scene * k.P;
+  const float* gf = k.gf + (size_t)scene * k.P * kC;
+  const float rm1 = (float)(k.res - 1);
+  float total = 0.0f;
+  bool any = false;
+#pragma unroll 1
+  for (int c = 0; c < 4; ++c) {                       // cells (a-1,b-1), (a,b-1), (a-1,b), (a,b): ascending cell index
+    const int ia = a - 1 + (c & 1), ib = b - 1 + (c >> 1);
+    if (ia < 0 || ib < 0 || ia > k.res - 2 || ib > k.res - 2) continue;
+    const bool right = !(c & 1), upper = !(c >> 1);   // which corner of the cell this texel is
+    const uint32_t cell = (uint32_t)(ib * k.res + ia);
+    const int64_t lo = ord_lower_bound(keys, k.P, (uint64_t)cell << 32);
+    const int64_t hi = ord_lower_bound(keys, k.P, (uint64_t)(cell + 1u) << 32);
+#pragma unroll 1
+    for (int64_t base = lo; base < hi; base += 32) {
+      const int64_t i = base + l32;
+      uint32_t pt = 0u;
+      float w = 0.0f;
+      if (i < hi) {
+        pt = (uint32_t)keys[i];
+        if ((int64_t)pt < k.P && flag[pt]) {
+          int i0;
+          float fa, fb;
+          plane_coord(pts[(size_t)pt * 3 + ax_a] / k.scene_range, rm1, k.res, i0, fa);
+          plane_coord(pts[(size_t)pt * 3 + ax_b] / k.scene_range, rm1, k.res, i0, fb);
+          w = (right ? fa : 1.0f - fa) * (upper ? fb : 1.0f - fb);
+        }
+      }
+      const int n = (int)min((int64_t)32, hi - base);
+      float part = 0.0f;
+#pragma unroll 4
+      for (int e = 0; e < n; ++e) {
+        const float we = __shfl(w, e, 32);
+        const uint32_t pe = (uint32_t)__shfl((int)pt, e, 32);
+        if (we != 0.0f) { part = fmaf(we, gf[(size_t)pe * kC + l32], part); any = true; }
+      }
+      total += part;
+    }
+  }
+  if (!any) return;
+  const size_t g_pix = k.layout ? 3 * kC : kC, g_plane = k.layout ? (size_t)kC : (size_t)rr * kC;
+  float* dst = k.g_texels + (size_t)scene * 3 * rr * kC + (size_t)pl * g_plane + (size_t)tex * g_pix + l32;
+  *dst += total;
+}
+
+struct FinishParams {
+  const float* slots; int slots_per_scene, n_scenes, A, n_out, use_sdf;
+  float *g_w1, *g_b1, *g_w2, *g_b2, *g_att, *g_beta, *g_alpha;
+};
+
+// grid (kSlotFloats / 16), 256 threads = 16 slot offsets x 16 parts: a part sums a contiguous range of slots in index
+// order, part 0 adds the 16 partial sums in part order to the caller's buffer
+__global__ __launch_bounds__(256) void param_finish_kernel(FinishParams k) {
+  __shared__ float partial[16][16];
+  const int e = threadIdx.x & 15, part = threadIdx.x >> 4;
+  const int o = blockIdx.x * 16 + e;
+  auto sum_slots = [&](int first, int n) -> float {
+    const int s0 = first + (int)(((int64_t)n * part) / 16), s1 = first + (int)(((int64_t)n * (part + 1)) / 16);
+    float acc = 0.0f;
+    for (int s = s0; s < s1; ++s) acc += k.slots[(size_t)s * kSlotFloats + o];
+    __syncthreads();
+    partial[part][e] = acc;
+    __syncthreads();
+    float t = 0.0f;
+    for (int q = 0; q < 16; ++q) t += partial[q][e];
+    return t;
+  };
+  if (o >= kSlotAtt && o < kSlotBeta) {               // (block-uniform: the regions are multiples of 16)
+    for (int sc = 0; sc < k.n_scenes; ++sc) {
+      const float t = sum_slots(sc * k.slots_per_scene, k.slots_per_scene);
+      if (part == 0 && o - kSlotAtt < k.A * 3) k.g_att[(size_t)sc * k.A * 3 + (o - kSlotAtt)] += t;
+    }
+    return;
+  }
+  const float t = sum_slots(0, k.n_scenes * k.slots_per_scene);
+  if (part != 0) return;
+  if (o < kSlotB1) k.g_w1[o] += t;
+  else if (o < kSlotW2) k.g_b1[o - kSlotB1] += t;
+  else if (o < kSlotB2) { if (o - kSlotW2 < k.n_out * kHidden) k.g_w2[o - kSlotW2] += t; }
+  else if (o < kSlotAtt) { if (o - kSlotB2 < k.n_out) k.g_b2[o - kSlotB2] += t; }
+  else if (k.use_sdf && o == kSlotBeta) k.g_beta[0] += t;
+  else if (k.use_sdf && o == kSlotAlpha) k.g_alpha[0] += t;
+}
+
 // point groups per scene: the smallest power of two that brings a group's gradient rows under kBinGroupRowBytes (1 when
 // the scene's rows already are, or when the points do not divide into groups of whole 1024-point blocks)
 static inline int bin_groups(int64_t P) {
@@ -1553,17 +1779,35 @@ static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // The workspace of one nfi_field_query_bwd call: byte offsets of its regions and the total.  Behind the backward operand
 // image come, for the binned scatter only, the feature-gradient rows, the sorted entries, the bucket counters
 // (count[nb], n_items + the reduce's cursor padded to 64 B, cursor[nb]), the work items and the per-point flags.
+// The ordered mode keeps the rows and the flags and adds the two key arrays of the radix sort, its digit counts and the
+// parameter-gradient slots (one per wave of the largest grid the call can get).
 struct FieldBwdCarve {
-  bool binned;
+  bool binned, ordered;
   int groups, tile, tps;             // binned scatter: point groups per scene, tile side, tiles per plane side
   size_t nb, max_items;              // buckets over all scenes, upper bound of the work items
   size_t gf, entries, counts, items, flag, total;
+  int sort_blocks, sort_passes;      // ordered: sort blocks per (scene, plane) segment, 8-bit radix passes over the cell index
+  size_t keys[2], hist, slots, slot_bytes;
 };
+
+// blocks per scene of the backward kernel's grid, before the ray-order hint rounds it down to the 8 XCDs:
+// one resident set of blocks (2 per CU, 1 for the view-direction variant): every wave ends with ~3 k atomics on
+// the same weight-gradient addresses as every other wave, so more waves than the chip holds only add flush traffic
+// (points_only has no flush and balances better with more, smaller blocks)
+static int64_t field_bwd_blocks(const nfi_field_bwd_args* a) {
+  const int64_t chunks = (a->points_per_scene + 63) / 64;
+  int64_t blocks = (chunks + 3) / 4;
+  int64_t cap = (a->points_only ? 1024 : (a->ray_features ? 256 : 512)) / a->n_scenes;
+  if (cap < 16) cap = 16;
+  return blocks > cap ? cap : blocks;
+}
 
 static FieldBwdCarve field_bwd_carve(const nfi_field_bwd_args* a) {
   FieldBwdCarve c;
   memset(&c, 0, sizeof(c));
   c.binned = a->scatter_mode == 1 && !a->points_only;
+  c.ordered = a->scatter_mode == 2 && !a->points_only && !a->ray_features && a->n_scenes > 0 && a->points_per_scene > 0 &&
+              a->plane_res >= 2;
   size_t at = align256((a->ray_features ? kVbImageFloats : kBwdImageFloats) * sizeof(float));      // operand image at 0
   if (c.binned) {
     const size_t n_pts = (size_t)a->n_scenes * (size_t)a->points_per_scene;
@@ -1577,6 +1821,20 @@ static FieldBwdCarve field_bwd_carve(const nfi_field_bwd_args* a) {
     c.counts = at; at += align256(2 * c.nb * sizeof(int) + 64);
     c.items = at; at += align256(c.max_items * sizeof(int4));
     c.flag = at; at += align256(n_pts);
+  }
+  if (c.ordered) {
+    const size_t n_pts = (size_t)a->n_scenes * (size_t)a->points_per_scene;
+    c.sort_blocks = (int)((a->points_per_scene + kOrdTile - 1) / kOrdTile);
+    int bits = 1;
+    while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)a->plane_res * a->plane_res) ++bits;
+    c.sort_passes = (bits + 7) / 8;
+    c.gf = at; at += align256(n_pts * kC * sizeof(float));
+    c.flag = at; at += align256(n_pts);
+    c.keys[0] = at; at += align256(3 * n_pts * sizeof(uint64_t));
+    c.keys[1] = at; at += align256(3 * n_pts * sizeof(uint64_t));
+    c.hist = at; at += align256((size_t)a->n_scenes * 3 * kOrdDigits * c.sort_blocks * sizeof(uint32_t));
+    c.slot_bytes = (size_t)a->n_scenes * (size_t)field_bwd_blocks(a) * 4 * kSlotFloats * sizeof(float);
+    c.slots = at; at += align256(c.slot_bytes);
   }
   c.total = at;
   return c;
@@ -1614,11 +1872,14 @@ static int field_bwd_check_call(const nfi_field_bwd_args* a) {
   REQUIRE(a->points_only || a->n_attention == 0 || a->g_attention_values, "field_query_bwd: g_attention_values missing");
   REQUIRE(a->points_only || !a->use_sdf || (a->g_beta && a->g_alpha), "field_query_bwd: g_beta / g_alpha missing");
   const bool vd = a->ray_features != nullptr;
-  REQUIRE(a->scatter_mode == 0 || a->scatter_mode == 1, "field_query_bwd: scatter_mode must be 0 or 1");
+  REQUIRE(a->scatter_mode >= 0 && a->scatter_mode <= 2, "field_query_bwd: scatter_mode must be 0, 1 or 2");
+  REQUIRE(a->scatter_mode != 2 || !vd,
+          "field_query_bwd: scatter_mode 2 (ordered) does not cover the view-direction decoder (its g_ray_features are atomics)");
+  REQUIRE(a->scatter_mode != 2 || !a->points_only, "field_query_bwd: scatter_mode 2 (ordered) with points_only has nothing to order");
   REQUIRE(a->workspace_bytes >= nfi_field_bwd_workspace_bytes(a), "field_query_bwd: workspace too small");
   REQUIRE(a->points_per_scene <= (int64_t)1 << 30, "field_query_bwd: at most 2^30 points per scene");
-  REQUIRE(a->scatter_mode != 1 || a->points_only || a->points_per_scene <= (int64_t)1 << 25,
-          "field_query_bwd: the binned scatter takes at most 2^25 points per scene (use scatter_mode 0 or split the query)");
+  REQUIRE(a->scatter_mode == 0 || a->points_only || a->points_per_scene <= (int64_t)1 << 25,
+          "field_query_bwd: the binned and the ordered scatter take at most 2^25 points per scene (use scatter_mode 0 or split the query)");
   REQUIRE(!vd || (a->w3 && a->samples_per_ray > 0 && a->points_per_scene % a->samples_per_ray == 0),
           "field_query_bwd: view-direction decoder needs w3 and points_per_scene % samples_per_ray == 0");
   REQUIRE(!vd || a->points_only || (a->g_w3 && a->g_b3), "field_query_bwd: g_w3 / g_b3 missing");
@@ -1690,14 +1951,23 @@ extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t str
     bp.tile = ws.tile; bp.tps = ws.tps; bp.bpg = 3 * ws.tps * ws.tps; bp.n_buckets = ws.groups * bp.bpg;
     bp.groups = ws.groups; bp.group_pts = a->points_per_scene / ws.groups; bp.next_item = n_items + 1;
   }
-  int64_t chunks = (a->points_per_scene + 63) / 64;
-  int64_t blocks = (chunks + 3) / 4;
-  // one resident set of blocks (2 per CU, 1 for the view-direction variant): every wave ends with ~3 k atomics on
-  // the same weight-gradient addresses as every other wave, so more waves than the chip holds only add flush traffic
-  // (points_only has no flush and balances better with more, smaller blocks)
-  int64_t cap = (a->points_only ? 1024 : (vd ? 256 : 512)) / a->n_scenes;
-  if (cap < 16) cap = 16;
-  if (blocks > cap) blocks = cap;
+  OrdParams op;
+  memset(&op, 0, sizeof(op));
+  if (ws.ordered) {
+    // every wave's slot is zeroed; keys, counts, rows and flags are written before they are read
+    float* slots = reinterpret_cast<float*>(w + ws.slots);
+    if (hipMemsetAsync(slots, 0, ws.slot_bytes, s) != hipSuccess) return fail(NFI_ERR_LAUNCH, "field_query_bwd: memset failed");
+    k.gf_out = reinterpret_cast<float*>(w + ws.gf);
+    k.bin_flag = reinterpret_cast<uint8_t*>(w + ws.flag);
+    k.g_w1 = slots + kSlotW1; k.g_b1 = slots + kSlotB1; k.g_w2 = slots + kSlotW2; k.g_b2 = slots + kSlotB2;
+    k.g_att = slots + kSlotAtt; k.g_beta = slots + kSlotBeta; k.g_alpha = slots + kSlotAlpha;
+    k.slot_stride = kSlotFloats;
+    op.points = a->points; op.P = a->points_per_scene; op.n_scenes = a->n_scenes; op.res = a->plane_res;
+    op.scene_range = a->scene_range; op.flag = k.bin_flag; op.gf = k.gf_out;
+    op.hist = reinterpret_cast<uint32_t*>(w + ws.hist); op.nblk = ws.sort_blocks;
+    op.g_texels = a->g_texels; op.layout = a->texel_layout;
+  }
+  int64_t blocks = field_bwd_blocks(a);
   if (a->rays_per_row > 0 && a->samples_per_ray > 0 && a->samples_per_ray % 64 == 0 &&
       a->points_per_scene % a->samples_per_ray == 0 && (a->points_per_scene / a->samples_per_ray) % a->rays_per_row == 0) {
     // ray-order hint: usable when the image divides into 16- or 8-pixel tiles and the grid into the 8 XCDs
@@ -1720,6 +1990,23 @@ extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t str
     hipLaunchKernelGGL(bin_fill_kernel, pgrid, dim3(256), 0, s, bp);
     // persistent: the resident set of workgroups (2 per CU) takes the work items in order from the cursor
     hipLaunchKernelGGL(bin_reduce_kernel, dim3((unsigned)std::min<size_t>(ws.max_items, 256 * 2)), dim3(kBinThreads), 0, s, bp);
+  }
+  if (ws.ordered) {
+    const FinishParams fp{reinterpret_cast<const float*>(w + ws.slots), (int)blocks * 4, a->n_scenes, a->n_attention, n_out, a->use_sdf,
+                          a->g_w1, a->g_b1, a->g_w2, a->g_b2, a->g_attention_values, a->g_beta, a->g_alpha};
+    hipLaunchKernelGGL(param_finish_kernel, dim3(kSlotFloats / 16), dim3(256), 0, s, fp);
+    const dim3 sgrid((unsigned)ws.sort_blocks, (unsigned)(a->n_scenes * 3));
+    op.keys_in = reinterpret_cast<uint64_t*>(w + ws.keys[0]); op.keys_out = reinterpret_cast<uint64_t*>(w + ws.keys[1]);
+    hipLaunchKernelGGL(ord_keys_kernel, dim3((unsigned)((a->points_per_scene + 255) / 256), (unsigned)a->n_scenes), dim3(256), 0, s, op);
+    for (int pass = 0; pass < ws.sort_passes; ++pass) {
+      op.shift = 8 * pass;
+      hipLaunchKernelGGL(ord_hist_kernel, sgrid, dim3(64), 0, s, op);
+      hipLaunchKernelGGL(ord_scan_kernel, dim3((unsigned)(a->n_scenes * 3)), dim3(256), 0, s, op);
+      hipLaunchKernelGGL(ord_scatter_kernel, sgrid, dim3(64), 0, s, op);
+      std::swap(op.keys_in, op.keys_out);
+    }
+    const int64_t half_waves = (int64_t)a->n_scenes * 3 * a->plane_res * a->plane_res;
+    hipLaunchKernelGGL(ord_gather_kernel, dim3((unsigned)((half_waves + 7) / 8)), dim3(256), 0, s, op);
   }
   return check_launch("field_query_bwd");
 }

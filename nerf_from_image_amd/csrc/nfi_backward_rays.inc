@@ -211,6 +211,75 @@ extern "C" int nfi_points_bwd(const float* g_points, const float* depth, int64_t
 // ------------------------------------------------------------------------------------------------
 // camera-ray backward (lib/nerf_utils.py:28-91 + F.normalize): g_ro, g_rd -> g_cam2world, g_focal
 // ------------------------------------------------------------------------------------------------
+// one pixel's terms of the 17 sums (16 entries of cam2world + focal), added to acc
+__device__ __forceinline__ void raygen_bwd_pixel(const CameraParams& cam, int b, int pix, const float* __restrict__ g_ro,
+                                                 const float* __restrict__ g_rd, double (&acc)[17]) {
+  const int hw = cam.height * cam.width;
+  const int row = pix / cam.width, col = pix - row * cam.width;
+  const int64_t ray = (int64_t)b * hw + pix;
+  const float* M = cam.cam2world + (size_t)b * 16;
+  // forward recompute of the camera-space vectors (un-normalised)
+  CameraParams c2 = cam;
+  c2.normalize = 0;
+  float o[3], raw[3];
+  make_ray(c2, b, row, col, o, raw);
+  float go[3] = {0.0f, 0.0f, 0.0f}, gd[3] = {0.0f, 0.0f, 0.0f};
+  if (g_ro) { go[0] = g_ro[ray * 3]; go[1] = g_ro[ray * 3 + 1]; go[2] = g_ro[ray * 3 + 2]; }
+  if (g_rd) { gd[0] = g_rd[ray * 3]; gd[1] = g_rd[ray * 3 + 1]; gd[2] = g_rd[ray * 3 + 2]; }
+  float graw[3] = {gd[0], gd[1], gd[2]};
+  if (cam.normalize) {
+    const float nrm = fmaxf(norm3(raw[0], raw[1], raw[2]), 1e-12f);
+    const float ux = raw[0] / nrm, uy = raw[1] / nrm, uz = raw[2] / nrm;
+    const float dot = ux * gd[0] + uy * gd[1] + uz * gd[2];
+    graw[0] = (gd[0] - ux * dot) / nrm; graw[1] = (gd[1] - uy * dot) / nrm; graw[2] = (gd[2] - uz * dot) / nrm;
+  }
+  float u = (float)col / (float)cam.width, v = (float)row / (float)cam.height;
+  if (cam.focal) {
+    if (cam.center) { u = (u - 0.5f * (2.0f * cam.center[b * 2] - 1.0f)) - 0.5f; v = (v - 0.5f * (2.0f * cam.center[b * 2 + 1] - 1.0f)) - 0.5f; }
+    else { u -= 0.5f; v -= 0.5f; }
+    if (cam.bbox) { const float* bb = cam.bbox + b * 4; u = (bb[2] * (u + 0.5f) + bb[0]) * 0.5f; v = -(bb[3] * (-v + 0.5f) + bb[1]) * 0.5f; }
+    const float f = cam.focal[b];
+    const float cd[3] = {u / f, -(v / f), -1.0f};
+    float gcd[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+      for (int m = 0; m < 3; ++m) { acc[k * 4 + m] += graw[k] * cd[m]; gcd[m] += graw[k] * M[k * 4 + m]; }
+      acc[k * 4 + 3] += go[k];
+    }
+    acc[16] += (gcd[0] * (-u) + gcd[1] * v) / (f * f);
+  } else {
+    u = (u - 0.5f) * 2.0f; v = (v - 0.5f) * 2.0f;
+    if (cam.bbox) { const float* bb = cam.bbox + b * 4; u = bb[2] * (u / 2.0f + 0.5f) + bb[0]; v = -(bb[3] * (-v / 2.0f + 0.5f) + bb[1]); }
+    const float co[3] = {u, -v, 0.0f};
+    const float w = M[15];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      acc[k * 4 + 0] += go[k] * co[0];
+      acc[k * 4 + 1] += go[k] * co[1];
+      acc[k * 4 + 2] += go[k] * co[2] - graw[k] / w;    // cd = (0,0,-1), rd = (R cd)/w
+      acc[k * 4 + 3] += go[k];
+      acc[15] += -graw[k] * raw[k] / w;                 // raw = (R cd)/w
+    }
+  }
+}
+
+// the block's 17 sums (256 threads): lanes, then the four waves, in float64 and in a fixed order; thread t < 17 gets sum t
+// rounded to fp32
+__device__ __forceinline__ float raygen_bwd_block_sum(const double (&acc)[17], double (&red)[4][17]) {
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < 17; ++i) {
+    double s = acc[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if ((threadIdx.x & 63) == 0) red[wave][i] = s;
+  }
+  __syncthreads();
+  const int t = threadIdx.x < 17 ? threadIdx.x : 0;
+  return (float)((red[0][t] + red[1][t]) + (red[2][t] + red[3][t]));
+}
+
 __global__ __launch_bounds__(256) void raygen_bwd_kernel(CameraParams cam, int n_scenes, const float* __restrict__ g_ro,
                                                          const float* __restrict__ g_rd, float* __restrict__ g_cam,
                                                          float* __restrict__ g_focal) {
@@ -223,66 +292,9 @@ __global__ __launch_bounds__(256) void raygen_bwd_kernel(CameraParams cam, int n
   double acc[17];
 #pragma unroll
   for (int i = 0; i < 17; ++i) acc[i] = 0.0;   // 16 matrix entries + focal
-  if (pix < hw) {
-    const int row = pix / cam.width, col = pix - row * cam.width;
-    const int64_t ray = (int64_t)b * hw + pix;
-    const float* M = cam.cam2world + (size_t)b * 16;
-    // forward recompute of the camera-space vectors (un-normalised)
-    CameraParams c2 = cam;
-    c2.normalize = 0;
-    float o[3], raw[3];
-    make_ray(c2, b, row, col, o, raw);
-    float go[3] = {0.0f, 0.0f, 0.0f}, gd[3] = {0.0f, 0.0f, 0.0f};
-    if (g_ro) { go[0] = g_ro[ray * 3]; go[1] = g_ro[ray * 3 + 1]; go[2] = g_ro[ray * 3 + 2]; }
-    if (g_rd) { gd[0] = g_rd[ray * 3]; gd[1] = g_rd[ray * 3 + 1]; gd[2] = g_rd[ray * 3 + 2]; }
-    float graw[3] = {gd[0], gd[1], gd[2]};
-    if (cam.normalize) {
-      const float nrm = fmaxf(norm3(raw[0], raw[1], raw[2]), 1e-12f);
-      const float ux = raw[0] / nrm, uy = raw[1] / nrm, uz = raw[2] / nrm;
-      const float dot = ux * gd[0] + uy * gd[1] + uz * gd[2];
-      graw[0] = (gd[0] - ux * dot) / nrm; graw[1] = (gd[1] - uy * dot) / nrm; graw[2] = (gd[2] - uz * dot) / nrm;
-    }
-    float u = (float)col / (float)cam.width, v = (float)row / (float)cam.height;
-    if (cam.focal) {
-      if (cam.center) { u = (u - 0.5f * (2.0f * cam.center[b * 2] - 1.0f)) - 0.5f; v = (v - 0.5f * (2.0f * cam.center[b * 2 + 1] - 1.0f)) - 0.5f; }
-      else { u -= 0.5f; v -= 0.5f; }
-      if (cam.bbox) { const float* bb = cam.bbox + b * 4; u = (bb[2] * (u + 0.5f) + bb[0]) * 0.5f; v = -(bb[3] * (-v + 0.5f) + bb[1]) * 0.5f; }
-      const float f = cam.focal[b];
-      const float cd[3] = {u / f, -(v / f), -1.0f};
-      float gcd[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int m = 0; m < 3; ++m) { acc[k * 4 + m] += graw[k] * cd[m]; gcd[m] += graw[k] * M[k * 4 + m]; }
-        acc[k * 4 + 3] += go[k];
-      }
-      acc[16] += (gcd[0] * (-u) + gcd[1] * v) / (f * f);
-    } else {
-      u = (u - 0.5f) * 2.0f; v = (v - 0.5f) * 2.0f;
-      if (cam.bbox) { const float* bb = cam.bbox + b * 4; u = bb[2] * (u / 2.0f + 0.5f) + bb[0]; v = -(bb[3] * (-v / 2.0f + 0.5f) + bb[1]); }
-      const float co[3] = {u, -v, 0.0f};
-      const float w = M[15];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        acc[k * 4 + 0] += go[k] * co[0];
-        acc[k * 4 + 1] += go[k] * co[1];
-        acc[k * 4 + 2] += go[k] * co[2] - graw[k] / w;    // cd = (0,0,-1), rd = (R cd)/w
-        acc[k * 4 + 3] += go[k];
-        acc[15] += -graw[k] * raw[k] / w;                 // raw = (R cd)/w
-      }
-    }
-  }
-  const int wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 17; ++i) {
-    double s = acc[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if ((threadIdx.x & 63) == 0) red[wave][i] = s;
-  }
-  __syncthreads();
+  if (pix < hw) raygen_bwd_pixel(cam, b, pix, g_ro, g_rd, acc);
+  const float s = raygen_bwd_block_sum(acc, red);
   if (threadIdx.x < 17) {
-    const float s = (float)((red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
     if (threadIdx.x < 16) atomicAdd(&g_cam[b * 16 + threadIdx.x], s);
     else if (g_focal) atomicAdd(&g_focal[b], s);
   }
@@ -301,4 +313,34 @@ extern "C" int nfi_raygen_bwd(const nfi_raygen_args* a, const float* g_ray_origi
   hipLaunchKernelGGL(raygen_bwd_kernel, grid, dim3(256), 0, s, cam, a->n_scenes, g_ray_origins, g_ray_directions,
                      g_cam2world, g_focal);
   return check_launch("raygen_bwd");
+}
+
+// ordered variant: one block per image walks all pixels (thread t: pixels t, t + 256, ...), the 17 sums stay in float64
+// over the whole image (lanes, then waves, in a fixed order), are rounded once and STORED: no atomic, no memset, the same
+// bits on every launch - and closer to the exact sums than the per-block rounding above
+__global__ __launch_bounds__(256) void raygen_bwd_ordered_kernel(CameraParams cam, const float* __restrict__ g_ro,
+                                                                 const float* __restrict__ g_rd, float* __restrict__ g_cam,
+                                                                 float* __restrict__ g_focal) {
+  __shared__ double red[4][17];
+  const int hw = cam.height * cam.width;
+  const int b = blockIdx.x;
+  double acc[17];
+#pragma unroll
+  for (int i = 0; i < 17; ++i) acc[i] = 0.0;
+  for (int pix = threadIdx.x; pix < hw; pix += 256) raygen_bwd_pixel(cam, b, pix, g_ro, g_rd, acc);
+  const float s = raygen_bwd_block_sum(acc, red);
+  if (threadIdx.x < 17) {
+    if (threadIdx.x < 16) g_cam[b * 16 + threadIdx.x] = s;
+    else if (g_focal) g_focal[b] = s;
+  }
+}
+
+extern "C" int nfi_raygen_bwd_ordered(const nfi_raygen_args* a, const float* g_ray_origins, const float* g_ray_directions,
+                                      float* g_cam2world, float* g_focal, nfi_stream_t stream) {
+  REQUIRE(a && a->cam2world && g_cam2world && (g_ray_origins || g_ray_directions), "raygen_bwd_ordered: null pointer");
+  REQUIRE(a->n_scenes > 0 && a->height > 0 && a->width > 0, "raygen_bwd_ordered: bad shape");
+  CameraParams cam{a->cam2world, a->focal, a->bbox, a->focal ? a->center : nullptr, a->height, a->width, a->normalize, a->height, 0};
+  hipLaunchKernelGGL(raygen_bwd_ordered_kernel, dim3((unsigned)a->n_scenes), dim3(256), 0, (hipStream_t)stream, cam,
+                     g_ray_origins, g_ray_directions, g_cam2world, g_focal);
+  return check_launch("raygen_bwd_ordered");
 }

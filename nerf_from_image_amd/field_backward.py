@@ -15,7 +15,12 @@ def field_query_bwd(points, texels, decoder_image, w1, w2, scene_range, n_attent
     viewdir: None or dict(ray_features=padded [B,N,48], samples_per_ray, w3) for the --use_viewdir decoder
     (decoder_image from ops.decoder_pack_viewdir, w2 [33,64]); adds g_ray_features [B,N,32], g_w3, g_b3.
     ray_order: None or (samples_per_ray, rays_per_row) - the points are [rays][samples] with the rays in row-major image
-    order (the fused render's stash): a locality hint for the kernel's walk, no effect on the result."""
+    order (the fused render's stash): a locality hint for the kernel's walk, no effect on the result.
+    scatter_mode: None (by size), 0 atomics per point, 1 binned, 2 ordered - every returned tensor bit-identical from
+    launch to launch (plain decoder, not points_only: NotImplementedError otherwise, before any launch)."""
+    if scatter_mode is not None and int(scatter_mode) == 2 and (viewdir is not None or points_only):
+        raise NotImplementedError('field_query_bwd: scatter_mode 2 (ordered) covers the plain decoder with parameter '
+                                  'gradients: not the view-direction decoder, not points_only')
     f = ops._f32c
     points = f(points, 'points')
     B, P = points.shape[0], points.shape[1]
@@ -78,10 +83,11 @@ def field_query_bwd(points, texels, decoder_image, w1, w2, scene_range, n_attent
 
 
 def make_field_bwd(texels, decoder_image, scene_range, n_attention, use_sdf, want_sdf, want_sem, viewdir_pad=None,
-                   samples_per_ray=0):
+                   samples_per_ray=0, scatter_mode=None):
     """Backward closure for ``autograd.differentiable('field_query', ...)``.
     inputs = (points, planes, w1, b1, w2, b2, attention_values, beta, alpha[, ray_feature, w3, b3]);
-    outputs = (sigma, rgb[, sdf][, semantics]).  viewdir_pad: padded ray features of the --use_viewdir decoder."""
+    outputs = (sigma, rgb[, sdf][, semantics]).  viewdir_pad: padded ray features of the --use_viewdir decoder.
+    scatter_mode: handed to field_query_bwd (2: the ordered mode)."""
     def bwd(inputs, outputs, grads, needs):
         pts, planes, w1, b1, w2, b2, att, be, al = inputs[:9]
         vd = None
@@ -97,7 +103,8 @@ def make_field_bwd(texels, decoder_image, scene_range, n_attention, use_sdf, wan
         if want_sem:
             g_sem = grads[i]
         g = field_query_bwd(pts, texels, decoder_image, w1, w2, scene_range, n_attention, att, use_sdf, be, al,
-                            g_sigma, g_rgb, g_sdf, g_sem, want_points=bool(needs[0]), viewdir=vd)
+                            g_sigma, g_rgb, g_sdf, g_sem, want_points=bool(needs[0]), viewdir=vd,
+                            scatter_mode=scatter_mode)
         g_planes = ops.texel_grad_to_planes(g['g_texels']) if needs[1] else None
         base = (g.get('g_points'), g_planes, g['g_w1'], g['g_b1'], g['g_w2'], g['g_b2'],
                 g.get('g_attention_values'), g.get('g_beta'), g.get('g_alpha'))

@@ -106,12 +106,15 @@ def texels_of(planes, texel_dtype=ops.TEXEL_F32, cache=None):
 
 
 def make_sampler(planes, decoder, scene_range, n_attention, attention_values, use_sdf, beta, alpha,
-                 texel_dtype=ops.TEXEL_F32, request_model_outputs=(), viewdir=None, texel_cache=None):
+                 texel_dtype=ops.TEXEL_F32, request_model_outputs=(), viewdir=None, texel_cache=None,
+                 deterministic_backward=False):
     """Builds the ``sampler(x_in, request_sampler_outputs)`` closure over HIP kernels.
 
     planes [B,3,32,R,R] (view of the synthesis output), decoder: module with .net[0]/.net[2].
     viewdir (--use_viewdir): (ray_feature [B,H,W,1,32] = output of ViewDirectionMapper.fc6, output_layer =
-    the mapper's `output` EqualizedLinear); the closure of generator.py:243-251 is then part of the kernels."""
+    the mapper's `output` EqualizedLinear); the closure of generator.py:243-251 is then part of the kernels.
+    deterministic_backward: the closure's backward runs the field backward in its ordered mode (scatter_mode 2, plain
+    decoder; the view-direction decoder keeps its own backward)."""
     w1, b1, w2, b2 = decoder_parameters(decoder)
     texels = texels_of(planes, texel_dtype, texel_cache)
     ray_feature = w3 = b3 = ray_pad = None
@@ -157,7 +160,8 @@ def make_sampler(planes, decoder, scene_range, n_attention, attention_values, us
                          (('semantics',) if want_sem else ()))
         bwd = None
         if texel_dtype == ops.TEXEL_F32 or ray_pad is None:      # (the view-direction decoder's backward is fp32-texel only)
-            bwd = make_field_bwd(texels, image, scene_range, n_attention, use_sdf, want_sdf, want_sem, ray_pad, spr)
+            bwd = make_field_bwd(texels, image, scene_range, n_attention, use_sdf, want_sdf, want_sem, ray_pad, spr,
+                                 scatter_mode=2 if (deterministic_backward and ray_pad is None) else None)
         # what an output does not depend on gets no gradient (None, not zeros - as in the reference's graph): the colour
         # table only enters rgb, beta / alpha only sigma
         det = (lambda t, used: t if (t is None or used) else t.detach())
@@ -279,6 +283,11 @@ def regulariser_outputs(self, planes, request_model_outputs, texel_cache=None):
     return out
 
 
+def _sampler_options(model):
+    """make_sampler's keywords that attach() switched on (none by default: the call is then the one it always was)."""
+    return {'deterministic_backward': True} if getattr(model, 'nfi_deterministic_backward', False) else {}
+
+
 def hip_forward(self, viewdir, c, request_model_outputs=['sampler'], model_inputs={}):
     """Replacement for Generator.forward (models/generator.py:407-686): same arguments, same
     returned dict; the plane producer is called as in the reference, the field is HIP."""
@@ -367,7 +376,7 @@ def hip_forward(self, viewdir, c, request_model_outputs=['sampler'], model_input
             planes, self.decoder, self.scene_range, self.attention_values, attention_values, self.use_sdf,
             self.beta if self.use_sdf else None, self.alpha if self.use_sdf else None,
             texel_dtype=getattr(self, 'nfi_texel_dtype', ops.TEXEL_F32), request_model_outputs=request_model_outputs,
-            viewdir=vd, texel_cache=texel_cache)
+            viewdir=vd, texel_cache=texel_cache, **_sampler_options(self))
     return model_outputs
 
 
@@ -504,7 +513,8 @@ def wrapped_forward(self, viewdir, c, request_model_outputs=['sampler'], model_i
             planes, self.decoder, self.scene_range, self.attention_values, att, self.use_sdf,
             self.beta if self.use_sdf else None, self.alpha if self.use_sdf else None,
             texel_dtype=getattr(self, 'nfi_texel_dtype', ops.TEXEL_F32), request_model_outputs=request_model_outputs,
-            viewdir=(cap['x'], self.viewdir_mapper.output) if use_vd else None, texel_cache=texel_cache)
+            viewdir=(cap['x'], self.viewdir_mapper.output) if use_vd else None, texel_cache=texel_cache,
+            **_sampler_options(self))
     if added_att:
         del model_outputs['attention_values']
     return model_outputs
@@ -533,8 +543,13 @@ def bake(model, model_input, model_inputs={}):
     return baked
 
 
-def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_handoff=False, hip_viewdir_mapper=False):
+def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_handoff=False, hip_viewdir_mapper=False,
+           deterministic_backward=False):
     """Gives a reference-style Generator the HIP sampler.  Returns the same module.
+
+    deterministic_backward: the sampler closure's backward (the staged path) runs the field backward in its ordered mode
+    (nfi_field_bwd_args.scatter_mode 2): bit-identical gradients from call to call, for the plain decoder; a use_viewdir
+    model's closure keeps its atomics.  The fused + stash node takes the render option of the same name.
 
     hip_viewdir_mapper (use_viewdir models only, off by default): the per-ray trunk of model.viewdir_mapper (fc0 .. fc6,
     norm1 .. norm4; generator.py:223-239) runs as one HIP autograd node instead of its PyTorch modules, which are then
@@ -555,6 +570,7 @@ def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_hando
         raise AttributeError('attach(): module lacks %s' % missing)
     model.nfi_texel_dtype = texel_dtype
     model.nfi_hip_regularisers = bool(hip_regularisers)
+    model.nfi_deterministic_backward = bool(deterministic_backward)
     if hip_viewdir_mapper:
         if not getattr(model, 'use_viewdir', False) or not hasattr(model, 'viewdir_mapper'):
             raise TypeError('attach(hip_viewdir_mapper=True): the model has no view-direction mapper (use_viewdir is off)')

@@ -705,7 +705,8 @@ def points_bwd(g_points, depth, want_ro=True, want_rd=True):
     return g_ro, g_rd
 
 
-def raygen_bwd(height, width, focal, cam2world, bbox, center, normalize, g_ro, g_rd):
+def raygen_bwd(height, width, focal, cam2world, bbox, center, normalize, g_ro, g_rd, ordered=False):
+    """g_cam2world [B,4,4], g_focal [B] or None.  ordered: nfi_raygen_bwd_ordered - the same bits on every launch."""
     cam2world = _f32c(cam2world, 'tform_cam2world')
     B = cam2world.shape[0]
     focal, bbox, center = _f32c(focal, 'focal_length'), _f32c(bbox, 'bbox'), _f32c(center, 'center')
@@ -716,8 +717,9 @@ def raygen_bwd(height, width, focal, cam2world, bbox, center, normalize, g_ro, g
                        bbox=bbox, center=center, normalize=int(normalize))
     import ctypes
     with torch.cuda.device(cam2world.device):
-        _lib.check(lib.nfi_raygen_bwd(ctypes.byref(a), _lib.ptr(_f32c(g_ro, 'g_ro')), _lib.ptr(_f32c(g_rd, 'g_rd')),
-                                      _lib.ptr(g_cam), _lib.ptr(g_focal), _stream(cam2world)), 'nfi_raygen_bwd')
+        name = 'nfi_raygen_bwd_ordered' if ordered else 'nfi_raygen_bwd'
+        _lib.check(getattr(lib, name)(ctypes.byref(a), _lib.ptr(_f32c(g_ro, 'g_ro')), _lib.ptr(_f32c(g_rd, 'g_rd')),
+                                      _lib.ptr(g_cam), _lib.ptr(g_focal), _stream(cam2world)), name)
     return g_cam, g_focal
 
 

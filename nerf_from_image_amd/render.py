@@ -60,6 +60,16 @@ process-wide - the reference calls render from one thread per GPU):
                     V*H*W rays per scene sums the views' plane / attention-value / decoder gradients, camera and focal
                     gradients stay per camera; at most 2^25 points per scene, V*H*W*samples - else ValueError), staged (the V
                     views of a scene as one image V*H rows tall; so are the viewdirs a use_viewdir model receives).
+  deterministic_backward  False (default), or True: every gradient the fused + stash node returns (planes, decoder, attention
+                    values, beta, alpha, camera, focal) is bit-identical from call to call for identical inputs on the same
+                    device and build: the field backward runs in its ordered mode (nfi_field_bwd_args.scatter_mode 2: sorted
+                    plane-gradient gather, per-wave parameter slots summed in order) and the camera backward through
+                    nfi_raygen_bwd_ordered, for any views_per_scene and either force_no_cam_grad.  Slower (DESIGN.md section
+                    6).  The forward, its outputs and every inference path ignore it.  A use_viewdir model that needs a
+                    gradient raises NotImplementedError (its per-ray feature gradient is summed with atomics); the staged
+                    path's sampler closure takes its own switch, generator.attach(..., deterministic_backward=True); the
+                    producer, the regulariser and the hand-off backward are outside it, and torch.use_deterministic_algorithms
+                    is not consulted.
 
 ``render_views(fused, height, width, tform_cam2world, focal_length, depth_samples_per_ray, ...)`` renders from planes that
 exist already (``generator.bake(model, model_input)``, or any sampler's ``.fused``) without calling a model: cameras
@@ -75,7 +85,8 @@ from .field_backward import field_query_bwd
 
 args = None
 dataset_config = None
-_DEFAULTS = dict(termination_eps=0.0, strict_near_far=True, row_window=None, row_window_sync=False, views_per_scene=1)
+_DEFAULTS = dict(termination_eps=0.0, strict_near_far=True, row_window=None, row_window_sync=False, views_per_scene=1,
+                 deterministic_backward=False)
 MAX_STASH_POINTS_PER_SCENE = 1 << 25      # nfi_field_query_bwd's binned scatter addresses a scene's points by 32-bit byte offsets
 options = types.SimpleNamespace(**_DEFAULTS)
 
@@ -128,7 +139,7 @@ def _needs_grad(*tensors):
 
 
 def _render_with_stash(fused, height, width, S, cam, focal, bbox, center, noise_c, noise_f, white, cam_grad, fine=True,
-                       strict=False, views_per_scene=1):
+                       strict=False, views_per_scene=1, deterministic=False):
     """The fused render as ONE autograd node (see the module docstring).  Gradients follow the reference's graph:
     rgb_map / mask -> sigma, rgb of every sample and (through dists * ||rd||) the ray directions; depth_map and the
     depth samples carry none; the field -> planes, decoder, colour table, beta, alpha and - unless the camera is
@@ -139,7 +150,8 @@ def _render_with_stash(fused, height, width, S, cam, focal, bbox, center, noise_
     views_per_scene = V: `cam` holds V cameras per scene of `fused`, scene-major.  The stash is ray-major, so the V views of
     a scene are one contiguous run of points: the ONE field backward launch sees B scenes of V * H * W rays (an image
     V * H rows tall) and sums the plane, attention-value and decoder gradients of all views; camera and focal gradients
-    stay per camera."""
+    stay per camera.
+    deterministic: the backward's ordered mode (the option deterministic_backward; plain decoder only)."""
     texels, image = fused.texels, fused.decoder_image
     A, use_sdf, scene_range = fused.n_attention, fused.use_sdf, fused.scene_range
     w1, b1, w2, b2 = fused.decoder_params[:4]
@@ -168,18 +180,18 @@ def _render_with_stash(fused, height, width, S, cam, focal, bbox, center, noise_
         viewdir = dict(ray_features=fused.ray_features, samples_per_ray=n_list, w3=inputs[11]) if vd else None
         g = field_query_bwd(pts, texels, image, a_w1, a_w2, scene_range, A, att, use_sdf, be, al,
                             cb['g_sigma'].view(B, -1), cb['g_rgb'].view(B, -1, 3), want_points=bool(cam_grad),
-                            viewdir=viewdir, ray_order=(n_list, width))
+                            viewdir=viewdir, ray_order=(n_list, width), scatter_mode=2 if deterministic else None)
         g_cam = g_focal = None
         if full:
             g_ro, g_rd = ops.points_bwd(g['g_points'].view(*st_t.shape, 3), st_t)
             g_rd = g_rd + cb['g_ray_directions']
-            g_cam, g_focal = ops.raygen_bwd(height, width, a_focal, a_cam, bbox, center, True, g_ro, g_rd)
+            g_cam, g_focal = ops.raygen_bwd(height, width, a_focal, a_cam, bbox, center, True, g_ro, g_rd, ordered=deterministic)
         elif cam_grad == 'fine_origins':
             # force_no_cam_grad: only the origins of the FINE samples (stash columns S ...) are attached in the reference
             g_pts = g['g_points'].view(*st_t.shape, 3).clone()
             g_pts[..., :S, :] = 0.0
             g_ro, _ = ops.points_bwd(g_pts, st_t, want_rd=False)
-            g_cam, _ = ops.raygen_bwd(height, width, a_focal, a_cam, bbox, center, True, g_ro, None)
+            g_cam, _ = ops.raygen_bwd(height, width, a_focal, a_cam, bbox, center, True, g_ro, None, ordered=deterministic)
         g_planes = ops.texel_grad_to_planes(g['g_texels']) if needs[2] else None
         base = (g_cam, g_focal, g_planes, g['g_w1'], g['g_b1'], g['g_w2'], g['g_b2'], g.get('g_attention_values'),
                 g.get('g_beta'), g.get('g_alpha'))
@@ -364,6 +376,9 @@ def _render_from_field(opts, fused, sampler, height, width, tform_cam2world, foc
         return out['rgb'], out['depth'], out['mask'], out.get('normals'), extra_map
     if opts.row_window is not None:
         raise NotImplementedError('row_window is an option of the fused inference path (no gradient, no extra maps)')
+    if opts.deterministic_backward and ray_features is not None:
+        raise NotImplementedError('deterministic_backward: the view-direction decoder has no ordered backward (its per-ray '
+                                  'feature gradient is summed with atomics)')
 
     if fused is not None and plain and (ray_features is None or fused.texels.dtype == torch.float32):
         # ---------------- fused render + stash as one differentiable node ----------------
@@ -380,7 +395,8 @@ def _render_from_field(opts, fused, sampler, height, width, tform_cam2world, foc
         det = (lambda t: None if t is None else t.detach())
         rgb_map, depth_map, mask = _render_with_stash(
             fused, height, width, S, tform_cam2world, focal_length, det(bbox), det(center), noise_c, inverse_cdf_draws(),
-            white, cam_grad, fine=fine_sampling, strict=_strict(opts), views_per_scene=V)
+            white, cam_grad, fine=fine_sampling, strict=_strict(opts), views_per_scene=V,
+            deterministic=bool(opts.deterministic_backward))
         return rgb_map, depth_map, mask, None, None
 
     # ---------------- staged path (extra maps with a gradient or over a pass of more than 128 samples) ----------------

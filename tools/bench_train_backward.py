@@ -3,6 +3,10 @@
 render of nerf_from_image_amd.render hands to field_query_bwd), replayed N times with HIP events.
 
     python tools/bench_train_backward.py [N]            NFI_PROBE_LIBRARY=<variant .so> selects a variant build
+    NFI_SCATTER_MODES=0,1,2 python tools/bench_train_backward.py     the atomic, the binned and the ordered scatter, alternating
+
+A variant library built from an older revision may lack exports the header has since gained: they are dropped from the
+binding (the calls timed here exist in every revision), and modes the variant refuses are skipped.
 """
 import os
 import sys
@@ -14,7 +18,12 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import torch  # noqa: E402
 from nerf_from_image_amd import _lib  # noqa: E402
 if os.environ.get('NFI_PROBE_LIBRARY'):
+    import ctypes
     _lib.LIBRARY = os.environ['NFI_PROBE_LIBRARY']
+    _probe = ctypes.CDLL(_lib.LIBRARY)
+    for _name in [f for f in _lib.FUNCTIONS if not hasattr(_probe, f)]:
+        print('%s lacks %s: dropped from the binding' % (os.path.basename(_lib.LIBRARY), _name))
+        del _lib.FUNCTIONS[_name]
 
 
 def capture(dev, batch=4, res=128, samples=64, plane_res=256):
@@ -61,7 +70,11 @@ def main():
     for rnd in range(2 if len(modes) > 1 else 1):          # (two alternating rounds when modes are compared)
         for mode in modes:
             km = dict(k, scatter_mode=mode)
-            out = fn(*a, **km)
+            try:
+                out = fn(*a, **km)
+            except RuntimeError as e:
+                print('%s scatter_mode %d: refused (%s)' % (os.path.basename(_lib.LIBRARY), mode, e))
+                continue
             torch.cuda.synchronize()
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
             for i in range(n):
@@ -75,12 +88,14 @@ def main():
             err_max = float((got - exact).abs().max() / exact.abs().max())
             err_l2 = float((got - exact).norm() / exact.norm())
             pts = a[0].shape[0] * a[0].shape[1]
+            ws_mb = _lib.struct_query('nfi_field_bwd_workspace_bytes', 'nfi_field_bwd_args', n_scenes=a[0].shape[0],
+                                      points_per_scene=a[0].shape[1], plane_res=a[1].shape[2], scatter_mode=mode) / 2.0 ** 20
             gs = a[11]
             print('%s scatter_mode %d: %.1f M points (%.1f %% with a non-zero sigma gradient): field backward + scatter %.3f ms median '
-                  '(min %.3f)  |g_texels| %.9e  sum %.9e  |g_w1| %.9e  vs atomic scatter: max %.2e of max, l2 %.2e' % (
+                  '(min %.3f)  |g_texels| %.9e  sum %.9e  |g_w1| %.9e  vs atomic scatter: max %.2e of max, l2 %.2e  workspace %.1f MiB' % (
                       os.path.basename(_lib.LIBRARY), mode, pts / 1e6, 100.0 * float((gs != 0).float().mean()), ms[n // 2], ms[0],
                       float(out['g_texels'].double().norm()), float(out['g_texels'].double().sum()),
-                      float(out['g_w1'].double().norm()), err_max, err_l2))
+                      float(out['g_w1'].double().norm()), err_max, err_l2, ws_mb))
 
 
 if __name__ == '__main__':
