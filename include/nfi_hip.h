@@ -406,6 +406,18 @@ typedef struct nfi_sdf_gradient_args {
 } nfi_sdf_gradient_args;
 int nfi_sdf_gradient_fwd(const nfi_sdf_gradient_args* a, nfi_stream_t stream);
 int nfi_sdf_gradient_bwd(const nfi_sdf_gradient_args* a, nfi_stream_t stream);
+/* nfi_sdf_gradient_bwd with every output bit-identical from launch to launch (same arguments, device and build): the
+ * same per-contribution arithmetic, summed in a fixed order instead of by float atomics.  The reference's double backward
+ * (lib/ops.py:58-120 under models/generator.py:534-540) sums with index_put / scatter atomics and makes no such promise;
+ * this is the regulariser's share of nfi_field_bwd_args.scatter_mode = 2.  Same arguments, NULL-upstream rules and
+ * ACCUMULATE contract as nfi_sdf_gradient_bwd (rows 1.. of g_w2 / g_b2 untouched).  No allocation, no synchronisation:
+ * all scratch is `workspace` (device memory, 256-byte aligned), which need not be zeroed and holds, per point, two
+ * gradient rows (2 x 128 B), a flag (1 B) and two sort keys per plane (2 x 3 x 8 B), plus the sort's digit counts and, per
+ * wave of the backward's grid, one slot of 2 192 floats (8 768 B).  Refused: a NULL or too-small workspace, both upstream
+ * gradients NULL, points_per_scene above 2^25 (the limit of nfi_field_query_bwd's ordered mode: 32-bit point indices in
+ * the keys).  nfi_sdf_gradient_bwd_ordered_workspace_bytes returns 0 for a shape the call would refuse. */
+size_t nfi_sdf_gradient_bwd_ordered_workspace_bytes(const nfi_sdf_gradient_args* a);
+int nfi_sdf_gradient_bwd_ordered(const nfi_sdf_gradient_args* a, void* workspace, size_t workspace_bytes, nfi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fused forward render: run.py::render (176-350) from cameras + texels to pixels in one

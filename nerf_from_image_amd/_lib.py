@@ -121,10 +121,13 @@ def make_args(struct_name, **kw):
     return s
 
 
-def call_struct(fname, struct_name, stream, **kw):
+def call_struct(fname, struct_name, stream, *extra, **kw):
+    """int f(const struct*, [extra...,] stream): `extra` are the entry's arguments between the struct and the stream
+    (a tensor stands for its device pointer)."""
     lib = load()
     a = make_args(struct_name, **kw)
-    check(getattr(lib, fname)(ctypes.byref(a), ctypes.c_void_p(stream)), fname)
+    extra = [ptr(v) if hasattr(v, 'data_ptr') else v for v in extra]
+    check(getattr(lib, fname)(ctypes.byref(a), *extra, ctypes.c_void_p(stream)), fname)
 
 
 def struct_query(fname, struct_name, **kw):

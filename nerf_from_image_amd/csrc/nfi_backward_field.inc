@@ -1654,6 +1654,35 @@ __global__ __launch_bounds__(64) void ord_scatter_kernel(OrdParams k) {
   }
 }
 
+// The sort as the two translation units call it (declared in nfi_host.hpp; the regulariser's ordered backward is the other
+// user): `segments` runs of P keys each, sorted by cell with `passes` stable 8-bit passes - as many as the cell index
+// res * res - 1 has digits.  keys / spare: [segments][P]; hist: plan.hist_bytes.  Returns the array that holds the result.
+OrdSortPlan ord_sort_plan(int64_t P, int segments, int res) {
+  OrdSortPlan plan;
+  plan.blocks = (int)((P + kOrdTile - 1) / kOrdTile);
+  int bits = 1;
+  while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)res * res) ++bits;
+  plan.passes = (bits + 7) / 8;
+  plan.hist_bytes = (size_t)segments * kOrdDigits * plan.blocks * sizeof(uint32_t);
+  return plan;
+}
+
+uint64_t* ord_sort_by_cell(uint64_t* keys, uint64_t* spare, uint32_t* hist, int64_t P, int segments, int res, hipStream_t s) {
+  const OrdSortPlan plan = ord_sort_plan(P, segments, res);
+  OrdParams op;
+  memset(&op, 0, sizeof(op));
+  op.P = P; op.keys_in = keys; op.keys_out = spare; op.hist = hist; op.nblk = plan.blocks;
+  const dim3 sgrid((unsigned)plan.blocks, (unsigned)segments);
+  for (int pass = 0; pass < plan.passes; ++pass) {
+    op.shift = 8 * pass;
+    hipLaunchKernelGGL(ord_hist_kernel, sgrid, dim3(64), 0, s, op);
+    hipLaunchKernelGGL(ord_scan_kernel, dim3((unsigned)segments), dim3(256), 0, s, op);
+    hipLaunchKernelGGL(ord_scatter_kernel, sgrid, dim3(64), 0, s, op);
+    std::swap(op.keys_in, op.keys_out);
+  }
+  return op.keys_in;
+}
+
 __device__ __forceinline__ int64_t ord_lower_bound(const uint64_t* keys, int64_t n, uint64_t v) {
   int64_t lo = 0, hi = n;
   while (lo < hi) {
@@ -1786,7 +1815,7 @@ struct FieldBwdCarve {
   int groups, tile, tps;             // binned scatter: point groups per scene, tile side, tiles per plane side
   size_t nb, max_items;              // buckets over all scenes, upper bound of the work items
   size_t gf, entries, counts, items, flag, total;
-  int sort_blocks, sort_passes;      // ordered: sort blocks per (scene, plane) segment, 8-bit radix passes over the cell index
+  int sort_blocks;                   // ordered: sort blocks per (scene, plane) segment (ord_sort_plan)
   size_t keys[2], hist, slots, slot_bytes;
 };
 
@@ -1824,15 +1853,13 @@ static FieldBwdCarve field_bwd_carve(const nfi_field_bwd_args* a) {
   }
   if (c.ordered) {
     const size_t n_pts = (size_t)a->n_scenes * (size_t)a->points_per_scene;
-    c.sort_blocks = (int)((a->points_per_scene + kOrdTile - 1) / kOrdTile);
-    int bits = 1;
-    while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)a->plane_res * a->plane_res) ++bits;
-    c.sort_passes = (bits + 7) / 8;
+    const OrdSortPlan plan = ord_sort_plan(a->points_per_scene, a->n_scenes * 3, a->plane_res);
+    c.sort_blocks = plan.blocks;
     c.gf = at; at += align256(n_pts * kC * sizeof(float));
     c.flag = at; at += align256(n_pts);
     c.keys[0] = at; at += align256(3 * n_pts * sizeof(uint64_t));
     c.keys[1] = at; at += align256(3 * n_pts * sizeof(uint64_t));
-    c.hist = at; at += align256((size_t)a->n_scenes * 3 * kOrdDigits * c.sort_blocks * sizeof(uint32_t));
+    c.hist = at; at += align256(plan.hist_bytes);
     c.slot_bytes = (size_t)a->n_scenes * (size_t)field_bwd_blocks(a) * 4 * kSlotFloats * sizeof(float);
     c.slots = at; at += align256(c.slot_bytes);
   }
@@ -1995,16 +2022,9 @@ extern "C" int nfi_field_query_bwd(const nfi_field_bwd_args* a, nfi_stream_t str
     const FinishParams fp{reinterpret_cast<const float*>(w + ws.slots), (int)blocks * 4, a->n_scenes, a->n_attention, n_out, a->use_sdf,
                           a->g_w1, a->g_b1, a->g_w2, a->g_b2, a->g_attention_values, a->g_beta, a->g_alpha};
     hipLaunchKernelGGL(param_finish_kernel, dim3(kSlotFloats / 16), dim3(256), 0, s, fp);
-    const dim3 sgrid((unsigned)ws.sort_blocks, (unsigned)(a->n_scenes * 3));
     op.keys_in = reinterpret_cast<uint64_t*>(w + ws.keys[0]); op.keys_out = reinterpret_cast<uint64_t*>(w + ws.keys[1]);
     hipLaunchKernelGGL(ord_keys_kernel, dim3((unsigned)((a->points_per_scene + 255) / 256), (unsigned)a->n_scenes), dim3(256), 0, s, op);
-    for (int pass = 0; pass < ws.sort_passes; ++pass) {
-      op.shift = 8 * pass;
-      hipLaunchKernelGGL(ord_hist_kernel, sgrid, dim3(64), 0, s, op);
-      hipLaunchKernelGGL(ord_scan_kernel, dim3((unsigned)(a->n_scenes * 3)), dim3(256), 0, s, op);
-      hipLaunchKernelGGL(ord_scatter_kernel, sgrid, dim3(64), 0, s, op);
-      std::swap(op.keys_in, op.keys_out);
-    }
+    op.keys_in = ord_sort_by_cell(op.keys_in, op.keys_out, op.hist, a->points_per_scene, a->n_scenes * 3, a->plane_res, s);
     const int64_t half_waves = (int64_t)a->n_scenes * 3 * a->plane_res * a->plane_res;
     hipLaunchKernelGGL(ord_gather_kernel, dim3((unsigned)((half_waves + 7) / 8)), dim3(256), 0, s, op);
   }

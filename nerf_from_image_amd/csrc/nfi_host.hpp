@@ -102,6 +102,11 @@ static inline int check_field_common(const void* texels, int plane_res, int texe
   return NFI_OK;
 }
 
+// The ordered modes' sort (defined in nfi_backward_field.inc, also called by nfi_regulariser.inc): a stable 8-bit radix sort
+// of 64-bit keys (cell << 32 | point) by cell, `segments` runs of P keys each.  Enqueues on `s`, allocates nothing.
+struct OrdSortPlan { int blocks, passes; size_t hist_bytes; };      // sort blocks per segment, passes, bytes of `hist`
+OrdSortPlan ord_sort_plan(int64_t P, int segments, int res);
+uint64_t* ord_sort_by_cell(uint64_t* keys, uint64_t* spare, uint32_t* hist, int64_t P, int segments, int res, hipStream_t s);
 
 namespace nfi {
 

@@ -31,6 +31,11 @@ struct SdfGradParams {
   const float* gd; const float* gg;                                          // backward: upstream gradients
   float* g_texels; float* g_w1; float* g_b1; float* g_w2; float* g_b2;
   int layout;                  // texel layout (nfi_device.hpp): strides below, in floats
+  // ordered backward only (nfi_sdf_gradient_bwd_ordered): regions of its workspace
+  float* ord_df; float* ord_v;         // [scene][point][32]: a point's df row (W1'^T dh) and v row (W1'^T (sg w2'))
+  uint8_t* ord_flag;                   // [scene][point]: 1 = the rows are written and count
+  float* ord_slots;                    // [wave slot][kRgSlotFloats]: a wave's weight-gradient sums
+  const uint64_t* ord_keys;            // [scene * 3 + plane][point]: (cell << 32 | point), sorted by cell for the gather
   __device__ __forceinline__ size_t pix_f() const { return layout ? 3 * kC : kC; }
   __device__ __forceinline__ size_t plane_f() const { return layout ? (size_t)kC : (size_t)res * res * kC; }
 };
@@ -245,6 +250,13 @@ __global__ __launch_bounds__(256, 2) void sdf_gradient_fwd_kernel(SdfGradParams 
 #define NFI_REG_OCC 1                      // workgroups per CU of the regulariser backward (2: 256 VGPRs with 96 B of scratch)
 #endif
 
+// a wave's slot of the ordered variant (floats): g_w1 [64][32], g_b1 [64], g_w2 row 0 [64], g_b2 [1], padded to 16
+constexpr int kRgSlotW1 = 0, kRgSlotB1 = 2048, kRgSlotW2 = 2112, kRgSlotB2 = 2176, kRgSlotFloats = 2192;
+
+// ORDERED (nfi_sdf_gradient_bwd_ordered, the scheme of nfi_backward_field.inc's ordered mode): no atomic at all - the
+// plane-gradient loop is replaced by a coalesced store of the tile's df and v rows (and a live flag per point) for
+// sdf_ord_gather_kernel, and the flush writes the wave's sums into its own slot for sdf_slot_finish_kernel.
+template <bool ORDERED>
 __global__ __launch_bounds__(256, NFI_REG_OCC) void sdf_gradient_bwd_kernel(SdfGradParams k) {
   extern __shared__ __attribute__((aligned(16))) float dyn[];
   typedef unsigned long long u64;
@@ -285,6 +297,7 @@ __global__ __launch_bounds__(256, NFI_REG_OCC) void sdf_gradient_bwd_kernel(SdfG
     float u[3] = {0.0f, 0.0f, 0.0f};
     if (valid && k.gg) { u[0] = k.gg[gi * 3] * scale; u[1] = k.gg[gi * 3 + 1] * scale; u[2] = k.gg[gi * 3 + 2] * scale; }
     db2 += dd;
+    if constexpr (ORDERED) { if (valid) k.ord_flag[gi] = 1; }        // (every point below P is live: none is skipped)
     const int xi = (int)((uint32_t)i0[0] | ((uint32_t)i0[1] << 10) | ((uint32_t)i0[2] << 20));
     const uint64_t live = __ballot(valid);
 #pragma unroll 1
@@ -496,6 +509,17 @@ __global__ __launch_bounds__(256, NFI_REG_OCC) void sdf_gradient_bwd_kernel(SdfG
         *reinterpret_cast<f32x4*>(vr + j * 36 + 16 + 4 * g) = v1 * s_inv;
         wave_lds_fence();
         const int lc = lane & 31, lh = lane >> 5;
+        if constexpr (ORDERED) {
+          // two points per instruction, lane = channel: 2 x 128 B per point and row set
+#pragma unroll 1
+          for (int pt = lh; pt < 16; pt += 2) {
+            const int src = 16 * t + pt;
+            if (!((live >> src) & 1ull)) continue;
+            const size_t row = ((size_t)scene * k.P + (size_t)(chunk * 64 + src)) * kC + lc;
+            k.ord_df[row] = dfr[pt * 36 + lc];
+            k.ord_v[row] = vr[pt * 36 + lc];
+          }
+        } else {
 #pragma unroll 1
         for (int pt = 0; pt < 16; ++pt) {
           const int src = 16 * t + pt;
@@ -522,26 +546,166 @@ __global__ __launch_bounds__(256, NFI_REG_OCC) void sdf_gradient_bwd_kernel(SdfG
             unsafeAtomicAdd(base + row_f, third * (w_y1 * gv + j_y1 * vv));
           }
         }
+        }
       }
       wave_lds_fence();
     }
   }
   // ---------------- flush ----------------
   const float un = (es == 0) ? 1.0f : bits2f((uint32_t)(254 - es) << 23);
+  if constexpr (ORDERED) {
+    // plain stores into this wave's slot, every element of it (a wave without a chunk writes zeros): nothing to pre-zero
+    float* slot = k.ord_slots + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * kRgSlotFloats;
 #pragma unroll
-  for (int nt = 0; nt < 4; ++nt)
+    for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * 32 + j], dW1[nt][0][r] * (gain1 * un));
-      atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * 32 + 16 + j], dW1[nt][1][r] * (gain1 * un));
-      const float b = row_allreduce_sum(db1a[nt][r]), w = row_allreduce_sum(dw2a[nt][r]);     // over the 16 point columns
-      if (j == 0) {
-        atomicAdd(&k.g_b1[16 * nt + 4 * g + r], b);
-        atomicAdd(&k.g_w2[16 * nt + 4 * g + r], w * gain2);
+      for (int r = 0; r < 4; ++r) {
+        slot[kRgSlotW1 + (16 * nt + 4 * g + r) * 32 + j] = dW1[nt][0][r] * (gain1 * un);
+        slot[kRgSlotW1 + (16 * nt + 4 * g + r) * 32 + 16 + j] = dW1[nt][1][r] * (gain1 * un);
+        const float b = row_allreduce_sum(db1a[nt][r]), w = row_allreduce_sum(dw2a[nt][r]);
+        if (j == 0) {
+          slot[kRgSlotB1 + 16 * nt + 4 * g + r] = b;
+          slot[kRgSlotW2 + 16 * nt + 4 * g + r] = w * gain2;
+        }
       }
+    db2 = wave_sum(db2);
+    if (lane < 16) slot[kRgSlotB2 + lane] = lane == 0 ? db2 : 0.0f;
+  } else {
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * 32 + j], dW1[nt][0][r] * (gain1 * un));
+        atomicAdd(&k.g_w1[(16 * nt + 4 * g + r) * 32 + 16 + j], dW1[nt][1][r] * (gain1 * un));
+        const float b = row_allreduce_sum(db1a[nt][r]), w = row_allreduce_sum(dw2a[nt][r]);     // over the 16 point columns
+        if (j == 0) {
+          atomicAdd(&k.g_b1[16 * nt + 4 * g + r], b);
+          atomicAdd(&k.g_w2[16 * nt + 4 * g + r], w * gain2);
+        }
+      }
+    db2 = wave_sum(db2);
+    if (lane == 0) atomicAdd(&k.g_b2[0], db2);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The ordered backward's other kernels.  Keys: one (cell << 32 | point) per point and plane, the cell from reg_coord - the
+// backward kernel's own arithmetic, so key and kernel agree on the cell of a point that sits on a texel node.  The sort is
+// the field backward's (ord_sort_by_cell).  Gather: one half-wave per texel and plane sums what the atomic loop above
+// would have added to that texel, in a fixed order, and adds it to g_texels: one writer per texel.
+// ------------------------------------------------------------------------------------------------
+// grid (ceil(P / 256), scenes): thread = point
+__global__ __launch_bounds__(256) void sdf_ord_keys_kernel(SdfGradParams k, uint64_t* keys) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= k.P) return;
+  const int scene = blockIdx.y;
+  const float* pt = k.points + ((size_t)scene * k.P + p) * 3;
+  int i0[3];
+  float fr;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) reg_coord(pt[a], k.scene_range, k.res, i0[a], fr);
+#pragma unroll
+  for (int pl = 0; pl < 3; ++pl) {
+    const int ia = i0[(pl == 2) ? 1 : 0], ib = i0[(pl == 0) ? 1 : 2];
+    keys[(size_t)(scene * 3 + pl) * k.P + p] = ((uint64_t)(uint32_t)(ib * k.res + ia) << 32) | (uint64_t)p;
+  }
+}
+
+// grid (ceil(scenes * 3 * res^2 / 8)), 256 threads: one half-wave per texel and plane, lane = channel.  The up to four cells
+// that touch the texel in ascending cell order (lanes 0..7 find the cells' runs: one binary search each, side by side), a
+// run in ascending point order in blocks of 32 entries: lane e works out entry e's corner weight w and Jacobian coefficient
+// j with the atomic loop's expressions, every lane then adds third * (w * df[c] + j * v[c]) entry by entry; the blocks'
+// sums are added in index order.
+__global__ __launch_bounds__(256) void sdf_ord_gather_kernel(SdfGradParams k) {
+  const int l32 = threadIdx.x & 31;
+  const int64_t h = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
+  const int rr = k.res * k.res;
+  if (h >= (int64_t)k.n_scenes * 3 * rr) return;
+  const int seg = (int)(h / rr), tex = (int)(h - (int64_t)seg * rr);
+  const int scene = seg / 3, pl = seg - scene * 3;
+  const int b = tex / k.res, a = tex - b * k.res;
+  const int aa = (pl == 2) ? 1 : 0, ab = (pl == 0) ? 1 : 2;
+  const uint64_t* keys = k.ord_keys + (size_t)seg * k.P;
+  const size_t first = (size_t)scene * k.P;
+  const float scale = (float)(k.res - 1) / (2.0f * k.scene_range);
+  const float third = 1.0f / 3.0f;
+  // lane 2c: where cell c's run begins, lane 2c + 1: where it ends (a cell outside the plane: an empty run)
+  int bound = 0;
+  if (l32 < 8) {
+    const int c = l32 >> 1, ia = a - 1 + (c & 1), ib = b - 1 + (c >> 1);
+    if (ia >= 0 && ib >= 0 && ia <= k.res - 2 && ib <= k.res - 2) {
+      const uint64_t v = (uint64_t)((uint32_t)(ib * k.res + ia) + (uint32_t)(l32 & 1)) << 32;
+      int64_t lo = 0, hi = k.P;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (keys[mid] < v) lo = mid + 1; else hi = mid;
+      }
+      bound = (int)lo;                        // P <= 2^25
     }
-  db2 = wave_sum(db2);
-  if (lane == 0) atomicAdd(&k.g_b2[0], db2);
+  }
+  float total = 0.0f;
+  bool any = false;
+#pragma unroll 1
+  for (int c = 0; c < 4; ++c) {                       // cells (a-1,b-1), (a,b-1), (a-1,b), (a,b): ascending cell index
+    const int lo = __shfl(bound, 2 * c, 32), hi = __shfl(bound, 2 * c + 1, 32);
+    const bool right = !(c & 1), upper = !(c >> 1);   // which corner of the cell this texel is
+#pragma unroll 1
+    for (int base = lo; base < hi; base += 32) {
+      const int i = base + l32;
+      uint32_t pt = 0u;
+      float w = 0.0f, jc = 0.0f;
+      bool live = false;
+      if (i < hi) {
+        pt = (uint32_t)keys[i];
+        live = (int64_t)pt < k.P && k.ord_flag[first + pt] != 0;
+        if (live) {
+          const float* x = k.points + (first + pt) * 3;
+          int i0;
+          float fa, fb, ua = 0.0f, ub = 0.0f;
+          reg_coord(x[aa], k.scene_range, k.res, i0, fa);
+          reg_coord(x[ab], k.scene_range, k.res, i0, fb);
+          if (k.gg) { ua = k.gg[(first + pt) * 3 + aa] * scale; ub = k.gg[(first + pt) * 3 + ab] * scale; }
+          const float wx = right ? fa : 1.0f - fa, sx = right ? 1.0f : -1.0f;
+          if (upper) { w = wx * fb; jc = sx * fb * ua + wx * ub; }
+          else { w = wx * (1.0f - fb); jc = sx * (1.0f - fb) * ua - wx * ub; }
+        }
+      }
+      const int n = min(32, hi - base);
+      float part = 0.0f;
+#pragma unroll 4
+      for (int e = 0; e < n; ++e) {
+        if (!__shfl((int)live, e, 32)) continue;
+        const float we = __shfl(w, e, 32), je = __shfl(jc, e, 32);
+        const size_t row = (first + (uint32_t)__shfl((int)pt, e, 32)) * kC + l32;
+        part += third * (we * k.ord_df[row] + je * k.ord_v[row]);
+        any = true;
+      }
+      total += part;
+    }
+  }
+  if (!any) return;
+  float* dst = k.g_texels + (size_t)scene * 3 * rr * kC + (size_t)pl * k.plane_f() + (size_t)tex * k.pix_f() + l32;
+  *dst += total;
+}
+
+// grid (kRgSlotFloats / 16), 256 threads = 16 slot offsets x 16 parts: a part sums a contiguous range of slots in index
+// order, part 0 adds the 16 partial sums in part order to the caller's buffer (param_finish_kernel's scheme)
+__global__ __launch_bounds__(256) void sdf_slot_finish_kernel(SdfGradParams k, int n_slots) {
+  __shared__ float partial[16][16];
+  const int e = threadIdx.x & 15, part = threadIdx.x >> 4;
+  const int o = blockIdx.x * 16 + e;
+  const int s0 = (int)(((int64_t)n_slots * part) / 16), s1 = (int)(((int64_t)n_slots * (part + 1)) / 16);
+  float acc = 0.0f;
+  for (int s = s0; s < s1; ++s) acc += k.ord_slots[(size_t)s * kRgSlotFloats + o];
+  partial[part][e] = acc;
+  __syncthreads();
+  if (part != 0) return;
+  float t = 0.0f;
+  for (int q = 0; q < 16; ++q) t += partial[q][e];
+  if (o < kRgSlotB1) k.g_w1[o] += t;
+  else if (o < kRgSlotW2) k.g_b1[o - kRgSlotB1] += t;
+  else if (o < kRgSlotB2) k.g_w2[o - kRgSlotW2] += t;
+  else if (o == kRgSlotB2) k.g_b2[0] += t;
 }
 
 static int sdf_gradient_common(const nfi_sdf_gradient_args* a, SdfGradParams& k) {
@@ -571,23 +735,101 @@ extern "C" int nfi_sdf_gradient_fwd(const nfi_sdf_gradient_args* a, nfi_stream_t
   return check_launch("sdf_gradient_fwd");
 }
 
-extern "C" int nfi_sdf_gradient_bwd(const nfi_sdf_gradient_args* a, nfi_stream_t stream) {
-  SdfGradParams k;
+// blocks per scene of the backward's grid: one 64-point chunk per wave and turn; a resident set of blocks (1 per CU: 256+
+// registers): every wave flushes 2 177 sums at its end.  A function of (P, n_scenes) alone, which is what fixes the ordered
+// variant's slot order.
+static int64_t sdf_gradient_bwd_blocks(const nfi_sdf_gradient_args* a) {
+  const int64_t blocks = (a->points_per_scene + 255) / 256;
+  return std::min(blocks, std::max<int64_t>(16, 256 * NFI_REG_OCC / a->n_scenes));
+}
+
+// the backward's arguments and grid, for both entries
+static int sdf_gradient_bwd_common(const nfi_sdf_gradient_args* a, SdfGradParams& k, dim3& grid, const char* no_upstream) {
   int rc = sdf_gradient_common(a, k);
   if (rc) return rc;
-  REQUIRE(a->g_sdf || a->g_gradient, "sdf_gradient_bwd: no upstream gradient");
+  REQUIRE(a->g_sdf || a->g_gradient, no_upstream);
   REQUIRE(a->g_texels && a->g_w1 && a->g_b1 && a->g_w2 && a->g_b2, "sdf_gradient_bwd: output pointer missing");
   k.gd = a->g_sdf; k.gg = a->g_gradient;
   k.g_texels = a->g_texels; k.g_w1 = a->g_w1; k.g_b1 = a->g_b1; k.g_w2 = a->g_w2; k.g_b2 = a->g_b2;
-  // one 64-point chunk per wave; a resident set of blocks (1 per CU: 256+ registers): every wave flushes 2 177 atomics at its end
-  int64_t blocks = (a->points_per_scene + 255) / 256;
-  int64_t cap = 256 * NFI_REG_OCC / a->n_scenes;
-  if (cap < 16) cap = 16;
-  if (blocks > cap) blocks = cap;
-  dim3 grid((unsigned)blocks, (unsigned)a->n_scenes);
+  grid = dim3((unsigned)sdf_gradient_bwd_blocks(a), (unsigned)a->n_scenes);
+  return NFI_OK;
+}
+
+template <bool ORDERED>
+static int launch_sdf_gradient_bwd(dim3 grid, hipStream_t s, const SdfGradParams& k) {
   const size_t shmem = (size_t)kRgLdsFloats * sizeof(float);
-  rc = ensure_dynamic_lds<&sdf_gradient_bwd_kernel>(shmem, "sdf_gradient_bwd");
+  const int rc = ensure_dynamic_lds<&sdf_gradient_bwd_kernel<ORDERED>>(shmem, "sdf_gradient_bwd");
   if (rc) return rc;
-  hipLaunchKernelGGL(sdf_gradient_bwd_kernel, grid, dim3(256), shmem, (hipStream_t)stream, k);
+  hipLaunchKernelGGL(sdf_gradient_bwd_kernel<ORDERED>, grid, dim3(256), shmem, s, k);
+  return NFI_OK;
+}
+
+extern "C" int nfi_sdf_gradient_bwd(const nfi_sdf_gradient_args* a, nfi_stream_t stream) {
+  SdfGradParams k;
+  dim3 grid;
+  int rc = sdf_gradient_bwd_common(a, k, grid, "sdf_gradient_bwd: no upstream gradient");
+  if (rc) return rc;
+  rc = launch_sdf_gradient_bwd<false>(grid, (hipStream_t)stream, k);
+  if (rc) return rc;
   return check_launch("sdf_gradient_bwd");
+}
+
+// The workspace of one nfi_sdf_gradient_bwd_ordered call: byte offsets of its regions and the total
+struct SdfOrdCarve { size_t df, v, flag, keys[2], hist, slots, total; int n_slots; };
+
+static size_t sdf_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+static SdfOrdCarve sdf_ord_carve(const nfi_sdf_gradient_args* a) {
+  SdfOrdCarve c;
+  memset(&c, 0, sizeof(c));
+  const size_t n_pts = (size_t)a->n_scenes * (size_t)a->points_per_scene;
+  c.n_slots = (int)(sdf_gradient_bwd_blocks(a) * a->n_scenes * 4);
+  size_t at = 0;
+  c.df = at; at += sdf_align256(n_pts * kC * sizeof(float));
+  c.v = at; at += sdf_align256(n_pts * kC * sizeof(float));
+  c.flag = at; at += sdf_align256(n_pts);
+  c.keys[0] = at; at += sdf_align256(3 * n_pts * sizeof(uint64_t));
+  c.keys[1] = at; at += sdf_align256(3 * n_pts * sizeof(uint64_t));
+  c.hist = at; at += sdf_align256(ord_sort_plan(a->points_per_scene, a->n_scenes * 3, a->plane_res).hist_bytes);
+  c.slots = at; at += sdf_align256((size_t)c.n_slots * kRgSlotFloats * sizeof(float));
+  c.total = at;
+  return c;
+}
+
+static bool sdf_ord_shape_ok(const nfi_sdf_gradient_args* a) {
+  return a && a->n_scenes > 0 && a->points_per_scene > 0 && a->points_per_scene <= (int64_t)1 << 25 && a->plane_res >= 2 &&
+         a->plane_res <= 1024;
+}
+
+extern "C" size_t nfi_sdf_gradient_bwd_ordered_workspace_bytes(const nfi_sdf_gradient_args* a) {
+  return sdf_ord_shape_ok(a) ? sdf_ord_carve(a).total : 0;
+}
+
+extern "C" int nfi_sdf_gradient_bwd_ordered(const nfi_sdf_gradient_args* a, void* workspace, size_t workspace_bytes,
+                                            nfi_stream_t stream) {
+  SdfGradParams k;
+  dim3 grid;
+  int rc = sdf_gradient_bwd_common(a, k, grid, "sdf_gradient_bwd_ordered: no upstream gradient");
+  if (rc) return rc;
+  REQUIRE(a->points_per_scene <= (int64_t)1 << 25, "sdf_gradient_bwd_ordered: at most 2^25 points per scene (split the call)");
+  REQUIRE(workspace, "sdf_gradient_bwd_ordered: workspace missing");
+  const SdfOrdCarve ws = sdf_ord_carve(a);
+  REQUIRE(workspace_bytes >= ws.total, "sdf_gradient_bwd_ordered: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  char* const w = reinterpret_cast<char*>(workspace);
+  // nothing here is read before this call has written it (rows and flags of every point, every slot, keys, counts)
+  k.ord_df = reinterpret_cast<float*>(w + ws.df); k.ord_v = reinterpret_cast<float*>(w + ws.v);
+  k.ord_flag = reinterpret_cast<uint8_t*>(w + ws.flag);
+  k.ord_slots = reinterpret_cast<float*>(w + ws.slots);
+  rc = launch_sdf_gradient_bwd<true>(grid, s, k);
+  if (rc) return rc;
+  hipLaunchKernelGGL(sdf_slot_finish_kernel, dim3(kRgSlotFloats / 16), dim3(256), 0, s, k, ws.n_slots);
+  uint64_t* keys = reinterpret_cast<uint64_t*>(w + ws.keys[0]);
+  hipLaunchKernelGGL(sdf_ord_keys_kernel, dim3((unsigned)((a->points_per_scene + 255) / 256), (unsigned)a->n_scenes), dim3(256), 0, s,
+                     k, keys);
+  k.ord_keys = ord_sort_by_cell(keys, reinterpret_cast<uint64_t*>(w + ws.keys[1]), reinterpret_cast<uint32_t*>(w + ws.hist),
+                                a->points_per_scene, a->n_scenes * 3, a->plane_res, s);
+  const int64_t half_waves = (int64_t)a->n_scenes * 3 * a->plane_res * a->plane_res;
+  hipLaunchKernelGGL(sdf_ord_gather_kernel, dim3((unsigned)((half_waves + 7) / 8)), dim3(256), 0, s, k);
+  return check_launch("sdf_gradient_bwd_ordered");
 }

@@ -219,10 +219,11 @@ def sample_volume_stratified(batch_size, nstrata, scene_range, device=None):
     return ((cell + jitter) / n * 2 - 1).reshape(batch_size, n ** 3, 3) * scene_range
 
 
-def sdf_and_gradient(points, planes, decoder, scene_range, texel_cache=None):
+def sdf_and_gradient(points, planes, decoder, scene_range, texel_cache=None, deterministic_backward=False):
     """(sdf [B,P], d sdf / d points [B,P,3]) at fixed points as ONE autograd node (HIP forward + HIP backward): the
     gradient output replaces torch.autograd.grad(..., create_graph=True) of generator.py:534-540, its backward is the
-    double backward lib/ops.grid_sample2d exists for.  Differentiable w.r.t. planes and the decoder parameters."""
+    double backward lib/ops.grid_sample2d exists for.  Differentiable w.r.t. planes and the decoder parameters.
+    deterministic_backward=True: the backward is nfi_sdf_gradient_bwd_ordered (bit-identical from launch to launch)."""
     w1, b1, w2, b2 = decoder_parameters(decoder)
     pts = points.detach()
     texels = texels_of(planes, cache=texel_cache)
@@ -232,7 +233,8 @@ def sdf_and_gradient(points, planes, decoder, scene_range, texel_cache=None):
 
     def bwd(inputs, outputs, grads, needs):
         pl, a_w1, a_b1, a_w2, a_b2 = inputs
-        g = ops.sdf_gradient_bwd(pts, texels, a_w1, a_b1, a_w2, a_b2, scene_range, grads[0], grads[1])
+        g = ops.sdf_gradient_bwd(pts, texels, a_w1, a_b1, a_w2, a_b2, scene_range, grads[0], grads[1],
+                                 ordered=deterministic_backward)
         return (ops.texel_grad_to_planes(g['g_texels']) if needs[0] else None, g['g_w1'], g['g_b1'], g['g_w2'], g['g_b2'])
     return differentiable('sdf_gradient', fwd, planes, w1, b1, w2, b2, bwd=bwd)
 
@@ -244,7 +246,8 @@ def regulariser_outputs(self, planes, request_model_outputs, texel_cache=None):
     bins_in = sample_volume_stratified(planes.shape[0], 32, self.scene_range, device=planes.device)
     if 'sdf_eikonal_loss' in request_model_outputs:
         assert self.use_sdf and self.training
-    d, g = sdf_and_gradient(bins_in, planes, self.decoder, self.scene_range, texel_cache)
+    d, g = sdf_and_gradient(bins_in, planes, self.decoder, self.scene_range, texel_cache,
+                            deterministic_backward=getattr(self, 'nfi_deterministic_backward', False))
     if 'sdf_eikonal_loss' in request_model_outputs:
         out['sdf_eikonal_loss'] = ((g.norm(dim=-1) - 1) ** 2).flatten(1).mean(dim=1)
     if 'sdf_distance_loss' in request_model_outputs:
@@ -265,7 +268,7 @@ def regulariser_outputs(self, planes, request_model_outputs, texel_cache=None):
             smp = make_sampler(planes, dec, self.scene_range, n_att,
                                torch.zeros((planes.shape[0], max(n_att, 1), 3), device=planes.device),
                                self.use_sdf, self.beta if self.use_sdf else None, self.alpha if self.use_sdf else None,
-                               texel_cache=texel_cache)
+                               texel_cache=texel_cache, **_sampler_options(self))
             d_p = smp((coords_p * self.scene_range).detach(), ['sdf_distance'])['sdf_distance'][..., 0]
         if self.use_sdf:
             beta = self.beta
@@ -549,7 +552,11 @@ def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_hando
 
     deterministic_backward: the sampler closure's backward (the staged path) runs the field backward in its ordered mode
     (nfi_field_bwd_args.scatter_mode 2): bit-identical gradients from call to call, for the plain decoder; a use_viewdir
-    model's closure keeps its atomics.  The fused + stash node takes the render option of the same name.
+    model's closure keeps its atomics.  The regulariser branch follows the same switch (regulariser_outputs): its
+    distance-plus-gradient node runs nfi_sdf_gradient_bwd_ordered and the total-variation term's sampler the ordered field
+    backward (for a use_viewdir model too: that term queries the plain distance head), so every HIP node of a G step
+    returns bit-identical gradients.  The fused + stash node takes the render option of the same name.  Outside the mode:
+    the fused hand-off backward, affine_warp_bwd, the view-direction decoder and mapper, and the producer.
 
     hip_viewdir_mapper (use_viewdir models only, off by default): the per-ray trunk of model.viewdir_mapper (fc0 .. fc6,
     norm1 .. norm4; generator.py:223-239) runs as one HIP autograd node instead of its PyTorch modules, which are then

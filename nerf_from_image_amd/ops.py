@@ -605,9 +605,11 @@ def sdf_gradient_fwd(points, texels, w1, b1, w2, b2, scene_range):
     return sdf, grad
 
 
-def sdf_gradient_bwd(points, texels, w1, b1, w2, b2, scene_range, g_sdf, g_gradient):
+def sdf_gradient_bwd(points, texels, w1, b1, w2, b2, scene_range, g_sdf, g_gradient, ordered=False):
     """Backward (= the reference's double backward) of sdf_gradient_fwd.  Returns dict(g_texels, g_w1, g_b1, g_w2
-    [n_out,64] with row 0 filled, g_b2 [n_out] with entry 0 filled)."""
+    [n_out,64] with row 0 filled, g_b2 [n_out] with entry 0 filled).  ordered=True: nfi_sdf_gradient_bwd_ordered - the same
+    contributions summed in a fixed order, every output bit-identical from launch to launch (a workspace is allocated
+    per call)."""
     points = _f32c(points, 'points')
     B, P = points.shape[0], points.shape[1]
     dev = points.device
@@ -615,12 +617,20 @@ def sdf_gradient_bwd(points, texels, w1, b1, w2, b2, scene_range, g_sdf, g_gradi
     out = {'g_texels': torch.zeros_like(texels), 'g_w1': torch.zeros((64, 32), dtype=torch.float32, device=dev),
            'g_b1': torch.zeros((64,), dtype=torch.float32, device=dev), 'g_w2': torch.zeros_like(w2),
            'g_b2': torch.zeros_like(b2)}
+    args = dict(n_scenes=B, points_per_scene=P, points=points, texels=texels, plane_res=texel_res(texels),
+                texel_layout=texel_layout_of(texels), scene_range=float(scene_range),
+                w1=_f32c(w1, 'w1'), b1=_f32c(b1, 'b1'), w2=w2, b2=b2, g_sdf=_f32c(g_sdf, 'g_sdf'),
+                g_gradient=_f32c(g_gradient, 'g_gradient'), **out)
     with torch.cuda.device(dev):
-        _lib.call_struct('nfi_sdf_gradient_bwd', 'nfi_sdf_gradient_args', _stream(points), n_scenes=B, points_per_scene=P,
-                         points=points, texels=texels, plane_res=texel_res(texels), texel_layout=texel_layout_of(texels),
-                         scene_range=float(scene_range),
-                         w1=_f32c(w1, 'w1'), b1=_f32c(b1, 'b1'), w2=w2, b2=b2, g_sdf=_f32c(g_sdf, 'g_sdf'),
-                         g_gradient=_f32c(g_gradient, 'g_gradient'), **out)
+        if ordered:
+            n_ws = _lib.struct_query('nfi_sdf_gradient_bwd_ordered_workspace_bytes', 'nfi_sdf_gradient_args', **args)
+            if n_ws == 0:
+                raise RuntimeError('sdf_gradient_bwd(ordered=True): shape not supported (at most 2^25 points per scene): %s'
+                                   % ((B, P, texel_res(texels)),))
+            ws = torch.empty((n_ws,), dtype=torch.uint8, device=dev)
+            _lib.call_struct('nfi_sdf_gradient_bwd_ordered', 'nfi_sdf_gradient_args', _stream(points), ws, n_ws, **args)
+        else:
+            _lib.call_struct('nfi_sdf_gradient_bwd', 'nfi_sdf_gradient_args', _stream(points), **args)
     return out
 
 

@@ -1,6 +1,7 @@
 """Timing of the regulariser operator (sdf + spatial gradient and its double backward) at the size Generator.forward
 uses it: 4 scenes x 31^3 stratified points, 256^2 planes.   python tools/bench_regulariser.py [N]
-(NFI_PROBE_LIBRARY=<variant .so> selects a variant build; the backward call includes its 100 MB zero-fill of g_texels)"""
+(NFI_PROBE_LIBRARY=<variant .so> selects a variant build; the backward call includes its 100 MB zero-fill of g_texels;
+the last line is the ordered backward beside the atomic one)"""
 import os
 import sys
 
@@ -41,6 +42,14 @@ def main():
     print('%s: %d x %d^3 points: forward %.3f ms, backward %.3f ms (of which zero-fill %.3f)  sums %.6e %.6e %.6e %.6e' % (
         os.path.basename(_lib.LIBRARY), B, S, f_ms, b_ms, z_ms, float(sdf.double().sum()), float(grad.double().sum()),
         float(out['g_texels'].double().abs().sum()), float(out['g_w1'].double().abs().sum())))
+    # the ordered backward (nfi_sdf_gradient_bwd_ordered): the whole call, its workspace allocation included
+    o_ms, ordered = timeit(lambda: ops.sdf_gradient_bwd(pts, texels, w1, b1, w2, b2, 0.55, gd, gg, ordered=True))
+    again = ops.sdf_gradient_bwd(pts, texels, w1, b1, w2, b2, 0.55, gd, gg, ordered=True)
+    n_ws = _lib.struct_query('nfi_sdf_gradient_bwd_ordered_workspace_bytes', 'nfi_sdf_gradient_args', n_scenes=B,
+                             points_per_scene=S ** 3, plane_res=R)
+    worst = max(float((ordered[k] - out[k]).abs().max() / out[k].abs().max()) for k in ('g_texels', 'g_w1', 'g_b1', 'g_w2', 'g_b2'))
+    print('ordered backward %.3f ms (atomic %.3f), workspace %.1f MiB, repeat bit-identical: %s, worst output against the atomic '
+          'entry %.1e of its maximum' % (o_ms, b_ms, n_ws / 2 ** 20, all(torch.equal(again[k], ordered[k]) for k in ordered), worst))
 
 
 if __name__ == '__main__':
