@@ -598,6 +598,20 @@ typedef struct nfi_torgb_args {
 } nfi_torgb_args;
 int nfi_torgb_texels_fwd(const nfi_torgb_args* a, nfi_stream_t stream);
 int nfi_torgb_texels_bwd(const nfi_torgb_args* a, nfi_stream_t stream);
+/* nfi_torgb_texels_bwd with every output bit-identical from launch to launch for identical arguments on the same device
+ * and build: the same per-element arithmetic, summed in a fixed order instead of by float atomics (the reference's
+ * backward of models/stylegan.py:424-443 - conv2d / conv_transpose2d gradients and the add - makes no such promise unless
+ * MIOpen is held to its deterministic solvers).  Same arguments, shapes and WRITE semantics as nfi_torgb_texels_bwd;
+ * g_x and g_previous_image carry the bits of that call (they have one writer per element there too).  g_styles: each wave
+ * of the data kernel stores its sums to a slot (scene, block, wave) and a finish kernel adds the slots in index order;
+ * g_weight / g_bias: the four waves of a block are combined in wave order, each block of the shape-determined grid
+ * (min(ceil(B R^2 / 64), 256) x ceil(Cin / 64)) stores one partial and a finish kernel adds them in block order.  No
+ * allocation, no synchronisation: all scratch is `workspace` (device memory, 4-byte aligned), which need not be zeroed
+ * and holds 4 Cin floats per data block (1 024 pixels) and scene, and 96 x 64 (+ 96) floats per weight block.  Refused: a
+ * NULL or too-small workspace, and what nfi_torgb_texels_bwd refuses.  nfi_torgb_texels_bwd_ordered_workspace_bytes
+ * reads n_scenes, in_channels and resolution alone and returns 0 for a shape the call would refuse. */
+size_t nfi_torgb_texels_bwd_ordered_workspace_bytes(const nfi_torgb_args* a);
+int nfi_torgb_texels_bwd_ordered(const nfi_torgb_args* a, void* workspace, size_t workspace_bytes, nfi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Neighbours of the renderer in the inversion loop.
@@ -618,6 +632,15 @@ typedef struct nfi_warp_args {
 } nfi_warp_args;
 int nfi_affine_warp_fwd(const nfi_warp_args* a, nfi_stream_t stream);
 int nfi_affine_warp_bwd(const nfi_warp_args* a, nfi_stream_t stream);
+/* nfi_affine_warp_bwd with g_image bit-identical from launch to launch for identical arguments on the same device and
+ * build.  The reference's backward of run.py:745-766 is grid_sample's scatter of atomics, as nfi_affine_warp_bwd's is;
+ * here the adjoint is a gather: one thread per SOURCE pixel visits, in row-major order, the output pixels whose bilinear
+ * footprint can reach it (the inverse affine image of its 2 x 2 neighbourhood, widened for fp32 rounding, clipped to the
+ * image - never by a constant: a zoom-out of `scale` sends about 4 / scale^2 outputs to one pixel), recomputes the
+ * forward's sample position and weights for each, adds the ones that touch it and stores once.  Same arguments, shapes and
+ * WRITE semantics as nfi_affine_warp_bwd (white_background is accepted and does not enter the adjoint); no workspace,
+ * no allocation, no synchronisation. */
+int nfi_affine_warp_bwd_ordered(const nfi_warp_args* a, nfi_stream_t stream);
 
 /* Image metrics of the inversion / evaluation loops: lib/metrics.py psnr (30-45) and iou (79-94), per image.
  *   pred / target: n_images x elements_per_image values in [0,1] (any layout, identical for both) -> psnr [n_images]

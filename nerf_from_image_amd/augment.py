@@ -8,6 +8,7 @@ expressions.
 
     import nerf_from_image_amd.augment as nfi_aug
     nfi_aug.configure(args, dataset_config)        # reads dataset_config['white_background'], args.supervise_alpha
+                                                    # deterministic_backward=True: the warp's ordered backward
     augment = nfi_aug.augment                       # replaces run.py's own def
 """
 import numpy as np
@@ -18,11 +19,13 @@ from .autograd import differentiable
 
 args = None
 dataset_config = None
+deterministic_backward = False
 
 
-def configure(new_args, new_dataset_config):
-    global args, dataset_config
-    args, dataset_config = new_args, new_dataset_config
+def configure(new_args, new_dataset_config, deterministic_backward=False):
+    """deterministic_backward: augment_impl's image warp runs nfi_affine_warp_bwd_ordered in its backward (bit-identical
+    image gradients from call to call; the forward is the same launch either way)."""
+    globals().update(args=new_args, dataset_config=new_dataset_config, deterministic_backward=bool(deterministic_backward))
 
 
 def invert_space(mat):
@@ -38,16 +41,16 @@ def invert_space(mat):
     return torch.cat([top, bottom], dim=1)
 
 
-def warp_images(img, rot, scale, translation, white_background):
+def warp_images(img, rot, scale, translation, white_background, deterministic_backward=False):
     """The image branch of augment_impl (run.py:745-766) as one differentiable HIP op (gradient w.r.t. img only: the
-    transform parameters are random draws)."""
+    transform parameters are random draws).  deterministic_backward=True: the backward is nfi_affine_warp_bwd_ordered."""
     r, s, t = rot.detach(), None if scale is None else scale.detach(), translation.detach()
 
     def fwd(x):
         return ops.affine_warp(x, r, s, t, white_background)
 
     def bwd(inputs, out_meta, grads, needs):
-        return (ops.affine_warp_bwd(grads[0].contiguous(), r, s, t, white_background),)
+        return (ops.affine_warp_bwd(grads[0].contiguous(), r, s, t, white_background, ordered=deterministic_backward),)
     return differentiable('affine_warp', fwd, img, bwd=bwd)
 
 
@@ -114,7 +117,7 @@ def augment_impl(img, pose, focal, p, disable_scale=False, cached_tform=None):
         white = bool(dataset_config['white_background'])
         if white:
             assert not args.supervise_alpha
-        img_transformed = warp_images(img, rot, scale, translation, white)
+        img_transformed = warp_images(img, rot, scale, translation, white, deterministic_backward=deterministic_backward)
     else:
         img_transformed = None
 

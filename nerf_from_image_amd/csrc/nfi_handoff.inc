@@ -25,6 +25,10 @@
 //   torgb_bwd_data_kernel    t = W^T g (MFMA, same tiling);  g_x = s * t (NCHW, 16-byte stores);  g_s = sum_p x * t
 //   torgb_bwd_weight_kernel  g_W = sum_{b,p} g (s x)^T (MFMA with the pixels along K), g_bias = sum g
 //   upsample_bwd_kernel      g_prev = the adjoint of the stride-2 bilinear up-filter (a 4x4 gather per coarse pixel)
+// The two MFMA kernels sum g_s, g_W and g_bias with float atomics (LDS and global).  nfi_torgb_texels_bwd_ordered runs
+// ordered twins of the two: every partial sum goes to a workspace slot of its own - one per (scene, block, wave) for g_s,
+// one per block for g_W / g_bias, the block's four waves combined in wave order - and two finish kernels add the slots in
+// index order.  g_x and g_prev have one writer per element either way.
 
 struct TorgbParams {
   const float* x; const float* styles; const float* weight; const float* bias; const float* prev;
@@ -218,6 +222,99 @@ __global__ __launch_bounds__(256, 2) void torgb_bwd_data_kernel(TorgbParams k) {
   }
 }
 
+// torgb_bwd_data_kernel with g_s left to a finish kernel: the same statements (g_x is that kernel's, bit for bit), but each
+// wave STORES its row-reduced sums to slots[scene][block][wave][Cin] - zeros from a wave without pixels.  A kernel of its
+// own, not a template arm: sharing the body changed the instructions the default kernel compiles to.
+__global__ __launch_bounds__(256, 2) void torgb_bwd_data_ordered_kernel(TorgbParams k, float* slots) {
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  const int Cin = k.Cin, TK = Cin >> 4;                  // 16-row tiles of input channels
+  float* ldsA = dyn;                                     // [TK][6 s6][64 lanes][4 u]: W[16 s6 + 4 kk + u][16 tk + i]
+  float* ldsS = dyn + kTorgbOut * Cin;                   // [Cin] styles of this sample
+  const int b = blockIdx.y;
+  for (int i = threadIdx.x; i < kTorgbOut * Cin; i += blockDim.x) {
+    const int u = i & 3, lane = (i >> 2) & 63, rest = i >> 8;
+    const int s6 = rest % 6, tk = rest / 6;
+    ldsA[i] = k.weight[(16 * s6 + 4 * (lane >> 4) + u) * Cin + 16 * tk + (lane & 15)];
+  }
+  for (int i = threadIdx.x; i < Cin; i += blockDim.x) ldsS[i] = k.styles[(size_t)b * Cin + i];
+  __syncthreads();
+  const int lane = lane_id(), wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
+  const int R = k.R, P = R * R;
+  const f32x4* A4 = reinterpret_cast<const f32x4*>(ldsA);
+  const float* xb = k.x + (size_t)b * Cin * P;
+  float* gxb = k.g_x + (size_t)b * Cin * P;
+  float gs[8][4];                                        // per-lane partial of g_s[16 tk + 4g + r] (TK <= 8 per pass)
+  float* slot = slots + (((size_t)b * gridDim.x + blockIdx.x) * 4 + wave) * Cin;
+  for (int tk0 = 0; tk0 < TK; tk0 += 8) {
+    const int ntk = min(8, TK - tk0);
+#pragma unroll
+    for (int a = 0; a < 8; ++a) gs[a][0] = gs[a][1] = gs[a][2] = gs[a][3] = 0.0f;
+    for (int w = 0; w < kTorgbTilesPerWave; ++w) {
+      const int pix0 = ((blockIdx.x * 4 + wave) * kTorgbTilesPerWave + w) * 64;
+      if (pix0 >= P) break;
+      f32x4 acc[8][4];
+#pragma unroll
+      for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[a][n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      const float* gb = k.g_out + ((size_t)b * P + pix0 + 4 * j) * kTorgbOut + 4 * g;
+#pragma unroll 1
+      for (int s6 = 0; s6 < 6; ++s6) {
+        // B operand: lane (kk = g, j), tile n': g[pix0 + 4j + n'][16 s6 + 4 kk + u]
+        f32x4 gv[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) gv[n] = *reinterpret_cast<const f32x4*>(gb + (size_t)n * kTorgbOut + 16 * s6);
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+          if (a < ntk) {
+            const f32x4 wv = A4[((tk0 + a) * 6 + s6) * 64 + lane];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+              for (int n = 0; n < 4; ++n)
+                acc[a][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u], gv[n][u], acc[a][n], 0, 0, 0);
+          }
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < 8; ++a) {
+        if (a < ntk) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int kc = 16 * (tk0 + a) + 4 * g + r;
+            const size_t off = (size_t)kc * P + pix0 + 4 * j;
+            const f32x4 t4 = {acc[a][0][r], acc[a][1][r], acc[a][2][r], acc[a][3][r]};
+            const f32x4 x4 = *reinterpret_cast<const f32x4*>(xb + off);
+            *reinterpret_cast<f32x4*>(gxb + off) = t4 * ldsS[kc];
+            gs[a][r] += (x4[0] * t4[0] + x4[1] * t4[1]) + (x4[2] * t4[2] + x4[3] * t4[3]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+      if (a < ntk) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = row_allreduce_sum(gs[a][r]);
+          if (j == 0) slot[16 * (tk0 + a) + 4 * g + r] = v;
+        }
+      }
+    }
+  }
+}
+
+// g_styles[b][kc] = the sum of its n_slots = blocks x 4 wave slots, in (block, wave) order
+__global__ __launch_bounds__(256) void torgb_bwd_styles_finish_kernel(TorgbParams k, const float* slots, int n_slots) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k.B * k.Cin) return;
+  const int b = i / k.Cin, kc = i - b * k.Cin;
+  const float* p = slots + (size_t)b * n_slots * k.Cin + kc;
+  float v = 0.0f;
+  for (int s = 0; s < n_slots; ++s) v += p[(size_t)s * k.Cin];
+  k.g_styles[i] = v;
+}
+
 // g_W[o][k] = sum_{b,p} g[b,p,o] * s[b,k] * x[b,k,p]  (pixels along the MFMA K axis), g_bias[o] = sum g.
 // blockIdx.y picks a group of 4 input-channel tiles (64 channels): 96 x 64 accumulators per wave.
 __global__ __launch_bounds__(256, 2) void torgb_bwd_weight_kernel(TorgbParams k, int groups_per_image) {
@@ -283,6 +380,103 @@ __global__ __launch_bounds__(256, 2) void torgb_bwd_weight_kernel(TorgbParams k,
       const float v = sum_xor32(sum_xor16(bsum[t]));       // over the four pixel groups kk
       if (g == 0 && v != 0.0f) atomicAdd(&k.g_bias[16 * t + j], v);
     }
+  }
+}
+
+// torgb_bwd_weight_kernel without atomics: the same grid-stride accumulation, then the four waves add into red one after
+// the other (wave order, a barrier between them), their bias sums meet in red_bias[wave][96], and the block stores its
+// sums to part_w[tkg][block][96 x 64] / part_b[block][96] for torgb_bwd_weight_finish_kernel.
+__global__ __launch_bounds__(256, 2) void torgb_bwd_weight_ordered_kernel(TorgbParams k, int groups_per_image, float* part_w,
+                                                                          float* part_b) {
+  __shared__ float red[kTorgbOut * 64];                    // 24 KB + 1.5 KB: two blocks per CU, as the kernel above
+  __shared__ float red_bias[4 * kTorgbOut];
+  const int Cin = k.Cin, R = k.R, P = R * R;
+  const int lane = lane_id(), wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
+  const int tkg = blockIdx.y;                             // input channels [64 tkg, 64 tkg + 64)
+  const int ntk = min(4, (Cin >> 4) - 4 * tkg);
+  f32x4 acc[6][4];
+  float bsum[6];
+#pragma unroll
+  for (int t = 0; t < 6; ++t) {
+    bsum[t] = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) acc[t][a] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+  const int64_t n_groups = (int64_t)k.B * groups_per_image;              // groups of 16 pixels
+  for (int64_t grp = (int64_t)blockIdx.x * 4 + wave; grp < n_groups; grp += (int64_t)gridDim.x * 4) {
+    const int b = (int)(grp / groups_per_image);
+    const int pix0 = (int)(grp - (int64_t)b * groups_per_image) * 16;
+    // B operand of k-step u: lane (kk = g, j): s * x[b][16 tk + j][pix0 + 4 kk + u]
+    f32x4 xs[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      if (a < ntk) {
+        const int kc = 16 * (4 * tkg + a) + j;
+        xs[a] = *reinterpret_cast<const f32x4*>(k.x + ((size_t)b * Cin + kc) * P + pix0 + 4 * g) * k.styles[(size_t)b * Cin + kc];
+      } else {
+        xs[a] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      }
+    }
+    // A operand of k-step u: lane (kk = g, i = j): g[b][pix0 + 4 kk + u][16 t + i]
+    const float* gp = k.g_out + ((size_t)b * P + pix0 + 4 * g) * kTorgbOut + j;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      float av[6];
+#pragma unroll
+      for (int t = 0; t < 6; ++t) { av[t] = gp[(size_t)u * kTorgbOut + 16 * t]; bsum[t] += av[t]; }
+#pragma unroll
+      for (int t = 0; t < 6; ++t)
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+          acc[t][a] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t], xs[a][u], acc[t][a], 0, 0, 0);
+    }
+  }
+#pragma unroll 1
+  for (int turn = 0; turn < 4; ++turn) {
+    if (wave == turn) {
+#pragma unroll
+      for (int t = 0; t < 6; ++t)
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float* e = &red[(16 * t + 4 * g + r) * 64 + 16 * a + j];    // one lane of the wave per element
+            *e = turn == 0 ? acc[t][a][r] : *e + acc[t][a][r];
+          }
+    }
+    __syncthreads();
+  }
+  float* pw = part_w + ((size_t)tkg * gridDim.x + blockIdx.x) * (kTorgbOut * 64);
+  for (int i = threadIdx.x; i < kTorgbOut * 64; i += blockDim.x) pw[i] = red[i];
+  if (tkg == 0) {
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      const float v = sum_xor32(sum_xor16(bsum[t]));     // over the four pixel groups kk
+      if (g == 0) red_bias[wave * kTorgbOut + 16 * t + j] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kTorgbOut) {
+      const float* rb = red_bias + threadIdx.x;
+      part_b[(size_t)blockIdx.x * kTorgbOut + threadIdx.x] = ((rb[0] + rb[kTorgbOut]) + rb[2 * kTorgbOut]) + rb[3 * kTorgbOut];
+    }
+  }
+}
+
+// g_weight[o][kc] / g_bias[o] = the sum of the n_blocks block partials, in block order
+__global__ __launch_bounds__(256) void torgb_bwd_weight_finish_kernel(TorgbParams k, const float* part_w, const float* part_b,
+                                                                      int n_blocks) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < kTorgbOut * k.Cin) {
+    const int o = i / k.Cin, kc = i - o * k.Cin;
+    const float* p = part_w + (size_t)(kc >> 6) * n_blocks * (kTorgbOut * 64) + o * 64 + (kc & 63);
+    float v = 0.0f;
+    for (int s = 0; s < n_blocks; ++s) v += p[(size_t)s * (kTorgbOut * 64)];
+    k.g_weight[i] = v;
+  } else if (i < kTorgbOut * k.Cin + kTorgbOut) {
+    const int o = i - kTorgbOut * k.Cin;
+    float v = 0.0f;
+    for (int s = 0; s < n_blocks; ++s) v += part_b[(size_t)s * kTorgbOut + o];
+    k.g_bias[o] = v;
   }
 }
 
@@ -375,4 +569,74 @@ extern "C" int nfi_torgb_texels_bwd(const nfi_torgb_args* a, nfi_stream_t stream
     hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, k);
   }
   return check_launch("torgb_texels_bwd");
+}
+
+// The workspace of one nfi_torgb_texels_bwd_ordered call: byte offsets of its regions and the total
+struct TorgbOrdCarve { size_t slots, part_w, part_b, total; int data_blocks, weight_blocks, weight_groups; };
+
+static bool torgb_shape_ok(const nfi_torgb_args* a) {
+  return a && a->n_scenes > 0 && a->in_channels >= 16 && a->in_channels <= kTorgbMaxCin && a->in_channels % 16 == 0 &&
+         a->resolution >= 8 && a->resolution <= 1024 && a->resolution % 8 == 0;
+}
+
+static TorgbOrdCarve torgb_ord_carve(const nfi_torgb_args* a) {
+  auto align256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  TorgbOrdCarve c;
+  const int64_t P = (int64_t)a->resolution * a->resolution;
+  c.data_blocks = (int)((P + 64 * 4 * kTorgbTilesPerWave - 1) / (64 * 4 * kTorgbTilesPerWave));
+  c.weight_blocks = (int)std::min<int64_t>(((int64_t)a->n_scenes * (P / 16) + 3) / 4, 256);
+  c.weight_groups = (a->in_channels + 63) / 64;
+  size_t at = 0;
+  c.slots = at; at += align256((size_t)a->n_scenes * c.data_blocks * 4 * a->in_channels * sizeof(float));
+  c.part_w = at; at += align256((size_t)c.weight_groups * c.weight_blocks * kTorgbOut * 64 * sizeof(float));
+  c.part_b = at; at += align256((size_t)c.weight_blocks * kTorgbOut * sizeof(float));
+  c.total = at;
+  return c;
+}
+
+extern "C" size_t nfi_torgb_texels_bwd_ordered_workspace_bytes(const nfi_torgb_args* a) {
+  return torgb_shape_ok(a) ? torgb_ord_carve(a).total : 0;
+}
+
+extern "C" int nfi_torgb_texels_bwd_ordered(const nfi_torgb_args* a, void* workspace, size_t workspace_bytes, nfi_stream_t stream) {
+  TorgbParams k;
+  int rc = torgb_common(a, k);
+  if (rc) return rc;
+  REQUIRE(a->g_texels && a->g_x && a->g_styles, "torgb_texels_bwd_ordered: g_texels / g_x / g_styles missing");
+  REQUIRE(!a->g_previous_image || a->previous_image, "torgb_texels_bwd_ordered: g_previous_image without previous_image");
+  REQUIRE(!a->g_weight || a->g_bias, "torgb_texels_bwd_ordered: g_bias missing");
+  REQUIRE(workspace, "torgb_texels_bwd_ordered: workspace missing");
+  const TorgbOrdCarve ws = torgb_ord_carve(a);
+  REQUIRE(workspace_bytes >= ws.total, "torgb_texels_bwd_ordered: workspace too small");
+  k.g_out = a->g_texels; k.g_x = a->g_x; k.g_styles = a->g_styles; k.g_weight = a->g_weight; k.g_bias = a->g_bias;
+  k.g_prev = a->g_previous_image;
+  hipStream_t s = (hipStream_t)stream;
+  char* const w = reinterpret_cast<char*>(workspace);
+  // nothing here is read before this call has written it: every wave stores its slot, every block its partial
+  float* slots = reinterpret_cast<float*>(w + ws.slots);
+  float* part_w = reinterpret_cast<float*>(w + ws.part_w);
+  float* part_b = reinterpret_cast<float*>(w + ws.part_b);
+  const int P = k.R * k.R;
+  {
+    dim3 grid((unsigned)ws.data_blocks, (unsigned)k.B);
+    const size_t shmem = ((size_t)kTorgbOut * k.Cin + k.Cin) * sizeof(float);
+    rc = ensure_dynamic_lds<&torgb_bwd_data_ordered_kernel>(((size_t)kTorgbOut * kTorgbMaxCin + kTorgbMaxCin) * sizeof(float),
+                                                            "torgb_texels_bwd_ordered");
+    if (rc) return rc;
+    hipLaunchKernelGGL(torgb_bwd_data_ordered_kernel, grid, dim3(256), shmem, s, k, slots);
+    hipLaunchKernelGGL(torgb_bwd_styles_finish_kernel, dim3((unsigned)((k.B * k.Cin + 255) / 256)), dim3(256), 0, s, k, slots,
+                       ws.data_blocks * 4);
+  }
+  if (k.g_weight) {
+    dim3 grid((unsigned)ws.weight_blocks, (unsigned)ws.weight_groups);
+    hipLaunchKernelGGL(torgb_bwd_weight_ordered_kernel, grid, dim3(256), 0, s, k, P / 16, part_w, part_b);
+    hipLaunchKernelGGL(torgb_bwd_weight_finish_kernel, dim3((unsigned)((kTorgbOut * k.Cin + kTorgbOut + 255) / 256)), dim3(256), 0, s, k,
+                       part_w, part_b, ws.weight_blocks);
+  }
+  if (k.g_prev) {
+    const int half = k.R / 2;
+    const int64_t total = (int64_t)k.B * half * half * 24;
+    hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, k);
+  }
+  return check_launch("torgb_texels_bwd_ordered");
 }

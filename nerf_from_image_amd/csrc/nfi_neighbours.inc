@@ -93,6 +93,75 @@ __global__ __launch_bounds__(256) void affine_warp_kernel(WarpParams k) {
   }
 }
 
+// The adjoint as a gather (nfi_affine_warp_bwd_ordered): one thread per SOURCE pixel (n, sy, sx) is the only writer of
+// g_img there.  It walks, row-major, the output pixels whose bilinear footprint can reach it - the inverse affine image
+// of the source square [sx-1, sx+1] x [sy-1, sy+1], widened for fp32 rounding and clipped to the image - recomputes
+// warp_source for each (so the weights, clamped far-away samples included, are the forward's bits) and adds w * g where
+// one of the candidate's corners is this pixel.  The window only has to be a superset: membership is decided by the
+// recomputed (x0, y0).  It is bounded by the image alone (a strong zoom-out sends many outputs to one source pixel; a
+// singular or non-finite matrix gives the whole image).  No atomics, one store per element.
+constexpr int kWarpGatherChannels = 8;     // accumulators per pass over the window (C = 6 or 8 in the inversion loss)
+
+__global__ __launch_bounds__(256) void affine_warp_bwd_gather_kernel(WarpParams k) {
+  __shared__ float mat[6];
+  const int n = blockIdx.y;
+  if (threadIdx.x == 0) {
+    float a[3], b[3];
+    warp_matrix(k, n, a, b);
+    mat[0] = a[0]; mat[1] = a[1]; mat[2] = a[2]; mat[3] = b[0]; mat[4] = b[1]; mat[5] = b[2];
+  }
+  __syncthreads();
+  const float a[3] = {mat[0], mat[1], mat[2]}, b[3] = {mat[3], mat[4], mat[5]};
+  const int hw = k.H * k.W;
+  const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pix >= hw) return;
+  const int sy = pix / k.W, sx = pix - sy * k.W;
+  // inverse map, source position (ix, iy) -> output position (ox, oy), both in pixels
+  const float det = a[0] * b[1] - a[1] * b[0];
+  const float fW = (float)k.W, fH = (float)k.H;
+  float min_x = INFINITY, max_x = -INFINITY, min_y = INFINITY, max_y = -INFINITY;
+#pragma unroll
+  for (int corner = 0; corner < 4; ++corner) {
+    const float ix = (float)(sx + ((corner & 1) ? 1 : -1)), iy = (float)(sy + ((corner & 2) ? 1 : -1));
+    const float gx = (2.0f * ix + 1.0f) / fW - 1.0f - a[2], gy = (2.0f * iy + 1.0f) / fH - 1.0f - b[2];
+    const float xs = (b[1] * gx - a[1] * gy) / det, ys = (a[0] * gy - b[0] * gx) / det;
+    const float ox = ((xs + 1.0f) * fW - 1.0f) * 0.5f, oy = ((ys + 1.0f) * fH - 1.0f) * 0.5f;
+    // a NaN must widen the window, not be dropped by fminf / fmaxf
+    min_x = (ox == ox) ? fminf(min_x, ox) : -INFINITY; max_x = (ox == ox) ? fmaxf(max_x, ox) : INFINITY;
+    min_y = (oy == oy) ? fminf(min_y, oy) : -INFINITY; max_y = (oy == oy) ? fmaxf(max_y, oy) : INFINITY;
+  }
+  // rounding of the forward's (ix, iy) and of the inverse above: a few ulp of the largest intermediate, (|row| + 1) * size,
+  // seen through the inverse map (1 / sqrt(det) output pixels per source pixel); floorf / ceilf below round outwards
+  const float reach = fabsf(a[0]) + fabsf(a[1]) + fabsf(a[2]) + fabsf(b[0]) + fabsf(b[1]) + fabsf(b[2]) + 2.0f;
+  const float margin = 0.01f + 1e-5f * reach * fmaxf(fW, fH) * rsqrtf(det);        // NaN / inf -> whole image below
+  const int x_lo = (int)fminf(fmaxf(floorf(min_x - margin), 0.0f), fW), x_hi = (int)fmaxf(fminf(ceilf(max_x + margin), fW - 1.0f), -1.0f);
+  const int y_lo = (int)fminf(fmaxf(floorf(min_y - margin), 0.0f), fH), y_hi = (int)fmaxf(fminf(ceilf(max_y + margin), fH - 1.0f), -1.0f);
+  for (int c0 = 0; c0 < k.C; c0 += kWarpGatherChannels) {
+    const int nc = min(kWarpGatherChannels, k.C - c0);
+    const size_t plane0 = ((size_t)n * k.C + c0) * hw;
+    float acc[kWarpGatherChannels];
+#pragma unroll
+    for (int c = 0; c < kWarpGatherChannels; ++c) acc[c] = 0.0f;
+    for (int y = y_lo; y <= y_hi; ++y) {
+      for (int x = x_lo; x <= x_hi; ++x) {
+        int x0, y0;
+        float fx, fy;
+        warp_source(k, a, b, y, x, x0, y0, fx, fy);
+        const bool at_x0 = x0 == sx, at_y0 = y0 == sy;
+        if (!(at_x0 || x0 + 1 == sx) || !(at_y0 || y0 + 1 == sy)) continue;
+        const float w = (at_x0 ? 1.0f - fx : fx) * (at_y0 ? 1.0f - fy : fy);     // the forward's w00 / w10 / w01 / w11
+        const float* gp = k.g_out + plane0 + (size_t)y * k.W + x;
+#pragma unroll
+        for (int c = 0; c < kWarpGatherChannels; ++c)
+          if (c < nc) acc[c] += w * gp[(size_t)c * hw];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kWarpGatherChannels; ++c)
+      if (c < nc) k.g_img[plane0 + (size_t)c * hw + pix] = acc[c];
+  }
+}
+
 static int warp_common(const nfi_warp_args* a, WarpParams& k) {
   REQUIRE(a && a->rot && a->translation, "affine_warp: null pointer");
   REQUIRE(a->n_images > 0 && a->channels > 0 && a->height > 0 && a->width > 0, "affine_warp: bad shape");
@@ -126,6 +195,17 @@ extern "C" int nfi_affine_warp_bwd(const nfi_warp_args* a, nfi_stream_t stream) 
   dim3 grid((unsigned)((k.H * k.W + 255) / 256), (unsigned)k.N);
   hipLaunchKernelGGL(affine_warp_kernel<true>, grid, dim3(256), 0, s, k);
   return check_launch("affine_warp_bwd");
+}
+
+extern "C" int nfi_affine_warp_bwd_ordered(const nfi_warp_args* a, nfi_stream_t stream) {
+  WarpParams k;
+  int rc = warp_common(a, k);
+  if (rc) return rc;
+  REQUIRE(a->g_warped && a->g_image, "affine_warp_bwd_ordered: null gradient pointer");
+  k.g_out = a->g_warped; k.g_img = a->g_image;
+  dim3 grid((unsigned)((k.H * k.W + 255) / 256), (unsigned)k.N);
+  hipLaunchKernelGGL(affine_warp_bwd_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, k);
+  return check_launch("affine_warp_bwd_ordered");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -555,8 +555,11 @@ def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_hando
     model's closure keeps its atomics.  The regulariser branch follows the same switch (regulariser_outputs): its
     distance-plus-gradient node runs nfi_sdf_gradient_bwd_ordered and the total-variation term's sampler the ordered field
     backward (for a use_viewdir model too: that term queries the plain distance head), so every HIP node of a G step
-    returns bit-identical gradients.  The fused + stash node takes the render option of the same name.  Outside the mode:
-    the fused hand-off backward, affine_warp_bwd, the view-direction decoder and mapper, and the producer.
+    returns bit-identical gradients.  With fused_handoff the last block's fused tail follows it as well (its backward
+    is nfi_torgb_texels_bwd_ordered; the flag lives on the block, handoff.fuse_last_block, and a later attach() without the
+    option clears it while the block stays fused).  The fused + stash node takes the render option of the same name, and the
+    augmentation warp its own (augment.configure(..., deterministic_backward=True)).  Outside the mode: the
+    view-direction decoder and mapper, and the producer (PyTorch / MIOpen: torch.backends.cudnn.deterministic).
 
     hip_viewdir_mapper (use_viewdir models only, off by default): the per-ray trunk of model.viewdir_mapper (fc0 .. fc6,
     norm1 .. norm4; generator.py:223-239) runs as one HIP autograd node instead of its PyTorch modules, which are then
@@ -587,9 +590,9 @@ def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_hando
             getattr(model.viewdir_mapper.__dict__['forward'], '__func__', None) is _hip_mapper_forward:
         del model.viewdir_mapper.__dict__['forward']             # switched off again: the class's own forward
     model.nfi_hip_viewdir_mapper = bool(hip_viewdir_mapper)
-    if fused_handoff:
-        from . import handoff
-        handoff.fuse_last_block(model.synthesis_network)
+    from . import handoff
+    if fused_handoff or handoff.fused_block(model.synthesis_network) is not None:    # fused earlier: stays fused, follows the switch
+        handoff.fuse_last_block(model.synthesis_network, deterministic_backward=deterministic_backward)
     if type(model).forward is not torch.nn.Module.forward and not hasattr(model, '_nfi_original_forward'):
         model._nfi_original_forward = model.forward          # bound method of the reference class
         model.forward = types.MethodType(wrapped_forward, model)

@@ -15,6 +15,9 @@ is then differentiated AGAIN) runs the block's original PyTorch tail for that ca
 
     import nerf_from_image_amd.handoff as nfi_handoff
     nfi_handoff.fuse_last_block(model.synthesis_network)          # or attach(model, fused_handoff=True)
+
+``deterministic_backward=True`` (here, or on ``attach``) runs the node's backward as ``nfi_torgb_texels_bwd_ordered``: the
+style, weight and bias gradients summed in a fixed order instead of by float atomics, bit-identical from call to call.
 """
 import types
 
@@ -24,9 +27,10 @@ from . import ops
 from .autograd import differentiable
 
 
-def torgb_upsample_add(x, styles, weight, bias, previous_image):
+def torgb_upsample_add(x, styles, weight, bias, previous_image, deterministic_backward=False):
     """Differentiable fused tail: x [B,Cin,R,R], styles [B,Cin] (already times weight_gain), weight [96,Cin,1,1] or
-    [96,Cin], bias [96], previous_image [B,96,R/2,R/2] or None -> [B,96,R,R] channels-last."""
+    [96,Cin], bias [96], previous_image [B,96,R/2,R/2] or None -> [B,96,R,R] channels-last.
+    deterministic_backward=True: the backward is nfi_torgb_texels_bwd_ordered."""
     if (not x.is_cuda) or weight.shape[0] != 96 or x.shape[1] % 16 or x.shape[1] > 256 or x.shape[-1] % 8:
         raise RuntimeError('fused hand-off: needs a GPU tensor, 96 image channels, a multiple of 16 (<= 256) feature '
                            'channels and a resolution that is a multiple of 8; got x %s' % (tuple(x.shape),))
@@ -40,7 +44,7 @@ def torgb_upsample_add(x, styles, weight, bias, previous_image):
         a_x, a_s, a_w = inputs[0], inputs[1], inputs[2]
         prev = inputs[4] if has_prev else None
         g = ops.torgb_texels_bwd(grads[0], a_x, a_s, a_w, prev, want_weight=bool(needs[2] or needs[3]),
-                                 want_prev=has_prev and bool(needs[4]))
+                                 want_prev=has_prev and bool(needs[4]), ordered=deterministic_backward)
         out = (g['g_x'], g['g_styles'], g.get('g_weight'), g.get('g_bias'))
         return out + ((g.get('g_previous_image'),) if has_prev else ())
     args = (x, styles, w2, bias) + ((previous_image,) if has_prev else ())
@@ -57,7 +61,8 @@ def fused_block_forward(self, x, img, ws, **layer_kwargs):
     x = self.conv1(x, next(w_iter), **layer_kwargs)
     torgb = self.torgb
     styles = torgb.affine(next(w_iter)) * torgb.weight_gain               # OutputLayer.forward, stylegan.py:365
-    img = torgb_upsample_add(x, styles, torgb.weight, torgb.bias, img)
+    ordered = {'deterministic_backward': True} if getattr(self, 'nfi_deterministic_backward', False) else {}
+    img = torgb_upsample_add(x, styles, torgb.weight, torgb.bias, img, **ordered)
     return x, img
 
 
@@ -69,13 +74,25 @@ def last_block(synthesis_network):
     return blk
 
 
-def fuse_last_block(synthesis_network):
-    """Swaps the forward of the last synthesis block for ``fused_block_forward``.  Returns the block."""
+def fuse_last_block(synthesis_network, deterministic_backward=False):
+    """Swaps the forward of the last synthesis block for ``fused_block_forward``.  Returns the block.
+    deterministic_backward is stored on the block (``nfi_deterministic_backward``) and read by every forward: calling
+    this again on a fused block only changes the flag."""
     blk = last_block(synthesis_network)
     if not hasattr(blk, '_nfi_original_forward'):
         blk._nfi_original_forward = blk.forward
         blk.forward = types.MethodType(fused_block_forward, blk)
+    blk.nfi_deterministic_backward = bool(deterministic_backward)
     return blk
+
+
+def fused_block(synthesis_network):
+    """The last synthesis block if ``fuse_last_block`` has fused it, else None."""
+    try:
+        blk = last_block(synthesis_network)
+    except AttributeError:
+        return None
+    return blk if hasattr(blk, '_nfi_original_forward') else None
 
 
 class unfused:

@@ -758,12 +758,14 @@ def affine_warp(img, rot, scale, translation, white_background=False):
     return out
 
 
-def affine_warp_bwd(g_out, rot, scale, translation, white_background=False):
-    """Adjoint of affine_warp w.r.t. the image: g_out [N,C,H,W] -> g_img [N,C,H,W]."""
+def affine_warp_bwd(g_out, rot, scale, translation, white_background=False, ordered=False):
+    """Adjoint of affine_warp w.r.t. the image: g_out [N,C,H,W] -> g_img [N,C,H,W].  ordered=True:
+    nfi_affine_warp_bwd_ordered - a gather per source pixel instead of a scatter of atomics, bit-identical from launch to
+    launch."""
     g_out = _f32c(g_out, 'g_out')
     g_img = torch.empty_like(g_out)
     with torch.cuda.device(g_out.device):
-        _lib.call_struct('nfi_affine_warp_bwd', 'nfi_warp_args', _stream(g_out), g_warped=g_out, g_image=g_img,
+        _lib.call_struct('nfi_affine_warp_bwd_ordered' if ordered else 'nfi_affine_warp_bwd', 'nfi_warp_args', _stream(g_out), g_warped=g_out, g_image=g_img,
                          **_warp_args(g_out.shape, rot, scale, translation, white_background))
     return g_img
 
@@ -819,9 +821,10 @@ def torgb_texels(x, styles, weight, bias, previous_image=None):
     return out
 
 
-def torgb_texels_bwd(g_out, x, styles, weight, previous_image=None, want_weight=True, want_prev=True):
+def torgb_texels_bwd(g_out, x, styles, weight, previous_image=None, want_weight=True, want_prev=True, ordered=False):
     """Backward of torgb_texels.  g_out: [B,96,R,R] (any strides; brought to channels-last).  Returns dict(g_x, g_styles,
-    g_weight?, g_bias?, g_previous_image?)."""
+    g_weight?, g_bias?, g_previous_image?).  ordered=True: nfi_torgb_texels_bwd_ordered - the style, weight and bias sums
+    in a fixed order, every output bit-identical from launch to launch (a workspace is allocated per call)."""
     x, styles, weight = _f32c(x, 'x'), _f32c(styles, 'styles'), _f32c(weight, 'weight')
     prev = _f32c(previous_image, 'previous_image')
     B, Cin, R, _ = x.shape
@@ -835,9 +838,17 @@ def torgb_texels_bwd(g_out, x, styles, weight, previous_image=None, want_weight=
         out['g_bias'] = torch.empty((96,), dtype=torch.float32, device=dev)
     if want_prev and prev is not None:
         out['g_previous_image'] = torch.empty_like(prev)
+    args = dict(n_scenes=B, in_channels=Cin, resolution=R, x=x, styles=styles, weight=weight, previous_image=prev, g_texels=g,
+                **out)
     with torch.cuda.device(dev):
-        _lib.call_struct('nfi_torgb_texels_bwd', 'nfi_torgb_args', _stream(x), n_scenes=B, in_channels=Cin, resolution=R,
-                         x=x, styles=styles, weight=weight, previous_image=prev, g_texels=g, **out)
+        if ordered:
+            n_ws = _lib.struct_query('nfi_torgb_texels_bwd_ordered_workspace_bytes', 'nfi_torgb_args', **args)
+            if n_ws == 0:
+                raise RuntimeError('torgb_texels_bwd(ordered=True): shape not supported: %s' % ((B, Cin, R),))
+            ws = torch.empty((n_ws,), dtype=torch.uint8, device=dev)
+            _lib.call_struct('nfi_torgb_texels_bwd_ordered', 'nfi_torgb_args', _stream(x), ws, n_ws, **args)
+        else:
+            _lib.call_struct('nfi_torgb_texels_bwd', 'nfi_torgb_args', _stream(x), **args)
     return out
 
 

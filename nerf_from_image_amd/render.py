@@ -67,10 +67,11 @@ process-wide - the reference calls render from one thread per GPU):
                     nfi_raygen_bwd_ordered, for any views_per_scene and either force_no_cam_grad.  Slower (DESIGN.md section
                     6).  The forward, its outputs and every inference path ignore it.  A use_viewdir model that needs a
                     gradient raises NotImplementedError (its per-ray feature gradient is summed with atomics); the staged
-                    path's sampler closure and the regulariser branch (nfi_sdf_gradient_bwd_ordered) take their own switch,
-                    generator.attach(..., deterministic_backward=True); the producer, the fused hand-off backward,
-                    affine_warp_bwd and the view-direction decoder and mapper are outside it, and
-                    torch.use_deterministic_algorithms is not consulted.
+                    path's sampler closure, the regulariser branch (nfi_sdf_gradient_bwd_ordered) and the fused hand-off
+                    backward (nfi_torgb_texels_bwd_ordered) take their own switch, generator.attach(...,
+                    deterministic_backward=True), the augmentation warp (nfi_affine_warp_bwd_ordered) its own,
+                    augment.configure(..., deterministic_backward=True); the producer and the view-direction decoder and
+                    mapper are outside it, and torch.use_deterministic_algorithms is not consulted.
 
 ``render_views(fused, height, width, tform_cam2world, focal_length, depth_samples_per_ray, ...)`` renders from planes that
 exist already (``generator.bake(model, model_input)``, or any sampler's ``.fused``) without calling a model: cameras
