@@ -75,6 +75,22 @@ def _f32c(t, name):
     return t.contiguous()
 
 
+def _need(t, n, tail, name, where):
+    """Refuse (ValueError, before any launch) a tensor that does not hold n rows of trailing shape `tail`: the kernels index
+    by the shapes of depth / bins alone, so a shorter argument would be read past its end."""
+    tail = tuple(tail)
+    rows = 1
+    for d in t.shape[:t.dim() - len(tail)]:
+        rows *= d
+    if t.dim() < len(tail) or tuple(t.shape[t.dim() - len(tail):]) != tail or rows != n:
+        raise ValueError('%s: %s must be %d rows of %s, got %s' % (where, name, n, list(tail), list(t.shape)))
+
+
+def _need_rays(rd, n, where):
+    if rd.shape[-1] != 3 or rd.numel() != 3 * n:
+        raise ValueError('%s: ray_directions must hold %d rays of 3 components, got %s' % (where, n, list(rd.shape)))
+
+
 # --------------------------------------------------------------------------- #
 def planes_to_texels(planes, texel_dtype=TEXEL_F32):
     """planes [B,3,32,R,R] fp32 -> texels [B,3,R,R,32] (fp32 or bf16)."""
@@ -270,6 +286,8 @@ def ray_weights(sigma, ray_directions, depth):
     sigma, rd, depth = _f32c(sigma, 'sigma'), _f32c(ray_directions, 'ray_directions'), _f32c(depth, 'depth')
     S = depth.shape[-1]
     n = depth.numel() // S
+    _need(sigma, n, (S,), 'sigma', 'ray_weights')
+    _need_rays(rd, n, 'ray_weights')
     w = torch.empty_like(depth)
     with torch.cuda.device(depth.device):
         _lib.call_struct('nfi_ray_weights', 'nfi_weights_args', _stream(depth), n_rays=n, n_samples=S, sigma=sigma,
@@ -277,17 +295,25 @@ def ray_weights(sigma, ray_directions, depth):
     return w
 
 
-def _u_and_stride(u, n, k):
+def _u_and_stride(u, n, k, where='sample_pdf'):
     """u: [n,k] dense, or a stride-0 broadcast of one row."""
+    if u.shape[-1] != k:
+        raise ValueError('%s: u must have %d entries per ray, got %s' % (where, k, list(u.shape)))
     if u.dim() == 2 and u.stride(0) == 0 and u.stride(1) == 1:
         return u, 0
+    if u.numel() != n * k:
+        raise ValueError('%s: u must hold one row per ray ([%d,%d]) or broadcast one row with stride 0, got %s' % (
+            where, n, k, list(u.shape)))
     u = u.contiguous()
     return u, k
 
 
 def sample_pdf(bins, weights, u, want_inds=False, want_cdf=False):
     bins, weights = _f32c(bins, 'bins'), _f32c(weights, 'weights')
+    if bins.dim() != 2:
+        raise ValueError('sample_pdf: bins must be [n,M], got %s' % (list(bins.shape),))
     n, M = bins.shape
+    _need(weights, n, (M - 1,), 'weights', 'sample_pdf')
     K = u.shape[-1]
     u, stride = _u_and_stride(u, n, K)
     dev = bins.device
@@ -304,7 +330,11 @@ def resample(sigma, ray_directions, depth, u, want_taps=False):
     sigma, rd, depth = _f32c(sigma, 'sigma'), _f32c(ray_directions, 'ray_directions'), _f32c(depth, 'depth')
     S = depth.shape[-1]
     n = depth.numel() // S
-    u, stride = _u_and_stride(u.reshape(-1, S) if u.stride(0) != 0 else u, n, S)
+    _need(sigma, n, (S,), 'sigma', 'resample')
+    _need_rays(rd, n, 'resample')
+    if u.shape[-1] != S:
+        raise ValueError('resample: u must have %d entries per ray, got %s' % (S, list(u.shape)))
+    u, stride = _u_and_stride(u.reshape(-1, S) if u.stride(0) != 0 else u, n, S, 'resample')
     dev = depth.device
     fine = torch.empty((n, S), dtype=torch.float32, device=dev)
     taps = {}
@@ -319,12 +349,35 @@ def resample(sigma, ray_directions, depth, u, want_taps=False):
     return fine, taps
 
 
+def _check_lists(where, rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a, extra_b):
+    """The shape rules of composite / composite_bwd (ValueError before any launch): every per-sample argument follows its
+    depth list, both lists and the directions hold the same rays, an extra attribute comes for every list."""
+    na = depth_a.shape[-1]
+    n = depth_a.numel() // na
+    _need_rays(rd, n, where)
+    _need(sigma_a, n, (na,), 'sigma_a', where)
+    _need(rgb_a, n, (na, 3), 'rgb_a', where)
+    if depth_b is not None:
+        if sigma_b is None or rgb_b is None:
+            raise ValueError('%s: list b needs depth_b, sigma_b and rgb_b' % where)
+        nb = depth_b.shape[-1]
+        _need(depth_b, n, (nb,), 'depth_b', where)
+        _need(sigma_b, n, (nb,), 'sigma_b', where)
+        _need(rgb_b, n, (nb, 3), 'rgb_b', where)
+    if extra_a is not None:
+        _need(extra_a, n, (na, extra_a.shape[-1]), 'extra_a', where)
+        if depth_b is not None:
+            if extra_b is None:
+                raise ValueError('%s: extra_a comes with a list b, but extra_b is missing' % where)
+            _need(extra_b, n, (nb, extra_a.shape[-1]), 'extra_b', where)
+    return n
+
+
 def composite(ray_directions, depth_a, sigma_a, rgb_a, depth_b=None, sigma_b=None, rgb_b=None, extra_a=None,
               extra_b=None, white_background=True, want_taps=False):
     rd = _f32c(ray_directions, 'ray_directions')
     depth_a, sigma_a, rgb_a = _f32c(depth_a, 'depth'), _f32c(sigma_a, 'sigma'), _f32c(rgb_a, 'rgb')
     na = depth_a.shape[-1]
-    n = depth_a.numel() // na
     nb = 0
     if depth_b is not None:
         depth_b, sigma_b, rgb_b = _f32c(depth_b, 'depth_b'), _f32c(sigma_b, 'sigma_b'), _f32c(rgb_b, 'rgb_b')
@@ -333,7 +386,8 @@ def composite(ray_directions, depth_a, sigma_a, rgb_a, depth_b=None, sigma_b=Non
     if extra_a is not None:
         extra_a = _f32c(extra_a, 'extra_a')
         n_extra = extra_a.shape[-1]
-        extra_b = _f32c(extra_b, 'extra_b')
+        extra_b = _f32c(extra_b, 'extra_b') if nb else None
+    n = _check_lists('composite', rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a, extra_b if nb else None)
     dev = depth_a.device
     shape = depth_a.shape[:-1]
     rgb_map = torch.empty((*shape, 3), dtype=torch.float32, device=dev)
@@ -501,7 +555,7 @@ def render_fwd(cam2world, focal, height, width, num_samples, texels, decoder_ima
     if fine_sampling:
         if noise_fine is None:
             noise_fine = torch.linspace(0.0, 1.0, steps=S, dtype=torch.float32, device=dev).expand(n, S)
-        u, ustride = _u_and_stride(noise_fine if noise_fine.dim() == 2 else noise_fine.reshape(-1, S), n, S)
+        u, ustride = _u_and_stride(noise_fine if noise_fine.dim() == 2 else noise_fine.reshape(-1, S), n, S, 'render_fwd')
     else:
         u, ustride = None, 0
     if ray_features is not None:
@@ -673,15 +727,21 @@ def composite_bwd(ray_directions, depth_a, sigma_a, rgb_a, g_rgb_map, g_mask=Non
     rd = _f32c(ray_directions, 'ray_directions')
     depth_a, sigma_a, rgb_a = _f32c(depth_a, 'depth'), _f32c(sigma_a, 'sigma'), _f32c(rgb_a, 'rgb')
     na = depth_a.shape[-1]
-    n = depth_a.numel() // na
     nb = 0
     if depth_b is not None:
         depth_b, sigma_b, rgb_b = _f32c(depth_b, 'depth_b'), _f32c(sigma_b, 'sigma_b'), _f32c(rgb_b, 'rgb_b')
         nb = depth_b.shape[-1]
     n_extra = 0
     if extra_a is not None and g_extra_map is not None:
-        extra_a, extra_b = _f32c(extra_a, 'extra_a'), _f32c(extra_b, 'extra_b')
+        extra_a, extra_b = _f32c(extra_a, 'extra_a'), _f32c(extra_b, 'extra_b') if nb else None
         n_extra = extra_a.shape[-1]
+    n = _check_lists('composite_bwd', rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a if n_extra else None,
+                     extra_b if n_extra and nb else None)
+    _need(g_rgb_map, n, (3,), 'g_rgb_map', 'composite_bwd')
+    if g_mask is not None:
+        _need(g_mask, n, (), 'g_mask', 'composite_bwd')
+    if n_extra:
+        _need(g_extra_map, n, (n_extra,), 'g_extra_map', 'composite_bwd')
     out = dict(g_sigma_a=torch.empty_like(sigma_a), g_rgb_a=torch.empty_like(rgb_a))
     if nb:
         out.update(g_sigma_b=torch.empty_like(sigma_b), g_rgb_b=torch.empty_like(rgb_b))
