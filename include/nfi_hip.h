@@ -424,7 +424,8 @@ int nfi_sdf_gradient_bwd_ordered(const nfi_sdf_gradient_args* a, void* workspace
  * persistent launch (plus the ray set-up launch), no per-sample HBM round trips.
  * ------------------------------------------------------------------------------------------ */
 /* bits of nfi_render_args.tuning that the library reads (described at the field; every other bit is ignored) */
-enum { NFI_TUNING_SCANLINE_ORDER = 4, NFI_TUNING_EXACT_FP32_MLP = 8, NFI_TUNING_SINGLE_WORK_COUNTER = 16 };
+enum { NFI_TUNING_SCANLINE_ORDER = 4, NFI_TUNING_EXACT_FP32_MLP = 8, NFI_TUNING_SINGLE_WORK_COUNTER = 16,
+       NFI_TUNING_XCD_BLOCKS_IN_ORDER = 32 };
 typedef struct nfi_render_args {
   int n_scenes, height, width;   /* n_scenes: the number of images (= scenes x views_per_scene) */
   int n_samples;                 /* S per pass, <= NFI_MAX_SAMPLES; without fine_sampling a single pass of up to
@@ -464,7 +465,9 @@ typedef struct nfi_render_args {
   /* workspace: nfi_render_workspace_bytes(n_scenes*height*width) bytes, 4-byte aligned, contents arbitrary (the ray set-up
    * writes every cell it or the render kernel reads).  Layout: a 576-byte header (the three reduction cells of the ray
    * set-up first), ray_origins and ray_directions [N,3], near and far [N], hit [N] bytes padded to 64, and behind those the
-   * set-up's per-block partial reductions (internal). */
+   * set-up's per-block partial reductions (internal, 16 384 bytes) and, at byte 576 + 32 N + pad64(N) + 16 384, the block
+   * table of the per-XCD queues: N / 64 uint32, queue slot -> pixel block (a hint for balance: every aligned group of 16
+   * slots is a permutation of itself, the render is the same for any such permutation). */
   void* workspace; size_t workspace_bytes;
   /* 1: rays whose line misses the scene cube inflated by 1e-4 skip both passes (exact:
    * every sample of such a ray is outside the cube, sigma==0).  0: evaluate every ray. */
@@ -478,7 +481,9 @@ typedef struct nfi_render_args {
    * storage the texels, not the MLP operands, set the precision - the call is refused).  bit 4 (SINGLE_WORK_COUNTER): ONE device-wide work
    * counter instead of the per-XCD queues over square pixel blocks (results identical; the per-XCD queues take the
    * largest of 32 / 16 / 8 pixels that divides both image sides, two positions per atomic, and fall back to the single
-   * counter when not even 8 does). */
+   * counter when not even 8 does).  bit 5 (XCD_BLOCKS_IN_ORDER): pixel block b sits in slot b of the per-XCD queues,
+   * instead of where the set-up's block table puts it - of every 16 consecutive blocks the heaviest and the lightest by
+   * rays that hit the scene cube go to one XCD, the second of each to the next, ... (results identical; for A/B runs). */
   int tuning;
   /* optional uint64[12] device array: per-phase shader-cycle sums over all waves (profiling build of
    * the kernel; NULL = off): field tile {unused (0), gather issue+wait+interp, mlp, count}, ray set-up, coarse field,

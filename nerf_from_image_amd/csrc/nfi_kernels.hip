@@ -1356,6 +1356,7 @@ struct RenderKernelParams {
   uint32_t* xcd_counter;   // 8 counters, 64 bytes apart
   int xcd_block_shift;     // log2 of the block side: 3, 4 or 5
   int fetch_batch;         // positions taken per atomic
+  const uint32_t* block_table;   // queue slot g = 8 * slot + q -> pixel block (the set-up's pairing by hit count); null: g
   // field
   const void* texels; int res; int layout;
   const float* image; int A; const float* att;
@@ -1415,10 +1416,18 @@ struct RayInputs {
 // from the next one's queue.  fetch() is wave-uniform and returns a RAY ID (n_rays: no work left); without the
 // per-XCD queues (image sides not multiples of the block side, or tuning bit 4) it returns a position of the single
 // queue, which ray_of() maps to a ray.
+// WHICH block sits in slot g = 8 * slot + q of the queues is the set-up's block table (raygen_finish_kernel: every
+// aligned group of 16 slots permuted so that each XCD gets a heavy and a light block by hit count; null or tuning bit 5:
+// block g).  The entry is wave-uniform and changes once per block: (tab_g, tab_b) keep the last look-up.  A look-up
+// behind the claim's atomic would be a second dependent round trip every fourth ray (256 waves x 2 positions turn a block
+// over in two rounds), so the entry of the queue's NEXT block (nxt_g = tab_g + 8) is loaded in front of the atomic, by a
+// scalar load that is under way together with it; only a claim that lands elsewhere (a steal, a block skipped) loads
+// behind it.
 struct RayQueue {
   const RenderKernelParams& k;
   int lane;
   uint32_t n_rays, xcd, bsh, bw, bps, n_blocks, q_cur, pos_next, pos_end, batch, tiles_x;
+  uint32_t tab_g, tab_b = 0u, nxt_g = 0xffffffffu, nxt_b = 0u;
   bool dry;
   __device__ __forceinline__ RayQueue(const RenderKernelParams& kk, int l) : k(kk), lane(l) {
     n_rays = (uint32_t)k.n_scenes * (uint32_t)k.hw;
@@ -1428,11 +1437,39 @@ struct RayQueue {
     bps = bw * (((uint32_t)k.hw / (uint32_t)k.width) >> bsh);
     n_blocks = bps * (uint32_t)k.n_scenes;
     q_cur = xcd; pos_next = 0; pos_end = 0; dry = false;
+    tab_g = xcd - 8u;                    // no entry yet; the first prefetch is for block `xcd`, the wave's first
     batch = (uint32_t)k.fetch_batch;
     tiles_x = (uint32_t)k.width >> 3;
   }
-  __device__ __forceinline__ uint32_t ray_at(uint32_t q, uint32_t pos) const {
-    const uint32_t b = (pos >> (2 * bsh)) * 8u + q;
+  // The table lists an XCD's pair of a complete group heavy block first (entries 16 G + x and 16 G + 8 + x); the queues
+  // take the LIGHT one first (g ^ 8): a launch then ends on heavy blocks, which keep every wave of the XCD busy to the
+  // end, and not on a few hits among misses (measured: profiles/r18, 9-20 us per launch whatever its size).
+  __device__ __forceinline__ uint32_t table_entry(uint32_t g) const {         // g < n_blocks
+    typedef __attribute__((address_space(4))) const uint32_t const_u32;       // written by the set-up, never by this kernel
+    const uint32_t e = (g | 15u) < n_blocks ? g ^ 8u : g;                     // (an incomplete last group is the identity)
+    return *reinterpret_cast<const_u32*>(reinterpret_cast<uintptr_t>(k.block_table) + (uintptr_t)e * 4u);
+  }
+  // in front of a claim's atomic / behind its issue: start the load of the next block's entry / keep it in front of the
+  // atomic's wait (the compiler would sink the load to its use, behind that wait)
+  __device__ __forceinline__ void table_prefetch() {
+    if (!k.block_table) return;
+    const uint32_t g = tab_g + 8u;
+    if (g < n_blocks && g != nxt_g) { nxt_g = g; nxt_b = table_entry(g); }
+  }
+  __device__ __forceinline__ void table_pin() {
+    if (k.block_table) asm volatile("" : "+s"(nxt_b));
+  }
+  __device__ __forceinline__ uint32_t block_at(uint32_t g) {
+    if (!k.block_table) return g;
+    if (g != tab_g) {        // g < n_blocks: fetch() / claim_finish() test it before they take a claim over
+      tab_b = g == nxt_g ? nxt_b : table_entry(g);
+      tab_g = g;
+    }
+    return tab_b;
+  }
+  __device__ __forceinline__ uint32_t ray_at(uint32_t q, uint32_t pos) {
+    // (readfirstlane: q and pos are uniform by construction only; see hit_bytes_scalar)
+    const uint32_t b = block_at((uint32_t)__builtin_amdgcn_readfirstlane((int)((pos >> (2 * bsh)) * 8u + q)));
     const uint32_t in = pos & ((1u << (2 * bsh)) - 1u), scene = fastdiv(b, k.div_bps), bb = b - scene * bps;
     const uint32_t by = fastdiv(bb, k.div_bw), bx = bb - by * bw;
     const uint32_t st = in >> 6, sty = st >> (bsh - 3), stx = st & ((1u << (bsh - 3)) - 1u);   // 8x8 sub-tile of the block
@@ -1447,9 +1484,11 @@ struct RayQueue {
     }
     if (pos_next == pos_end && !dry) {
       dry = true;
+      table_prefetch();
       for (uint32_t i = 0; i < 8; ++i) {
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(k.xcd_counter + q_cur * 16, batch);
+        if (i == 0) table_pin();
         base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
         if ((base >> (2 * bsh)) * 8u + q_cur < n_blocks) { pos_next = base; pos_end = base + batch; dry = false; break; }
         q_cur = (q_cur + 1) & 7u;        // this queue is empty: steal from the next XCD's
@@ -1465,11 +1504,13 @@ struct RayQueue {
   // atomic optimiser rewrites the add so that its result is read back on the spot.
   __device__ __forceinline__ bool claimed() const { return pos_next != pos_end; }
   __device__ __forceinline__ uint32_t take() { return ray_at(q_cur, pos_next++); }      // only if claimed()
-  __device__ __forceinline__ uint32_t claim_issue() const {
+  __device__ __forceinline__ uint32_t claim_issue() {
     uint32_t raw = 0, off = k.xcd_blocks ? q_cur * 16 : 0;
     asm volatile("" : "+v"(off));
     if (k.xcd_blocks && (claimed() || dry)) return raw;
+    table_prefetch();
     if (lane == 0) raw = atomicAdd((k.xcd_blocks ? k.xcd_counter : k.counter) + off, k.xcd_blocks ? batch : 1u);
+    table_pin();
     return raw;
   }
   __device__ __forceinline__ uint32_t claim_finish(uint32_t raw) {
@@ -2252,8 +2293,9 @@ __global__ __launch_bounds__(256, NFI_RENDER_OCC) void render_fwd_long_kernel(Re
 }
 
 // The render workspace: [RenderWorkspaceHeader][ro, rd: 3n floats each][near_raw, far_raw: n floats each][hit: n bytes,
-// padded to 64][kRayBlocks RayPartial: the per-block partials of the ray set-up's reduction].  The header is what
-// raygen_finish_kernel writes, every cell of it; callers read reduce[] from it (the first three cells of the workspace).
+// padded to 64][kRayBlocks RayPartial: the per-block partials of the ray set-up's reduction][block_table: n / 64
+// uint32, at byte 576 + 32 n + pad64(n) + 16 384].  The header is what raygen_finish_kernel writes, every cell of it;
+// callers read reduce[] from it (the first three cells of the workspace).
 struct RenderWorkspaceHeader {
   uint32_t reduce[3];            // the batch-wide miss-fill of the ray set-up: ~key(min near), key(max far), hit count
   uint32_t counter;              // the device-wide work counter (RenderKernelParams::counter)
@@ -2269,15 +2311,80 @@ static size_t render_workspace_prefix_bytes(int64_t n_rays) {
   return sizeof(RenderWorkspaceHeader) + n * 8 * sizeof(float) + ((n + 63) & ~(size_t)63);
 }
 
-extern "C" size_t nfi_render_workspace_bytes(int64_t n_rays) {
+static size_t render_workspace_table_offset(int64_t n_rays) {
   return render_workspace_prefix_bytes(n_rays) + kRayBlocks * sizeof(RayPartial);
 }
 
-// The tail of the ray set-up, one block behind raygen_kernel in the stream: reduce[0..2] from the blocks' partials (max,
-// max, sum: any order gives the same cells) and zeros in the work counters - plain stores to every cell of the header, so
-// a workspace straight from the allocator needs no clearing.
+extern "C" size_t nfi_render_workspace_bytes(int64_t n_rays) {
+  return render_workspace_table_offset(n_rays) + ((size_t)n_rays / 64) * sizeof(uint32_t);
+}
+
+// The square pixel blocks of the per-XCD queues: the largest of 32 / 16 / 8 pixels that divides both image sides (shift:
+// log2 of the side; ok: at least 8 does).  One copy for the set-up, which writes the block table, and the render kernel.
+struct BlockGeometry { int shift, ok; uint32_t bw, bh, n_blocks; };
+static BlockGeometry render_block_geometry(const nfi_render_args* a) {
+  BlockGeometry g;
+  const int both = a->width | a->height;
+  g.shift = (both & 31) == 0 ? 5 : ((both & 15) == 0 ? 4 : 3);
+  const int side = 1 << g.shift;
+  g.ok = (a->width % side == 0) && (a->height % side == 0) ? 1 : 0;
+  g.bw = (uint32_t)a->width >> g.shift; g.bh = (uint32_t)a->height >> g.shift;
+  g.n_blocks = g.bw * g.bh * (uint32_t)a->n_scenes;
+  return g;
+}
+
+// rays of p[0..bytes) whose hit byte has bit 1 set (the inflated test); bytes: 8 or 16
+__device__ __forceinline__ uint32_t count_wide_hits(const uint8_t* p, int bytes) {
+  uint32_t c = 0;
+  if (bytes == 16 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+    const uint4 v = *reinterpret_cast<const uint4*>(p);
+    c = __popc(v.x & 0x02020202u) + __popc(v.y & 0x02020202u) + __popc(v.z & 0x02020202u) + __popc(v.w & 0x02020202u);
+  } else if ((reinterpret_cast<uintptr_t>(p) & 3) == 0) {
+    for (int i = 0; i < bytes; i += 4) c += __popc(*reinterpret_cast<const uint32_t*>(p + i) & 0x02020202u);
+  } else {
+    for (int i = 0; i < bytes; ++i) c += (p[i] >> 1) & 1u;
+  }
+  return c;
+}
+
+// The tail of the ray set-up, behind raygen_kernel in the stream.  Block 0: reduce[0..2] from the blocks' partials (max,
+// max, sum: any order gives the same cells), zeros in the work counters and the identity part of the block table (every
+// slot outside a complete group of 16) - plain stores to every cell, so a workspace straight from the allocator needs no
+// clearing.  Block 1 + G: group G of the block table.  Slot g = 8 * slot + q belongs to XCD q, so an aligned group of 16
+// slots gives every XCD two blocks; the group's 16 pixel blocks are ranked by their rays with hit bit 1 (count descending,
+// index ascending; 16 threads count one block along its rows, the counts meet in LDS, 16 lanes rank by counting), rank r
+// and rank 15 - r share XCD (min(r, 15 - r) + G) % 8, the heavier of the two first.  No atomics, no block waits for
+// another; the render kernels read the table as a hint for balance only (any permutation of a group renders the same).
+struct BlockTableParams { const uint8_t* hit; uint32_t* table; int shift, width, hw; uint32_t bw, bps, n_blocks, groups; };
+
 __global__ __launch_bounds__(256) void raygen_finish_kernel(const RayPartial* __restrict__ partial, int n_partials,
-                                                            RenderWorkspaceHeader* __restrict__ head) {
+                                                            RenderWorkspaceHeader* __restrict__ head, BlockTableParams t) {
+  if (blockIdx.x != 0) {
+    __shared__ uint32_t s_part[256], s_count[16];
+    const uint32_t G = blockIdx.x - 1, i = threadIdx.x >> 4, sub = threadIdx.x & 15u;
+    const uint32_t b = 16u * G + i, scene = b / t.bps, bb = b - scene * t.bps, by = bb / t.bw, bx = bb - by * t.bw;
+    const uint8_t* base = t.hit + (size_t)scene * (size_t)t.hw + (size_t)(by << t.shift) * (size_t)t.width + (bx << t.shift);
+    const int side = 1 << t.shift, cw = side < 16 ? side : 16, per_row = side / cw;     // a row in chunks of cw bytes
+    uint32_t c = 0;
+    for (int ch = (int)sub; ch < side * per_row; ch += 16)
+      c += count_wide_hits(base + (size_t)(ch / per_row) * (size_t)t.width + (ch % per_row) * cw, cw);
+    s_part[threadIdx.x] = c;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+      uint32_t sum = 0;
+      for (int j = 0; j < 16; ++j) sum += s_part[threadIdx.x * 16 + j];
+      s_count[threadIdx.x] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) {
+      const uint32_t me = threadIdx.x, mine = s_count[me];
+      uint32_t r = 0;
+      for (uint32_t j = 0; j < 16; ++j) r += (s_count[j] > mine || (s_count[j] == mine && j < me)) ? 1u : 0u;
+      const uint32_t pair = r < 8 ? r : 15u - r, x = (pair + G) & 7u;
+      t.table[16u * G + (r < 8 ? 0u : 8u) + x] = 16u * G + me;
+    }
+    return;
+  }
   uint32_t kmin = 0u, kmax = 0u, cnt = 0u;
   for (int i = threadIdx.x; i < n_partials; i += blockDim.x) {
     const RayPartial p = partial[i];
@@ -2289,11 +2396,12 @@ __global__ __launch_bounds__(256) void raygen_finish_kernel(const RayPartial* __
   uint32_t* cells = reinterpret_cast<uint32_t*>(head);
   for (int i = 3 + threadIdx.x; i < (int)(sizeof(RenderWorkspaceHeader) / sizeof(uint32_t)); i += blockDim.x) cells[i] = 0u;
   if (threadIdx.x == 0) { head->reduce[0] = kmin; head->reduce[1] = kmax; head->reduce[2] = cnt; }
+  for (uint32_t g = 16u * t.groups + threadIdx.x; g < t.n_blocks; g += blockDim.x) t.table[g] = g;
 }
 
 // workspace carve + ray set-up shared by nfi_render_setup and nfi_render_fwd
 struct RenderWorkspace {
-  RenderWorkspaceHeader* head; float* ro; float* rd; float* near_raw; float* far_raw; uint8_t* hit; RayPartial* partial; int64_t n;
+  RenderWorkspaceHeader* head; float* ro; float* rd; float* near_raw; float* far_raw; uint8_t* hit; RayPartial* partial; uint32_t* block_table; int64_t n;
 };
 
 static int render_carve(const nfi_render_args* a, RenderWorkspace& w) {
@@ -2310,6 +2418,7 @@ static int render_carve(const nfi_render_args* a, RenderWorkspace& w) {
   w.far_raw = rays + 7 * n;
   w.hit = a->hit ? a->hit : reinterpret_cast<uint8_t*>(rays + 8 * n);
   w.partial = reinterpret_cast<RayPartial*>(reinterpret_cast<char*>(a->workspace) + render_workspace_prefix_bytes(n));
+  w.block_table = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a->workspace) + render_workspace_table_offset(n));
   return NFI_OK;
 }
 
@@ -2320,7 +2429,12 @@ static int render_setup(const nfi_render_args* a, const RenderWorkspace& w, hipS
   RaygenOut rout{w.ro, w.rd, w.near_raw, w.far_raw, w.hit, w.partial, a->scene_range};
   const int blocks = (int)std::min<int64_t>((w.n + 255) / 256, kRayBlocks);
   hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)blocks), dim3(256), 0, s, cam, a->n_scenes, rout);
-  hipLaunchKernelGGL(raygen_finish_kernel, dim3(1), dim3(256), 0, s, w.partial, blocks, w.head);
+  // the block table: complete groups of 16 blocks are paired by hit count, the rest (and everything when the per-XCD
+  // queues cannot be used, or there are fewer than 16 blocks) is the identity
+  const BlockGeometry g = render_block_geometry(a);
+  const uint32_t n_table = g.ok ? g.n_blocks : (uint32_t)(w.n / 64), groups = g.ok ? g.n_blocks / 16 : 0u;
+  const BlockTableParams t{w.hit, w.block_table, g.shift, a->width, a->height * a->width, g.bw, g.bw * g.bh, n_table, groups};
+  hipLaunchKernelGGL(raygen_finish_kernel, dim3(1 + groups), dim3(256), 0, s, w.partial, blocks, w.head, t);
   return NFI_OK;
 }
 
@@ -2427,11 +2541,12 @@ static RenderKernelParams render_kernel_params(const nfi_render_args* a, const R
   // result); the block side mostly through the balance of the chairs-like images, whose rays that cross the cube are
   // clustered.
   k.fetch_batch = 2;
-  const int both = a->width | a->height;
-  k.xcd_block_shift = (both & 31) == 0 ? 5 : ((both & 15) == 0 ? 4 : 3);
-  const int side = 1 << k.xcd_block_shift;
-  k.xcd_blocks = (!(a->tuning & NFI_TUNING_SINGLE_WORK_COUNTER) && (a->width % side == 0) && (a->height % side == 0)) ? 1 : 0;
-  const uint32_t bw = (uint32_t)a->width >> k.xcd_block_shift, bh = (uint32_t)a->height >> k.xcd_block_shift;
+  const BlockGeometry geo = render_block_geometry(a);
+  k.xcd_block_shift = geo.shift;
+  k.xcd_blocks = (!(a->tuning & NFI_TUNING_SINGLE_WORK_COUNTER) && geo.ok) ? 1 : 0;
+  // which block sits in which queue slot: the set-up's pairing of heavy and light blocks (tuning bit 5: in order)
+  k.block_table = (k.xcd_blocks && !(a->tuning & NFI_TUNING_XCD_BLOCKS_IN_ORDER)) ? w.block_table : nullptr;
+  const uint32_t bw = geo.bw, bh = geo.bh;
   // the scene of a ray: its image / views_per_scene (the images of a call are scene-major); hw * V <= rays of the call < 2^32
   k.div_scene_rays = make_fastdiv((uint32_t)k.hw * (uint32_t)std::max(a->views_per_scene, 1));
   k.div_bw = make_fastdiv(bw > 0 ? bw : 1u);
