@@ -98,6 +98,13 @@ __device__ __forceinline__ uint32_t fastdiv(uint32_t x, FastDiv f) {
 
 // ---- small wave helpers ---------------------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
+// A launch-invariant, wave-uniform integer made opaque at the place of its use.  What is computed from the result - a
+// compare, a mask, a shift - is scalar-ALU work next to its use and cannot be hoisted out of the enclosing loops; computed
+// from the value itself it is, as one more loop-invariant scalar for kernels that have no scalar register left for it.
+__device__ __forceinline__ int scalar_here(int v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
 // Ordering point between the lanes of ONE wave around its private LDS slab: LDS operations of a wave execute in
 // issue order, so a compiler fence plus a wave barrier (no s_waitcnt) is all a write -> read-by-other-lanes needs.
 __device__ __forceinline__ void wave_lds_fence() {
@@ -870,7 +877,7 @@ __device__ __forceinline__ void sample_epilogue(const FieldParams& P, int lane, 
   const float sdf = tb[0];
   const float outs = outside ? 1.0f : 0.0f;
   float sigma, cr, cg, cb;
-  if (P.use_sdf) {
+  if (scalar_here(P.use_sdf)) {        // (scalar_here: see A below)
     // sigma = (1/alpha) * (0.5 + 0.5*sign(-d)*(1 - exp(-|d|/beta))) * (1 - outside)
     float e = __builtin_amdgcn_exp2f(fabsf(sdf) * P.neg_log2e_over_beta);
     float sgn = (sdf < 0.0f) ? 0.5f : ((sdf > 0.0f) ? -0.5f : 0.0f);
@@ -883,9 +890,14 @@ __device__ __forceinline__ void sample_epilogue(const FieldParams& P, int lane, 
   }
   if constexpr (ATT) {
     // softmax over rows 1..A (pre-scaled by log2e); A and the group conditions are wave-uniform
-    const int A = P.n_attention;
+    // A passes through an opaque scalar register in front of each of the three passes (scalar_here): the eighteen
+    // conditions on it are then scalar compares at their use.  Left to itself the compiler hoists every one of them out of
+    // the caller's ray loop as a 64-bit lane mask, and the render kernels, short of scalar registers, keep those masks in
+    // lanes of a vector register: two v_readlane in front of every select below, for the coarse and for the fine pass.
+    const int A0 = P.n_attention;
     float x[16], e16[16];
     float m = -INFINITY;
+    int A = scalar_here(A0);
 #pragma unroll
     for (int gi = 0; gi < 4; ++gi) {
       if (4 * gi <= A) {
@@ -898,6 +910,7 @@ __device__ __forceinline__ void sample_epilogue(const FieldParams& P, int lane, 
         }
       }
     }
+    A = scalar_here(A0);
     // the scene's attention values: one row per decoder row, wave-uniform addresses (LDS broadcast reads)
     const f32x4* vf = reinterpret_cast<const f32x4*>(P.vf);
     float seg[4], srg[4], sgg[4], sbg[4];
@@ -925,6 +938,7 @@ __device__ __forceinline__ void sample_epilogue(const FieldParams& P, int lane, 
     float inv = __builtin_amdgcn_rcpf(se);
     inv = inv * (2.0f - se * inv);      // one Newton step: the quotient is then within 1 ulp
     cr = sr * inv; cg = sg * inv; cb = sb * inv;
+    A = scalar_here(A0);
     if (sem && live) {
 #pragma unroll
       for (int gi = 0; gi < 4; ++gi) {

@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 using namespace nfi;
 
@@ -1399,6 +1400,19 @@ struct ClockProbe {
   }
 };
 
+// The kernel's argument block, read again where it is used.  Every argument the compiler keeps live through the ray loop is
+// a scalar register (two for a pointer) of a kernel that has none to spare: the plain S <= 64 kernel held 121 of them in
+// lanes of two vector registers and fetched them back with v_readlane - vector instructions, ~190 per marched ray, for
+// values that never change.  A scalar load from the argument segment (which a kernel's only by-value parameter starts)
+// costs the vector pipe nothing and the scalar cache always has the line.  The pointer is opaque to the compiler, or it
+// would hoist the loads back out of the loop; call this AT the use, once per group of loads that may wait together.
+typedef __attribute__((address_space(4))) const RenderKernelParams RenderKernelArgs;
+__device__ __forceinline__ RenderKernelArgs* kernel_args_here() {
+  auto* p = reinterpret_cast<RenderKernelArgs*>(reinterpret_cast<uintptr_t>(__builtin_amdgcn_kernarg_segment_ptr()));
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
 __device__ __forceinline__ float uniform_f32(float v) {
   return bits2f((uint32_t)__builtin_amdgcn_readfirstlane((int)f2bits(v)));
 }
@@ -1612,7 +1626,9 @@ __device__ __forceinline__ void enter_scene(FieldParams& P, const RenderKernelPa
 }
 
 // a ray's five results (the caller picks the lane, and the place: see the work fetch of render_fwd_kernel)
-__device__ __forceinline__ void store_pixel(const RenderKernelParams& k, uint32_t ray, float r, float g, float b, float depth,
+// (K: RenderKernelParams, or RenderKernelArgs - the three pointers re-read from the argument segment)
+template <class K>
+__device__ __forceinline__ void store_pixel(const K& k, uint32_t ray, float r, float g, float b, float depth,
                                             float mask) {
   k.rgb[(size_t)ray * 3] = r; k.rgb[(size_t)ray * 3 + 1] = g; k.rgb[(size_t)ray * 3 + 2] = b;
   k.depth[ray] = depth; k.mask[ray] = mask;
@@ -1778,14 +1794,27 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
     }
   }
 
-  auto load_inputs = [&](uint32_t ray, RayInputs& in) {
+  // (the seven pointers, S, `fine` and the stride from the argument segment - see kernel_args_here.  together: all through
+  //  one empty asm, so that the scalar loads go out in front of ONE wait - the ray loop's load, once per marched ray.  Not
+  //  for the loads of skip_miss_run, one per run of misses: in its three branches the asm's outputs meet values that do not
+  //  exist, which the compiler fills in with v_readfirstlane of nothing)
+  auto load_inputs = [&](uint32_t ray, RayInputs& in, auto together) {
+    RenderKernelArgs& a = *kernel_args_here();
+    const uint8_t* hit = a.hit;
+    const float *ro = a.ro, *rd = a.rd, *near_raw = a.near_raw, *far_raw = a.far_raw, *noise_c = a.noise_c, *noise_f = a.noise_f;
+    int64_t noise_f_stride = a.noise_f_stride;
+    int n_samples = a.S, fine = a.fine;
+    if constexpr (decltype(together)::value)
+      asm volatile("" : "+s"(hit), "+s"(ro), "+s"(rd), "+s"(near_raw), "+s"(far_raw), "+s"(noise_c), "+s"(noise_f),
+                        "+s"(noise_f_stride), "+s"(n_samples), "+s"(fine));
     const size_t r3 = (size_t)ray * 3;
-    in.hit = k.hit[ray];
-    in.ox = k.ro[r3]; in.oy = k.ro[r3 + 1]; in.oz = k.ro[r3 + 2];
-    in.dx = k.rd[r3]; in.dy = k.rd[r3 + 1]; in.dz = k.rd[r3 + 2];
-    in.near = k.near_raw[ray]; in.far = k.far_raw[ray];
-    in.noise = (k.noise_c && valid) ? k.noise_c[(size_t)ray * S + lane] : 0.0f;
-    in.u = (k.fine && valid) ? k.noise_f[(size_t)ray * k.noise_f_stride + lane] : 0.0f;
+    const bool has = lane < n_samples;
+    in.hit = hit[ray];
+    in.ox = ro[r3]; in.oy = ro[r3 + 1]; in.oz = ro[r3 + 2];
+    in.dx = rd[r3]; in.dy = rd[r3 + 1]; in.dz = rd[r3 + 2];
+    in.near = near_raw[ray]; in.far = far_raw[ray];
+    in.noise = (noise_c && has) ? noise_c[(size_t)ray * n_samples + lane] : 0.0f;
+    in.u = (fine && has) ? noise_f[(size_t)ray * noise_f_stride + lane] : 0.0f;
   };
 
   // ray indices: cur (being marched), nxt (inputs being loaded), and one more in flight
@@ -1797,7 +1826,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
   // [6] resample, [7] fine field, [8] merge, [9] composite + store, [10] rays, [11] total
   unsigned long long pc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tk0 = PROF ? __builtin_readcyclecounter() : 0;
-  if (cur < n_rays) load_inputs(queue.ray_of(cur), in);
+  if (cur < n_rays) load_inputs(queue.ray_of(cur), in, std::false_type());
   // A ray that misses the cube never enters the loop below: it and the missed ones behind it are dealt with here, before
   // the first ray and behind every marched one, and `in` is loaded afresh for the ray that ends the run.  (Behind the
   // loop's turn and not in front of it: a second way back to the loop's head cost 14-23 vector registers.  The hit byte
@@ -1805,17 +1834,19 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
   // vector register the compiler moves that state, the ray index and with it the texel descriptor to vector registers.)
   auto skip_run = [&]() {
     if (k.skip_missed && cur < n_rays && !((uint32_t)__builtin_amdgcn_readfirstlane((int)in.hit) & 2))
-      skip_miss_run<EXTRA, NRM, TAPS>(queue, k, S, lane, bg, cur, nxt, [&](uint32_t r) { load_inputs(r, in); });
+      skip_miss_run<EXTRA, NRM, TAPS>(queue, k, S, lane, bg, cur, nxt, [&](uint32_t r) { load_inputs(r, in, std::false_type()); });
   };
   skip_run();
   while (cur < n_rays) {
-    if (nxt < n_rays) load_inputs(queue.ray_of(nxt), pre);
+    if (nxt < n_rays) load_inputs(queue.ray_of(nxt), pre, std::true_type());
     const uint32_t ray = queue.ray_of(cur);
     const uint32_t hitb = in.hit;
     // the ray's five results: stored after the work fetch at the end of the iteration (see there)
     float out_r = bg, out_g = bg, out_b = bg, out_d = 0.0f, out_m = 0.0f;
     unsigned long long t0 = PROF ? __builtin_readcyclecounter() : 0;
-    const int scene = (int)fastdiv(ray, k.div_scene_rays);
+    // (the divisor's words: a struct in the constant address space does not copy into fastdiv's by-value parameter)
+    RenderKernelArgs& ka = *kernel_args_here();
+    const int scene = (int)fastdiv(ray, FastDiv{ka.div_scene_rays.mul, ka.div_scene_rays.shift});
     if (scene != cur_scene) {
       cur_scene = scene;
       enter_scene<TEX>(P, k, vf, scene, lane);
@@ -1828,7 +1859,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
 
     // ---- coarse pass ----
     float tc = 0.0f;
-    if (valid) tc = stratified_depth(near, far, lane, S, in.noise, k.noise_c != nullptr);
+    if (valid) tc = stratified_depth(near, far, lane, S, in.noise, kernel_args_here()->noise_c != nullptr);
     MergeIn c;
     float ncx = 0.0f, ncy = 0.0f, ncz = 0.0f, nfx = 0.0f, nfy = 0.0f, nfz = 0.0f;     // NRM: the samples' unit normals
     unsigned long long t1 = PROF ? __builtin_readcyclecounter() : 0;
@@ -1845,7 +1876,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
     if (k.fine) {
       // ---- hierarchical resampling + fine pass ----
       ResampleTaps rt;
-      float tf = resample_ray(slab, c.sigma, tc, S, dnorm, in.u, lane, TERM ? &rt : nullptr);
+      float tf = resample_ray(slab, c.sigma, tc, scalar_here(S), dnorm, in.u, lane, TERM ? &rt : nullptr);
       MergeIn f;
       if (PROF) { asm volatile("" :: "v"(tf)); t3 = __builtin_readcyclecounter(); }
       if constexpr (TERM) {
@@ -1881,14 +1912,14 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
       }
       n = 2 * S;
       if (PROF) t4 = __builtin_readcyclecounter();
-      merge_pair_scatter(slab, c, f, S, lane, rank_c, rank_f);
+      merge_pair_scatter(slab, c, f, scalar_here(S), lane, rank_c, rank_f);
       if (PROF) t5 = __builtin_readcyclecounter();
     } else {
       if (valid) { slab.srt[0][lane] = c.t; slab.srt[1][lane] = c.sigma; slab.srt[2][lane] = c.r; slab.srt[3][lane] = c.g; slab.srt[4][lane] = c.b; }
       wave_lds_fence();
     }
     float w[2];
-    CompositeOut o = composite_slab<2>(slab, n, dnorm, k.white, lane, w);
+    CompositeOut o = composite_slab<2>(slab, scalar_here(n), dnorm, k.white, lane, w);
     out_r = o.r; out_g = o.g; out_b = o.b; out_d = o.depth; out_m = o.mask;
     if constexpr (EXTRA) {
       if (k.coords) composite_coords<2>(slab, w, n, lane, ox, oy, oz, dx, dy, dz, k.coords + (size_t)ray * 3);
@@ -1943,7 +1974,7 @@ __global__ __launch_bounds__(256, OCC) void render_fwd_kernel(RenderKernelParams
     // every store the wave has in flight.  Here, after the ray's arithmetic and BEFORE its result stores, nothing of this
     // ray is in flight any more (the taps / extra maps of those variants excepted): the wait is the atomic's alone.
     fly = fetch();
-    if (lane == 0) store_pixel(k, ray, out_r, out_g, out_b, out_d, out_m);
+    if (lane == 0) store_pixel(*kernel_args_here(), ray, out_r, out_g, out_b, out_d, out_m);
     in = pre;
     cur = nxt;
     nxt = fly;
