@@ -1683,15 +1683,6 @@ uint64_t* ord_sort_by_cell(uint64_t* keys, uint64_t* spare, uint32_t* hist, int6
   return op.keys_in;
 }
 
-__device__ __forceinline__ int64_t ord_lower_bound(const uint64_t* keys, int64_t n, uint64_t v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 // grid (ceil(scenes * 3 * res^2 / 8)), 256 threads: one half-wave per texel and plane, lane = channel (keys_in: the sorted keys)
 __global__ __launch_bounds__(256) void ord_gather_kernel(OrdParams k) {
   const int l32 = threadIdx.x & 31;
@@ -1754,31 +1745,20 @@ struct FinishParams {
   float *g_w1, *g_b1, *g_w2, *g_b2, *g_att, *g_beta, *g_alpha;
 };
 
-// grid (kSlotFloats / 16), 256 threads = 16 slot offsets x 16 parts: a part sums a contiguous range of slots in index
-// order, part 0 adds the 16 partial sums in part order to the caller's buffer
+// grid (kSlotFloats / 16), 256 threads = 16 slot offsets x 16 parts: ordered_slot_sum over all slots (the attention
+// values: over each scene's), part 0 adds the sum to the caller's buffer
 __global__ __launch_bounds__(256) void param_finish_kernel(FinishParams k) {
   __shared__ float partial[16][16];
   const int e = threadIdx.x & 15, part = threadIdx.x >> 4;
   const int o = blockIdx.x * 16 + e;
-  auto sum_slots = [&](int first, int n) -> float {
-    const int s0 = first + (int)(((int64_t)n * part) / 16), s1 = first + (int)(((int64_t)n * (part + 1)) / 16);
-    float acc = 0.0f;
-    for (int s = s0; s < s1; ++s) acc += k.slots[(size_t)s * kSlotFloats + o];
-    __syncthreads();
-    partial[part][e] = acc;
-    __syncthreads();
-    float t = 0.0f;
-    for (int q = 0; q < 16; ++q) t += partial[q][e];
-    return t;
-  };
   if (o >= kSlotAtt && o < kSlotBeta) {               // (block-uniform: the regions are multiples of 16)
     for (int sc = 0; sc < k.n_scenes; ++sc) {
-      const float t = sum_slots(sc * k.slots_per_scene, k.slots_per_scene);
+      const float t = ordered_slot_sum(k.slots, kSlotFloats, o, sc * k.slots_per_scene, k.slots_per_scene, partial);
       if (part == 0 && o - kSlotAtt < k.A * 3) k.g_att[(size_t)sc * k.A * 3 + (o - kSlotAtt)] += t;
     }
     return;
   }
-  const float t = sum_slots(0, k.n_scenes * k.slots_per_scene);
+  const float t = ordered_slot_sum(k.slots, kSlotFloats, o, 0, k.n_scenes * k.slots_per_scene, partial);
   if (part != 0) return;
   if (o < kSlotB1) k.g_w1[o] += t;
   else if (o < kSlotW2) k.g_b1[o - kSlotB1] += t;
@@ -1802,8 +1782,6 @@ static inline size_t bin_max_items(int n_scenes, int64_t P, int res) {
   const int g = bin_groups(P), t = bin_tile_side(res, g), tps = (res + t - 1) / t;
   return (size_t)n_scenes * ((size_t)(3 * P / kBinChunk) + (size_t)g * 3 * tps * tps);
 }
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The workspace of one nfi_field_query_bwd call: byte offsets of its regions and the total.  Behind the backward operand
 // image come, for the binned scatter only, the feature-gradient rows, the sorted entries, the bucket counters

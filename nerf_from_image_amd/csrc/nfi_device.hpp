@@ -1649,4 +1649,31 @@ __device__ __forceinline__ int upper_bound_lds(const float* cdf, int M, float u)
   return pos;
 }
 
+// ---- the ordered (bit-reproducible) backward modes: what their gather and finish kernels share -------------------
+// first index of the sorted keys[0, n) whose key is not below v
+__device__ __forceinline__ int64_t ord_lower_bound(const uint64_t* keys, int64_t n, uint64_t v) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// Sum over the slots [first, first + n) of the float at offset o (slots of `pitch` floats) by a block of 256 threads = 16
+// offsets (threadIdx.x & 15) x 16 parts (threadIdx.x >> 4): a part sums a contiguous range of slots in index order, then the
+// 16 partial sums are added in part order (every part returns the sum, part 0 writes it).  Two barriers: the whole block calls.
+__device__ __forceinline__ float ordered_slot_sum(const float* slots, int pitch, int o, int first, int n, float (&partial)[16][16]) {
+  const int e = threadIdx.x & 15, part = threadIdx.x >> 4;
+  const int s0 = first + (int)(((int64_t)n * part) / 16), s1 = first + (int)(((int64_t)n * (part + 1)) / 16);
+  float acc = 0.0f;
+  for (int s = s0; s < s1; ++s) acc += slots[(size_t)s * pitch + o];
+  __syncthreads();
+  partial[part][e] = acc;
+  __syncthreads();
+  float t = 0.0f;
+  for (int q = 0; q < 16; ++q) t += partial[q][e];
+  return t;
+}
+
 }  // namespace nfi

@@ -26,9 +26,9 @@
 //   torgb_bwd_weight_kernel  g_W = sum_{b,p} g (s x)^T (MFMA with the pixels along K), g_bias = sum g
 //   upsample_bwd_kernel      g_prev = the adjoint of the stride-2 bilinear up-filter (a 4x4 gather per coarse pixel)
 // The two MFMA kernels sum g_s, g_W and g_bias with float atomics (LDS and global).  nfi_torgb_texels_bwd_ordered runs
-// ordered twins of the two: every partial sum goes to a workspace slot of its own - one per (scene, block, wave) for g_s,
-// one per block for g_W / g_bias, the block's four waves combined in wave order - and two finish kernels add the slots in
-// index order.  g_x and g_prev have one writer per element either way.
+// ordered COPIES of the two (why copies: at the ordered data kernel): every partial sum goes to a workspace slot of its own -
+// one per (scene, block, wave) for g_s, one per block for g_W / g_bias, the block's four waves combined in wave order - and
+// two finish kernels add the slots in index order.  g_x and g_prev have one writer per element either way.
 
 struct TorgbParams {
   const float* x; const float* styles; const float* weight; const float* bias; const float* prev;
@@ -40,6 +40,7 @@ struct TorgbParams {
 constexpr int kTorgbOut = 96;          // 3 planes x 32 channels
 constexpr int kTorgbMaxCin = 256;      // largest in_channels accepted (sizes the dynamic-LDS limit once)
 constexpr int kTorgbTilesPerWave = 4;  // 64-pixel tiles a wave walks per block visit
+constexpr int kTorgbBlockPixels = 64 * 4 * kTorgbTilesPerWave;   // of a block of the forward and the data kernels
 
 // 1-D taps of the up-filter for output index Y: rows (m_lo weight .., m_hi ..) of the coarse image, zero outside
 __device__ __forceinline__ void up_taps(int Y, int half, int& m_a, int& m_b, float& w_a, float& w_b) {
@@ -223,8 +224,8 @@ __global__ __launch_bounds__(256, 2) void torgb_bwd_data_kernel(TorgbParams k) {
 }
 
 // torgb_bwd_data_kernel with g_s left to a finish kernel: the same statements (g_x is that kernel's, bit for bit), but each
-// wave STORES its row-reduced sums to slots[scene][block][wave][Cin] - zeros from a wave without pixels.  A kernel of its
-// own, not a template arm: sharing the body changed the instructions the default kernel compiles to.
+// wave STORES its row-reduced sums to slots[scene][block][wave][Cin] - zeros from a wave without pixels.  Still a copy: one
+// inlined body with a stateless flush functor kept every resource, and cost both default kernels 1 % (profiles/r20).
 __global__ __launch_bounds__(256, 2) void torgb_bwd_data_ordered_kernel(TorgbParams k, float* slots) {
   extern __shared__ __attribute__((aligned(16))) float dyn[];
   const int Cin = k.Cin, TK = Cin >> 4;                  // 16-row tiles of input channels
@@ -383,9 +384,9 @@ __global__ __launch_bounds__(256, 2) void torgb_bwd_weight_kernel(TorgbParams k,
   }
 }
 
-// torgb_bwd_weight_kernel without atomics: the same grid-stride accumulation, then the four waves add into red one after
-// the other (wave order, a barrier between them), their bias sums meet in red_bias[wave][96], and the block stores its
-// sums to part_w[tkg][block][96 x 64] / part_b[block][96] for torgb_bwd_weight_finish_kernel.
+// torgb_bwd_weight_kernel without atomics: a copy of its grid-stride accumulation (shared, the default kernel was 1 % slower:
+// profiles/r20), then the four waves add into red one after the other (wave order, a barrier between them), their bias sums
+// meet in red_bias[wave][96], and the block stores part_w[tkg][block][96 x 64] / part_b[block][96] for the finish kernel.
 __global__ __launch_bounds__(256, 2) void torgb_bwd_weight_ordered_kernel(TorgbParams k, int groups_per_image, float* part_w,
                                                                           float* part_b) {
   __shared__ float red[kTorgbOut * 64];                    // 24 KB + 1.5 KB: two blocks per CU, as the kernel above
@@ -507,11 +508,18 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(TorgbParams k) {
   for (int r = 0; r < 4; ++r) k.g_prev[(((size_t)b * kTorgbOut + 4 * q + r) * half + m) * half + n] = acc[r];
 }
 
+// the shape rule of every entry (torgb_common refuses with one message per line, the workspace query answers 0)
+static bool torgb_channels_ok(const nfi_torgb_args* a) {
+  return a->n_scenes > 0 && a->in_channels >= 16 && a->in_channels <= kTorgbMaxCin && a->in_channels % 16 == 0;
+}
+static bool torgb_resolution_ok(const nfi_torgb_args* a) {
+  return a->resolution >= 8 && a->resolution <= 1024 && a->resolution % 8 == 0;
+}
+
 static int torgb_common(const nfi_torgb_args* a, TorgbParams& k) {
   REQUIRE(a && a->x && a->styles && a->weight, "torgb_texels: null pointer");
-  REQUIRE(a->n_scenes > 0 && a->in_channels >= 16 && a->in_channels <= kTorgbMaxCin && a->in_channels % 16 == 0,
-          "torgb_texels: in_channels must be a multiple of 16 in [16,256]");
-  REQUIRE(a->resolution >= 8 && a->resolution <= 1024 && a->resolution % 8 == 0, "torgb_texels: resolution must be a multiple of 8 in [8,1024]");
+  REQUIRE(torgb_channels_ok(a), "torgb_texels: in_channels must be a multiple of 16 in [16,256]");
+  REQUIRE(torgb_resolution_ok(a), "torgb_texels: resolution must be a multiple of 8 in [8,1024]");
   memset(&k, 0, sizeof(k));
   k.x = a->x; k.styles = a->styles; k.weight = a->weight; k.bias = a->bias; k.prev = a->previous_image;
   k.B = a->n_scenes; k.Cin = a->in_channels; k.R = a->resolution;
@@ -525,8 +533,7 @@ extern "C" int nfi_torgb_texels_fwd(const nfi_torgb_args* a, nfi_stream_t stream
   REQUIRE(a->bias && a->texels, "torgb_texels_fwd: null pointer");
   k.out = a->texels;
   const int P = k.R * k.R;
-  const int per_block = 64 * 4 * kTorgbTilesPerWave;
-  dim3 grid((unsigned)((P + per_block - 1) / per_block), (unsigned)k.B);
+  dim3 grid((unsigned)((P + kTorgbBlockPixels - 1) / kTorgbBlockPixels), (unsigned)k.B);
   const size_t shmem = ((size_t)kTorgbOut * k.Cin + k.Cin + kTorgbOut) * sizeof(float);
   rc = ensure_dynamic_lds<&torgb_texels_fwd_kernel>(((size_t)kTorgbOut * kTorgbMaxCin + kTorgbMaxCin + kTorgbOut) * sizeof(float), "torgb_texels_fwd");
   if (rc) return rc;
@@ -534,109 +541,106 @@ extern "C" int nfi_torgb_texels_fwd(const nfi_torgb_args* a, nfi_stream_t stream
   return check_launch("torgb_texels_fwd");
 }
 
-extern "C" int nfi_torgb_texels_bwd(const nfi_torgb_args* a, nfi_stream_t stream) {
-  TorgbParams k;
-  int rc = torgb_common(a, k);
+// the backward's arguments, for both entries (`entry`: the name in front of the messages)
+static int torgb_bwd_common(const nfi_torgb_args* a, TorgbParams& k, const char* entry) {
+  const int rc = torgb_common(a, k);
   if (rc) return rc;
-  REQUIRE(a->g_texels && a->g_x && a->g_styles, "torgb_texels_bwd: g_texels / g_x / g_styles missing");
-  REQUIRE(!a->g_previous_image || a->previous_image, "torgb_texels_bwd: g_previous_image without previous_image");
+  const char* bad = !(a->g_texels && a->g_x && a->g_styles) ? "g_texels / g_x / g_styles missing"
+                    : a->g_previous_image && !a->previous_image ? "g_previous_image without previous_image" : nullptr;
+  if (bad) {
+    snprintf(nfi_err_buf, sizeof(nfi_err_buf), "%s: %s", entry, bad);
+    return NFI_ERR_INVALID_ARGUMENT;
+  }
   k.g_out = a->g_texels; k.g_x = a->g_x; k.g_styles = a->g_styles; k.g_weight = a->g_weight; k.g_bias = a->g_bias;
   k.g_prev = a->g_previous_image;
+  return NFI_OK;
+}
+
+// The backward's grids, a function of the shape alone (which is what fixes the ordered entry's slot order): blocks per
+// scene of the data kernels and their dynamic LDS, blocks and 64-channel groups of the weight kernels
+struct TorgbBwdGrids { int data_blocks, weight_blocks, weight_groups; size_t data_lds; };
+constexpr size_t kTorgbBwdMaxLds = ((size_t)kTorgbOut * kTorgbMaxCin + kTorgbMaxCin) * sizeof(float);
+
+static TorgbBwdGrids torgb_bwd_grids(const nfi_torgb_args* a) {
+  const int64_t P = (int64_t)a->resolution * a->resolution;
+  TorgbBwdGrids g;
+  g.data_blocks = (int)((P + kTorgbBlockPixels - 1) / kTorgbBlockPixels);
+  g.weight_blocks = (int)std::min<int64_t>(((int64_t)a->n_scenes * (P / 16) + 3) / 4, 256);
+  g.weight_groups = (a->in_channels + 63) / 64;
+  g.data_lds = ((size_t)kTorgbOut * a->in_channels + a->in_channels) * sizeof(float);
+  return g;
+}
+
+static void launch_upsample_bwd(const TorgbParams& k, hipStream_t s) {
+  if (!k.g_prev) return;
+  const int half = k.R / 2;
+  const int64_t total = (int64_t)k.B * half * half * 24;
+  hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, k);
+}
+
+extern "C" int nfi_torgb_texels_bwd(const nfi_torgb_args* a, nfi_stream_t stream) {
+  TorgbParams k;
+  int rc = torgb_bwd_common(a, k, "torgb_texels_bwd");
+  if (rc) return rc;
+  const TorgbBwdGrids g = torgb_bwd_grids(a);
   hipStream_t s = (hipStream_t)stream;
-  const int P = k.R * k.R;
   if (hipMemsetAsync(k.g_styles, 0, sizeof(float) * (size_t)k.B * k.Cin, s) != hipSuccess) return fail(NFI_ERR_LAUNCH, "torgb_texels_bwd: memset failed");
-  {
-    const int per_block = 64 * 4 * kTorgbTilesPerWave;
-    dim3 grid((unsigned)((P + per_block - 1) / per_block), (unsigned)k.B);
-    const size_t shmem = ((size_t)kTorgbOut * k.Cin + k.Cin) * sizeof(float);
-    rc = ensure_dynamic_lds<&torgb_bwd_data_kernel>(((size_t)kTorgbOut * kTorgbMaxCin + kTorgbMaxCin) * sizeof(float), "torgb_texels_bwd");
-    if (rc) return rc;
-    hipLaunchKernelGGL(torgb_bwd_data_kernel, grid, dim3(256), shmem, s, k);
-  }
+  rc = ensure_dynamic_lds<&torgb_bwd_data_kernel>(kTorgbBwdMaxLds, "torgb_texels_bwd");
+  if (rc) return rc;
+  hipLaunchKernelGGL(torgb_bwd_data_kernel, dim3((unsigned)g.data_blocks, (unsigned)k.B), dim3(256), g.data_lds, s, k);
   if (k.g_weight) {
     REQUIRE(k.g_bias, "torgb_texels_bwd: g_bias missing");
     if (hipMemsetAsync(k.g_weight, 0, sizeof(float) * (size_t)kTorgbOut * k.Cin, s) != hipSuccess ||
         hipMemsetAsync(k.g_bias, 0, sizeof(float) * kTorgbOut, s) != hipSuccess)
       return fail(NFI_ERR_LAUNCH, "torgb_texels_bwd: memset failed");
-    const int groups_per_image = P / 16;
-    int64_t want = ((int64_t)k.B * groups_per_image + 3) / 4;
-    dim3 grid((unsigned)std::min<int64_t>(want, 256), (unsigned)((k.Cin + 63) / 64));
-    hipLaunchKernelGGL(torgb_bwd_weight_kernel, grid, dim3(256), 0, s, k, groups_per_image);
+    hipLaunchKernelGGL(torgb_bwd_weight_kernel, dim3((unsigned)g.weight_blocks, (unsigned)g.weight_groups), dim3(256), 0, s, k,
+                       k.R * k.R / 16);
   }
-  if (k.g_prev) {
-    const int half = k.R / 2;
-    const int64_t total = (int64_t)k.B * half * half * 24;
-    hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, k);
-  }
+  launch_upsample_bwd(k, s);
   return check_launch("torgb_texels_bwd");
 }
 
 // The workspace of one nfi_torgb_texels_bwd_ordered call: byte offsets of its regions and the total
-struct TorgbOrdCarve { size_t slots, part_w, part_b, total; int data_blocks, weight_blocks, weight_groups; };
+struct TorgbOrdCarve { size_t slots, part_w, part_b, total; };
 
-static bool torgb_shape_ok(const nfi_torgb_args* a) {
-  return a && a->n_scenes > 0 && a->in_channels >= 16 && a->in_channels <= kTorgbMaxCin && a->in_channels % 16 == 0 &&
-         a->resolution >= 8 && a->resolution <= 1024 && a->resolution % 8 == 0;
-}
-
-static TorgbOrdCarve torgb_ord_carve(const nfi_torgb_args* a) {
-  auto align256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+static TorgbOrdCarve torgb_ord_carve(const nfi_torgb_args* a, const TorgbBwdGrids& g) {
   TorgbOrdCarve c;
-  const int64_t P = (int64_t)a->resolution * a->resolution;
-  c.data_blocks = (int)((P + 64 * 4 * kTorgbTilesPerWave - 1) / (64 * 4 * kTorgbTilesPerWave));
-  c.weight_blocks = (int)std::min<int64_t>(((int64_t)a->n_scenes * (P / 16) + 3) / 4, 256);
-  c.weight_groups = (a->in_channels + 63) / 64;
   size_t at = 0;
-  c.slots = at; at += align256((size_t)a->n_scenes * c.data_blocks * 4 * a->in_channels * sizeof(float));
-  c.part_w = at; at += align256((size_t)c.weight_groups * c.weight_blocks * kTorgbOut * 64 * sizeof(float));
-  c.part_b = at; at += align256((size_t)c.weight_blocks * kTorgbOut * sizeof(float));
+  c.slots = at; at += align256((size_t)a->n_scenes * g.data_blocks * 4 * a->in_channels * sizeof(float));
+  c.part_w = at; at += align256((size_t)g.weight_groups * g.weight_blocks * kTorgbOut * 64 * sizeof(float));
+  c.part_b = at; at += align256((size_t)g.weight_blocks * kTorgbOut * sizeof(float));
   c.total = at;
   return c;
 }
 
 extern "C" size_t nfi_torgb_texels_bwd_ordered_workspace_bytes(const nfi_torgb_args* a) {
-  return torgb_shape_ok(a) ? torgb_ord_carve(a).total : 0;
+  return a && torgb_channels_ok(a) && torgb_resolution_ok(a) ? torgb_ord_carve(a, torgb_bwd_grids(a)).total : 0;
 }
 
 extern "C" int nfi_torgb_texels_bwd_ordered(const nfi_torgb_args* a, void* workspace, size_t workspace_bytes, nfi_stream_t stream) {
   TorgbParams k;
-  int rc = torgb_common(a, k);
+  int rc = torgb_bwd_common(a, k, "torgb_texels_bwd_ordered");
   if (rc) return rc;
-  REQUIRE(a->g_texels && a->g_x && a->g_styles, "torgb_texels_bwd_ordered: g_texels / g_x / g_styles missing");
-  REQUIRE(!a->g_previous_image || a->previous_image, "torgb_texels_bwd_ordered: g_previous_image without previous_image");
-  REQUIRE(!a->g_weight || a->g_bias, "torgb_texels_bwd_ordered: g_bias missing");
+  REQUIRE(!k.g_weight || k.g_bias, "torgb_texels_bwd_ordered: g_bias missing");
   REQUIRE(workspace, "torgb_texels_bwd_ordered: workspace missing");
-  const TorgbOrdCarve ws = torgb_ord_carve(a);
+  const TorgbBwdGrids g = torgb_bwd_grids(a);
+  const TorgbOrdCarve ws = torgb_ord_carve(a, g);
   REQUIRE(workspace_bytes >= ws.total, "torgb_texels_bwd_ordered: workspace too small");
-  k.g_out = a->g_texels; k.g_x = a->g_x; k.g_styles = a->g_styles; k.g_weight = a->g_weight; k.g_bias = a->g_bias;
-  k.g_prev = a->g_previous_image;
   hipStream_t s = (hipStream_t)stream;
-  char* const w = reinterpret_cast<char*>(workspace);
   // nothing here is read before this call has written it: every wave stores its slot, every block its partial
-  float* slots = reinterpret_cast<float*>(w + ws.slots);
-  float* part_w = reinterpret_cast<float*>(w + ws.part_w);
-  float* part_b = reinterpret_cast<float*>(w + ws.part_b);
-  const int P = k.R * k.R;
-  {
-    dim3 grid((unsigned)ws.data_blocks, (unsigned)k.B);
-    const size_t shmem = ((size_t)kTorgbOut * k.Cin + k.Cin) * sizeof(float);
-    rc = ensure_dynamic_lds<&torgb_bwd_data_ordered_kernel>(((size_t)kTorgbOut * kTorgbMaxCin + kTorgbMaxCin) * sizeof(float),
-                                                            "torgb_texels_bwd_ordered");
-    if (rc) return rc;
-    hipLaunchKernelGGL(torgb_bwd_data_ordered_kernel, grid, dim3(256), shmem, s, k, slots);
-    hipLaunchKernelGGL(torgb_bwd_styles_finish_kernel, dim3((unsigned)((k.B * k.Cin + 255) / 256)), dim3(256), 0, s, k, slots,
-                       ws.data_blocks * 4);
-  }
+  auto region = [&](size_t at) { return reinterpret_cast<float*>(static_cast<char*>(workspace) + at); };
+  float *slots = region(ws.slots), *part_w = region(ws.part_w), *part_b = region(ws.part_b);
+  rc = ensure_dynamic_lds<&torgb_bwd_data_ordered_kernel>(kTorgbBwdMaxLds, "torgb_texels_bwd_ordered");
+  if (rc) return rc;
+  hipLaunchKernelGGL(torgb_bwd_data_ordered_kernel, dim3((unsigned)g.data_blocks, (unsigned)k.B), dim3(256), g.data_lds, s, k, slots);
+  hipLaunchKernelGGL(torgb_bwd_styles_finish_kernel, dim3((unsigned)((k.B * k.Cin + 255) / 256)), dim3(256), 0, s, k, slots,
+                     g.data_blocks * 4);
   if (k.g_weight) {
-    dim3 grid((unsigned)ws.weight_blocks, (unsigned)ws.weight_groups);
-    hipLaunchKernelGGL(torgb_bwd_weight_ordered_kernel, grid, dim3(256), 0, s, k, P / 16, part_w, part_b);
+    hipLaunchKernelGGL(torgb_bwd_weight_ordered_kernel, dim3((unsigned)g.weight_blocks, (unsigned)g.weight_groups), dim3(256), 0, s,
+                       k, k.R * k.R / 16, part_w, part_b);
     hipLaunchKernelGGL(torgb_bwd_weight_finish_kernel, dim3((unsigned)((kTorgbOut * k.Cin + kTorgbOut + 255) / 256)), dim3(256), 0, s, k,
-                       part_w, part_b, ws.weight_blocks);
+                       part_w, part_b, g.weight_blocks);
   }
-  if (k.g_prev) {
-    const int half = k.R / 2;
-    const int64_t total = (int64_t)k.B * half * half * 24;
-    hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, k);
-  }
+  launch_upsample_bwd(k, s);
   return check_launch("torgb_texels_bwd_ordered");
 }

@@ -51,6 +51,7 @@ static int ensure_dynamic_lds(size_t bytes, const char* what) {
     if (!(cond)) return fail(NFI_ERR_INVALID_ARGUMENT, msg); \
   } while (0)
 
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }      // where a workspace region may start
 static inline int texel_bytes(int dtype) { return dtype == NFI_TEXEL_F32 ? 128 : 64; }
 
 // The run-time -> compile-time step of the kernel dispatchers: calls f(std::integral_constant<int, TEX>, std::bool_constant<ATT>)

@@ -635,12 +635,7 @@ __global__ __launch_bounds__(256) void sdf_ord_gather_kernel(SdfGradParams k) {
     const int c = l32 >> 1, ia = a - 1 + (c & 1), ib = b - 1 + (c >> 1);
     if (ia >= 0 && ib >= 0 && ia <= k.res - 2 && ib <= k.res - 2) {
       const uint64_t v = (uint64_t)((uint32_t)(ib * k.res + ia) + (uint32_t)(l32 & 1)) << 32;
-      int64_t lo = 0, hi = k.P;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < v) lo = mid + 1; else hi = mid;
-      }
-      bound = (int)lo;                        // P <= 2^25
+      bound = (int)ord_lower_bound(keys, k.P, v);       // P <= 2^25
     }
   }
   float total = 0.0f;
@@ -688,20 +683,14 @@ __global__ __launch_bounds__(256) void sdf_ord_gather_kernel(SdfGradParams k) {
   *dst += total;
 }
 
-// grid (kRgSlotFloats / 16), 256 threads = 16 slot offsets x 16 parts: a part sums a contiguous range of slots in index
-// order, part 0 adds the 16 partial sums in part order to the caller's buffer (param_finish_kernel's scheme)
+// grid (kRgSlotFloats / 16), 256 threads = 16 slot offsets x 16 parts: ordered_slot_sum over all slots, part 0 adds the sum
+// to the caller's buffer
 __global__ __launch_bounds__(256) void sdf_slot_finish_kernel(SdfGradParams k, int n_slots) {
   __shared__ float partial[16][16];
   const int e = threadIdx.x & 15, part = threadIdx.x >> 4;
   const int o = blockIdx.x * 16 + e;
-  const int s0 = (int)(((int64_t)n_slots * part) / 16), s1 = (int)(((int64_t)n_slots * (part + 1)) / 16);
-  float acc = 0.0f;
-  for (int s = s0; s < s1; ++s) acc += k.ord_slots[(size_t)s * kRgSlotFloats + o];
-  partial[part][e] = acc;
-  __syncthreads();
+  const float t = ordered_slot_sum(k.ord_slots, kRgSlotFloats, o, 0, n_slots, partial);
   if (part != 0) return;
-  float t = 0.0f;
-  for (int q = 0; q < 16; ++q) t += partial[q][e];
   if (o < kRgSlotB1) k.g_w1[o] += t;
   else if (o < kRgSlotW2) k.g_b1[o - kRgSlotB1] += t;
   else if (o < kRgSlotB2) k.g_w2[o - kRgSlotW2] += t;
@@ -777,21 +766,19 @@ extern "C" int nfi_sdf_gradient_bwd(const nfi_sdf_gradient_args* a, nfi_stream_t
 // The workspace of one nfi_sdf_gradient_bwd_ordered call: byte offsets of its regions and the total
 struct SdfOrdCarve { size_t df, v, flag, keys[2], hist, slots, total; int n_slots; };
 
-static size_t sdf_align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static SdfOrdCarve sdf_ord_carve(const nfi_sdf_gradient_args* a) {
   SdfOrdCarve c;
   memset(&c, 0, sizeof(c));
   const size_t n_pts = (size_t)a->n_scenes * (size_t)a->points_per_scene;
   c.n_slots = (int)(sdf_gradient_bwd_blocks(a) * a->n_scenes * 4);
   size_t at = 0;
-  c.df = at; at += sdf_align256(n_pts * kC * sizeof(float));
-  c.v = at; at += sdf_align256(n_pts * kC * sizeof(float));
-  c.flag = at; at += sdf_align256(n_pts);
-  c.keys[0] = at; at += sdf_align256(3 * n_pts * sizeof(uint64_t));
-  c.keys[1] = at; at += sdf_align256(3 * n_pts * sizeof(uint64_t));
-  c.hist = at; at += sdf_align256(ord_sort_plan(a->points_per_scene, a->n_scenes * 3, a->plane_res).hist_bytes);
-  c.slots = at; at += sdf_align256((size_t)c.n_slots * kRgSlotFloats * sizeof(float));
+  c.df = at; at += align256(n_pts * kC * sizeof(float));
+  c.v = at; at += align256(n_pts * kC * sizeof(float));
+  c.flag = at; at += align256(n_pts);
+  c.keys[0] = at; at += align256(3 * n_pts * sizeof(uint64_t));
+  c.keys[1] = at; at += align256(3 * n_pts * sizeof(uint64_t));
+  c.hist = at; at += align256(ord_sort_plan(a->points_per_scene, a->n_scenes * 3, a->plane_res).hist_bytes);
+  c.slots = at; at += align256((size_t)c.n_slots * kRgSlotFloats * sizeof(float));
   c.total = at;
   return c;
 }

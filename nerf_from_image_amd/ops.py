@@ -65,6 +65,15 @@ def _stream(t):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def _call_ordered(entry, struct, on, unsupported, args):
+    """An ordered entry with a workspace: the size from `entry`_workspace_bytes (0: RuntimeError(unsupported)), allocated per call."""
+    n_ws = _lib.struct_query(entry + '_workspace_bytes', struct, **args)
+    if n_ws == 0:
+        raise RuntimeError(unsupported)
+    ws = torch.empty((n_ws,), dtype=torch.uint8, device=on.device)
+    _lib.call_struct(entry, struct, _stream(on), ws, n_ws, **args)
+
+
 def _f32c(t, name):
     if t is None:
         return None
@@ -677,12 +686,8 @@ def sdf_gradient_bwd(points, texels, w1, b1, w2, b2, scene_range, g_sdf, g_gradi
                 g_gradient=_f32c(g_gradient, 'g_gradient'), **out)
     with torch.cuda.device(dev):
         if ordered:
-            n_ws = _lib.struct_query('nfi_sdf_gradient_bwd_ordered_workspace_bytes', 'nfi_sdf_gradient_args', **args)
-            if n_ws == 0:
-                raise RuntimeError('sdf_gradient_bwd(ordered=True): shape not supported (at most 2^25 points per scene): %s'
-                                   % ((B, P, texel_res(texels)),))
-            ws = torch.empty((n_ws,), dtype=torch.uint8, device=dev)
-            _lib.call_struct('nfi_sdf_gradient_bwd_ordered', 'nfi_sdf_gradient_args', _stream(points), ws, n_ws, **args)
+            _call_ordered('nfi_sdf_gradient_bwd_ordered', 'nfi_sdf_gradient_args', points, 'sdf_gradient_bwd(ordered=True): shape '
+                          'not supported (at most 2^25 points per scene): %s' % ((B, P, texel_res(texels)),), args)
         else:
             _lib.call_struct('nfi_sdf_gradient_bwd', 'nfi_sdf_gradient_args', _stream(points), **args)
     return out
@@ -902,11 +907,8 @@ def torgb_texels_bwd(g_out, x, styles, weight, previous_image=None, want_weight=
                 **out)
     with torch.cuda.device(dev):
         if ordered:
-            n_ws = _lib.struct_query('nfi_torgb_texels_bwd_ordered_workspace_bytes', 'nfi_torgb_args', **args)
-            if n_ws == 0:
-                raise RuntimeError('torgb_texels_bwd(ordered=True): shape not supported: %s' % ((B, Cin, R),))
-            ws = torch.empty((n_ws,), dtype=torch.uint8, device=dev)
-            _lib.call_struct('nfi_torgb_texels_bwd_ordered', 'nfi_torgb_args', _stream(x), ws, n_ws, **args)
+            _call_ordered('nfi_torgb_texels_bwd_ordered', 'nfi_torgb_args', x,
+                          'torgb_texels_bwd(ordered=True): shape not supported: %s' % ((B, Cin, R),), args)
         else:
             _lib.call_struct('nfi_torgb_texels_bwd', 'nfi_torgb_args', _stream(x), **args)
     return out

@@ -9,7 +9,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
-from nerf_from_image_amd import _lib, augment, ops  # noqa: E402
+from nerf_from_image_amd import _lib  # noqa: E402
+if os.environ.get('NFI_PROBE_LIBRARY'):          # a variant build, as tools/bench_regulariser.py
+    _lib.LIBRARY = os.environ['NFI_PROBE_LIBRARY']
+from nerf_from_image_amd import augment, ops  # noqa: E402
 
 
 def alternate(fns, n, warm=5):

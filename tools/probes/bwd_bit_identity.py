@@ -8,7 +8,15 @@ scatter modes, points_only, points_only + normalize_points; (2) every output of 
 working wave: its atomics are ordered) with per-point mixed scales, both scatter modes.  g_texels of the binned scatter is
 NOT reproducible from launch to launch (bin_reduce adds a cell's partial sums from several half-waves with atomics): it is
 launched eight more times, the number of distinct hashes is recorded, and it is compared with the atomic scatter by value.
-Record of round 10: profiles/r10/bit_identity_{parent,new}.json."""
+Record of round 10: profiles/r10/bit_identity_{parent,new}.json.
+
+    python tools/probes/bwd_bit_identity.py hash-ordered <libnfi_hip.so> <out.json>
+
+The ordered (bit-reproducible) backwards, whose every output is a pure function of its inputs: ops.torgb_texels_bwd(ordered=True)
+at the SHAPES of tests/test_handoff_warp_ordered.py with and without a previous image (and g_x / g_previous_image of the
+atomic entry: one writer per element), ops.sdf_gradient_bwd(ordered=True) at the launches of tests/test_regulariser_ordered.py
+and scatter_mode 2 at the cases of test_ordered_mode_repeats_bit_for_bit; inputs as those tests draw them.  `compare` as above.
+Record of round 20: profiles/r20/ordered_bits_{parent,tree}.json."""
 import hashlib
 import json
 import os
@@ -89,6 +97,54 @@ def hash_outputs(lib, out_path):
     print('%s: %d hashes' % (lib, len(out)))
 
 
+def hash_ordered(lib, out_path):
+    import torch
+    from nerf_from_image_amd import _lib
+    _lib.LIBRARY = os.path.abspath(lib)
+    from nerf_from_image_amd import ops
+    from nerf_from_image_amd.field_backward import field_query_bwd
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import test_handoff_warp_ordered as tho
+    import test_ordered_backward as tob
+    import test_regulariser_operator as tro
+    import test_regulariser_ordered as trd
+    dev = torch.device('cuda:0')
+
+    def sha(t):
+        return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()[:16]
+
+    out = {}
+    for shape in tho.SHAPES:
+        B, Cin, R = shape
+        g = torch.Generator().manual_seed(B * 1000 + Cin + R)            # handoff_case's draws, without its float64 reference
+        t = dict(x=torch.randn(B, Cin, R, R, generator=g), s=torch.randn(B, Cin, generator=g) / Cin ** 0.5,
+                 w=torch.randn(96, Cin, generator=g), bias=torch.randn(96, generator=g),
+                 prev=torch.randn(B, 96, R // 2, R // 2, generator=g), up=torch.randn(B, 96, R, R, generator=g))
+        for has_prev in (False, True):
+            for k, v in sorted(tho.handoff_bwd(t, dev, has_prev, True, True).items()):
+                out['torgb ordered %s prev %d %s' % (shape, has_prev, k)] = sha(v)
+            atomic = tho.handoff_bwd(t, dev, has_prev, True, False)
+            for k in ('g_x', 'g_previous_image'):
+                if k in atomic:
+                    out['torgb atomic %s prev %d %s' % (shape, has_prev, k)] = sha(atomic[k])
+    for name, interleaved in trd.LAUNCHES:
+        c = tro.CASE[name]
+        t = tro.scene(c)
+        texels = tro.texels_of(t, dev, interleaved)
+        got = ops.sdf_gradient_bwd(t['x'].to(dev), texels, t['w1'].to(dev), t['b1'].to(dev), t['w2'].to(dev), t['b2'].to(dev),
+                                   tro.range_of(c), t['u_d'].to(dev), t['u_g'].to(dev), ordered=True)
+        for k, v in sorted(got.items()):
+            out['sdf_gradient ordered %s%s %s' % (name, ' interleaved' if interleaved else '', k)] = sha(v)
+    cases = [m for m in tob.test_ordered_mode_repeats_bit_for_bit.pytestmark if m.name == 'parametrize'][0].args[1]
+    for i, (B, P, kw, ray_order) in enumerate(cases):
+        got = field_query_bwd(*tob.scatter_case(dev, P, 24, B=B, **kw), want_points=True, scatter_mode=2, ray_order=ray_order)
+        for k, v in sorted(got.items()):
+            out['field scatter 2 case %d %s' % (i, k)] = sha(v)
+    torch.cuda.synchronize()
+    json.dump(out, open(out_path, 'w'), indent=1, sort_keys=True)
+    print('%s: %d hashes' % (lib, len(out)))
+
+
 def compare(pa, pb):
     a, b = json.load(open(pa)), json.load(open(pb))
     skip = lambda k: 'distinct hashes' in k or (k.endswith('scatter 1 g_texels') and (a.get(k + ', distinct hashes in 8 more launches', 1) > 1))
@@ -106,5 +162,7 @@ def compare(pa, pb):
 if __name__ == '__main__':
     if sys.argv[1] == 'hash':
         hash_outputs(sys.argv[2], sys.argv[3])
+    elif sys.argv[1] == 'hash-ordered':
+        hash_ordered(sys.argv[2], sys.argv[3])
     else:
         compare(sys.argv[2], sys.argv[3])
