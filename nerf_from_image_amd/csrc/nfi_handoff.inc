@@ -582,6 +582,7 @@ extern "C" int nfi_torgb_texels_bwd(const nfi_torgb_args* a, nfi_stream_t stream
   TorgbParams k;
   int rc = torgb_bwd_common(a, k, "torgb_texels_bwd");
   if (rc) return rc;
+  REQUIRE(!k.g_weight || k.g_bias, "torgb_texels_bwd: g_bias missing");      // before the first memset and launch
   const TorgbBwdGrids g = torgb_bwd_grids(a);
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(k.g_styles, 0, sizeof(float) * (size_t)k.B * k.Cin, s) != hipSuccess) return fail(NFI_ERR_LAUNCH, "torgb_texels_bwd: memset failed");
@@ -589,7 +590,6 @@ extern "C" int nfi_torgb_texels_bwd(const nfi_torgb_args* a, nfi_stream_t stream
   if (rc) return rc;
   hipLaunchKernelGGL(torgb_bwd_data_kernel, dim3((unsigned)g.data_blocks, (unsigned)k.B), dim3(256), g.data_lds, s, k);
   if (k.g_weight) {
-    REQUIRE(k.g_bias, "torgb_texels_bwd: g_bias missing");
     if (hipMemsetAsync(k.g_weight, 0, sizeof(float) * (size_t)kTorgbOut * k.Cin, s) != hipSuccess ||
         hipMemsetAsync(k.g_bias, 0, sizeof(float) * kTorgbOut, s) != hipSuccess)
       return fail(NFI_ERR_LAUNCH, "torgb_texels_bwd: memset failed");
