@@ -1094,28 +1094,80 @@ __device__ __forceinline__ void normal_contraction(const FieldParams& P, int lan
 //         other waves (tools/probes/mfma_valu_overlap.hip), so this time comes straight off the kernel.
 // NRM: Gout[n][ct] receives G = W1'^T (sigmoid(h) * W2'[0]) of tile n - d(distance) / d(feature) up to the positive factors
 // the normalisation drops -, rows 16 ct + 4 g + r of point j: the operand of the normal map (field_wave).
+// The split-fp16 decoder's first operands - the bias fragment and the W1' hi / lo fragments of hidden-unit group 0 -, fetched
+// by the caller ahead of the decoder (mlp_head_fetch): behind field_wave's last transpose read they return together with
+// it, and tile_mlp opens on MFMAs instead of on a wait for its own reads.
+struct MlpHead {
+  f32x4 b1;
+  f16x8 wh, wl;
+};
+__device__ __forceinline__ f16x8 lds_w1_frag(const FieldParams& P, int lane, int frag) {
+  return __builtin_bit_cast(f16x8, reinterpret_cast<const u32x4*>(P.lds)[(kW1H_lds >> 2) + frag * 64 + lane]);
+}
+__device__ __forceinline__ f16x8 lds_w2_frag(const FieldParams& P, int lane, int frag) {
+  return __builtin_bit_cast(f16x8, reinterpret_cast<const u32x4*>(P.lds)[(kW2H_lds >> 2) + frag * 64 + lane]);
+}
+__device__ __forceinline__ void mlp_head_fetch(const FieldParams& P, int lane, MlpHead& H) {
+  H.b1 = reinterpret_cast<const f32x4*>(P.lds)[(kB1F >> 2) + (lane >> 4) * 4];
+  H.wh = lds_w1_frag(P, lane, 0);
+  H.wl = lds_w1_frag(P, lane, 1);
+}
+// MFMAs and LDS operations stay on their side of this line, plain vector and scalar work may cross it: the operand reads of
+// the NEXT MFMA group stay in front of the current group's MFMAs (tile_mlp), the softplus still fills the gaps between MFMAs
+__device__ __forceinline__ void mfma_lds_line() { __builtin_amdgcn_sched_barrier(0x0002 | 0x0004 | 0x0400); }
+
 template <int N, int PREC, bool NRM = false>
 __device__ __forceinline__ void tile_mlp(const FieldParams& P, int lane, const float (&feat)[N][8], f32x4 (&o)[N],
-                                         f32x4 (&Gout)[N][2]) {
+                                         f32x4 (&Gout)[N][2], const MlpHead* head = nullptr) {
   const int g = lane >> 4;
   const f32x4* ldsv = reinterpret_cast<const f32x4*>(P.lds);
   if constexpr (PREC == 1) {
-    const u32x4* ldsu = reinterpret_cast<const u32x4*>(P.lds);
+    // every operand fragment is read one MFMA group ahead of its use (the first by the caller where it can: MlpHead); the
+    // normal map's kernels, whose registers are spoken for through the softplus and the contraction, read them at their use
+    constexpr bool AHEAD = !NRM;
+    MlpHead own;
+    if (AHEAD && head == nullptr) mlp_head_fetch(P, lane, own);
+    const MlpHead& H = head ? *head : own;
     f16x8 fh[N], fl[N];
 #pragma unroll
     for (int n = 0; n < N; ++n) split_f16x8(feat[n], fh[n], fl[n]);
     f32x4 acc1[N][4];
+    f32x4 b;
+    f16x8 wh, wl;
+    if constexpr (AHEAD) { b = H.b1; wh = H.wh; wl = H.wl; }
+    f32x4 b2;
+    f16x8 w2h[2], w2l[2];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
-      const f32x4 b = ldsv[(kB1F >> 2) + g * 4 + nt];
-      const f16x8 wh = __builtin_bit_cast(f16x8, ldsu[(kW1H_lds >> 2) + (nt * 2 + 0) * 64 + lane]);
-      const f16x8 wl = __builtin_bit_cast(f16x8, ldsu[(kW1H_lds >> 2) + (nt * 2 + 1) * 64 + lane]);
+      f32x4 bn;
+      f16x8 whn, wln;
+      if constexpr (AHEAD) {
+        if (nt < 3) {
+          bn = ldsv[(kB1F >> 2) + g * 4 + nt + 1];
+          whn = lds_w1_frag(P, lane, (nt + 1) * 2 + 0);
+          wln = lds_w1_frag(P, lane, (nt + 1) * 2 + 1);
+        } else {
+          // layer 2's first operands, under the last group and the softplus
+          b2 = ldsv[(kB2F >> 2) + g];
+          w2h[0] = lds_w2_frag(P, lane, 0);
+          w2l[0] = lds_w2_frag(P, lane, 1);
+        }
+        mfma_lds_line();
+      } else {
+        b = ldsv[(kB1F >> 2) + g * 4 + nt];
+        wh = lds_w1_frag(P, lane, nt * 2 + 0);
+        wl = lds_w1_frag(P, lane, nt * 2 + 1);
+      }
 #pragma unroll
       for (int n = 0; n < N; ++n) acc1[n][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, fh[n], b, 0, 0, 0);
 #pragma unroll
       for (int n = 0; n < N; ++n) acc1[n][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, fl[n], acc1[n][nt], 0, 0, 0);
 #pragma unroll
       for (int n = 0; n < N; ++n) acc1[n][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, fh[n], acc1[n][nt], 0, 0, 0);
+      if constexpr (AHEAD) {
+        mfma_lds_line();
+        if (nt < 3) { b = bn; wh = whn; wl = wln; }
+      }
     }
 #pragma unroll
     for (int n = 0; n < N; ++n) {
@@ -1140,13 +1192,20 @@ __device__ __forceinline__ void tile_mlp(const FieldParams& P, int lane, const f
       // (right behind this tile's softplus, so that GH never outlives it)
       if constexpr (NRM) normal_contraction(P, lane, gh, Gout[n][0], Gout[n][1]);
     }
-    const f32x4 b2 = ldsv[(kB2F >> 2) + g];
+    if constexpr (!AHEAD) b2 = ldsv[(kB2F >> 2) + g];
 #pragma unroll
     for (int n = 0; n < N; ++n) o[n] = b2;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const f16x8 wh = __builtin_bit_cast(f16x8, ldsu[(kW2H_lds >> 2) + (kk * 2 + 0) * 64 + lane]);
-      const f16x8 wl = __builtin_bit_cast(f16x8, ldsu[(kW2H_lds >> 2) + (kk * 2 + 1) * 64 + lane]);
+      if constexpr (AHEAD) {
+        if (kk == 0) {
+          w2h[1] = lds_w2_frag(P, lane, 2);
+          w2l[1] = lds_w2_frag(P, lane, 3);
+          mfma_lds_line();
+        }
+      }
+      const f16x8 wh2 = AHEAD ? w2h[kk] : lds_w2_frag(P, lane, kk * 2 + 0);
+      const f16x8 wl2 = AHEAD ? w2l[kk] : lds_w2_frag(P, lane, kk * 2 + 1);
       f16x8 sh[N], sl[N];
 #pragma unroll
       for (int n = 0; n < N; ++n) {
@@ -1155,11 +1214,11 @@ __device__ __forceinline__ void tile_mlp(const FieldParams& P, int lane, const f
         split_f16x8(x, sh[n], sl[n]);
       }
 #pragma unroll
-      for (int n = 0; n < N; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, sh[n], o[n], 0, 0, 0);
+      for (int n = 0; n < N; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh2, sh[n], o[n], 0, 0, 0);
 #pragma unroll
-      for (int n = 0; n < N; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, sl[n], o[n], 0, 0, 0);
+      for (int n = 0; n < N; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh2, sl[n], o[n], 0, 0, 0);
 #pragma unroll
-      for (int n = 0; n < N; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, sh[n], o[n], 0, 0, 0);
+      for (int n = 0; n < N; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl2, sh[n], o[n], 0, 0, 0);
     }
   } else {
     // ---- layer 1: H^T[64 x 16] = W1'[64 x 32] * F^T[32 x 16], bias pre-loaded, log2 domain ----
@@ -1377,30 +1436,21 @@ __device__ __forceinline__ SampleOut field_wave(const FieldParams& P, float scen
   // chunk q of L and channel group g of M hold the same channels, so the W1 operand image is
   // independent of this choice.
   const int lp = lane >> 2, lq = lane & 3;        // L layout
-  // gather + interpolation + L->M transpose of one tile; returns the tile's flags for this lane's point (the per-tile
-  // epilogue's; with the output table `outside` and `valid` are the sample lane's own and nothing is fetched)
-  auto gather_tile = [&](int t, float (&feat)[8]) -> int {
-    const int srcL = 16 * t + lp, srcM = 16 * t + j;
-    const float cfx = __shfl(fx, srcL, 64), cfy = __shfl(fy, srcL, 64), cfz = __shfl(fz, srcL, 64);
-    const uint32_t cxi = (uint32_t)__shfl(xi, srcL, 64);
-    const int fcur = OTAB ? 0 : __shfl(flags, srcM, 64);
-    float featL[8];
-    TileTex<TEX> T;
-    tile_issue<TEX>(P, lq, cxi, T);
-    tile_bilinear<TEX>(T, cfx, cfy, cfz, featL);
+  // the two halves of a tile's L -> M transpose (the plain schedule below issues them apart), each closed by the wave's
+  // ordering point: the reads see the writes, and the next tile's writes stay behind the reads
+  auto stage_write = [&](const float (&featL)[8]) {
     // pitch 36 floats: conflict-free for both the 16-byte writes and the 16-byte reads
-    __builtin_amdgcn_sched_barrier(0);
     f32x4* wr = reinterpret_cast<f32x4*>(stage + lp * 36 + lq * 4);
     wr[0] = f32x4{featL[0], featL[1], featL[2], featL[3]};
     wr[4] = f32x4{featL[4], featL[5], featL[6], featL[7]};
     wave_lds_fence();
+  };
+  auto stage_read = [&](float (&feat)[8]) {
     const f32x4* rd = reinterpret_cast<const f32x4*>(stage + j * 36 + g * 4);
     const f32x4 lo = rd[0], hi = rd[4];
     feat[0] = lo.x; feat[1] = lo.y; feat[2] = lo.z; feat[3] = lo.w;
     feat[4] = hi.x; feat[5] = hi.y; feat[6] = hi.z; feat[7] = hi.w;
     wave_lds_fence();
-    __builtin_amdgcn_sched_barrier(0);
-    return fcur;
   };
   // a point's semantics: row [A] of the global output, or its column of the wave's LDS table (SEMP > 0)
   // (SEMP < 0: a table of 16-bit entries - the pointer only carries the column's address to tile_epilogue)
@@ -1543,14 +1593,43 @@ __device__ __forceinline__ SampleOut field_wave(const FieldParams& P, float scen
     // same pipe (measured, images identical: fp16 texels 3 workgroups per CU -2 % chairs-like / -3 % every ray hits, fp32
     // -0.2 .. -0.7 %; raising the MLP half instead: nothing)
     __builtin_amdgcn_s_setprio(3);
-    const int fa = gather_tile(ta, feat[0]);
-    int fb = fa;
-    if (pair) {
-      fb = gather_tile(tb, feat[1]);
-    } else {
-#pragma unroll
-      for (int s8 = 0; s8 < 8; ++s8) feat[1][s8] = feat[0][s8];
+    // The order of a turn: BOTH tiles' operands come over in front of one wait; tile a is fetched and blended; tile b's 24
+    // loads go out; and only then do tile a's features take the L -> M round trip through `stage`, under tile b's memory
+    // latency.  (LDS operations of a wave execute in issue order: tile b's writes to `stage` cannot pass tile a's reads.)
+    const int srcLa = 16 * ta + lp, srcLb = 16 * tb + lp;
+    const uint32_t cxa = (uint32_t)__shfl(xi, srcLa, 64);
+    const float fxa = __shfl(fx, srcLa, 64), fya = __shfl(fy, srcLa, 64), fza = __shfl(fz, srcLa, 64);
+    const uint32_t cxb = (uint32_t)__shfl(xi, srcLb, 64);
+    const float fxb = __shfl(fx, srcLb, 64), fyb = __shfl(fy, srcLb, 64), fzb = __shfl(fz, srcLb, 64);
+    const int fa = OTAB ? 0 : __shfl(flags, 16 * ta + j, 64);
+    const int fb = OTAB ? 0 : __shfl(flags, 16 * tb + j, 64);
+    float featL[8];
+    {
+      TileTex<TEX> T;
+      tile_issue<TEX>(P, lq, cxa, T);
+      tile_bilinear<TEX>(T, fxa, fya, fza, featL);
     }
+    __builtin_amdgcn_sched_barrier(0);
+    if (pair) {
+      TileTex<TEX> T;
+      tile_issue<TEX>(P, lq, cxb, T);
+      __builtin_amdgcn_sched_barrier(0);
+      stage_write(featL);
+      stage_read(feat[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      tile_bilinear<TEX>(T, fxb, fyb, fzb, featL);
+      __builtin_amdgcn_sched_barrier(0);
+      stage_write(featL);
+      stage_read(feat[1]);
+    } else {
+      stage_write(featL);
+      stage_read(feat[0]);
+      stage_read(feat[1]);     // (the unpaired last turn runs tile a in both slots; it has fetched tile a's operands twice)
+    }
+    // the decoder's first operand group goes out with the last transpose read, in front of the half's last wait
+    MlpHead head;
+    if constexpr (PREC == 1 && !VD) mlp_head_fetch(P, lane, head);
+    __builtin_amdgcn_sched_barrier(0);
     unsigned long long c2 = prof ? __builtin_readcyclecounter() : 0;
     __builtin_amdgcn_s_setprio(0);
     // (the per-tile epilogue's operands, where they have always been made: ahead of the decoder)
@@ -1570,7 +1649,7 @@ __device__ __forceinline__ SampleOut field_wave(const FieldParams& P, float scen
       }
       tile_mlp_vd<2, false>(P, lane, feat, xr, o, Gp);
     } else {
-      tile_mlp<2, PREC, false>(P, lane, feat, o, Gp);
+      tile_mlp<2, PREC, false>(P, lane, feat, o, Gp, PREC == 1 ? &head : nullptr);
     }
     if constexpr (OTAB) {
       park_tile_outputs<ATT>(otab, lane, ta, o[0]);
