@@ -661,6 +661,37 @@ typedef struct nfi_metrics_args {
 } nfi_metrics_args;
 int nfi_image_metrics(const nfi_metrics_args* a, nfi_stream_t stream);
 
+/* SSIM of the same loops: lib/metrics.py:48-76 ssim, per image - skimage.metrics.structural_similarity(channel_axis=0,
+ * data_range=1.) with its other arguments at their defaults, on inputs clamped to [0,1].  Per channel, with u(.) the 7 x 7
+ * box mean, v. = (49/48) (u(..) - u(.) u(.)), C1 = 1e-4, C2 = 9e-4:
+ *   S = ((2 ux uy + C1) (2 vxy + C2)) / ((ux^2 + uy^2 + C1) (vx + vy + C2)),
+ * averaged over the window centres at least 3 pixels from every edge ((H-6) x (W-6) values: no padding rule enters), then
+ * over the three channels.  fp32 per window (the sums are taken about a per-tile pivot, so flat regions do not cancel),
+ * float64 from the tile sums on.  One block per (image, channel, tile of 16 x 32 centres) writes one partial sum; a second
+ * kernel adds them in index order: no float atomics, the same bits on every launch, and an image's value does not depend
+ * on the batch around it.  No allocation, no synchronisation.
+ *   n_images, height, width: B >= 1, H >= 7, W >= 7 (lib/metrics.py:48-76: scikit-image raises below one window).
+ *   pred / target: B x 3 x H x W values, each dense in its own layout (lib/metrics.py:48-76 asserts [B,3,H,W]):
+ *   pred_layout / target_layout 0 = [B,3,H,W], 1 = [B,H,W,3] (what run.py's permute(0,3,1,2) of a render is in memory).
+ *   ssim [B] (required); ssim_map [B,3,H-6,W-6] or NULL: S per window centre, the cropped map of lib/metrics.py:48-76's
+ *   call with full=True.  out_of_range (int, optional): 1 if any input violates the range_check lib/metrics.py:48-76
+ *   runs on both inputs (-0.1 < v < 1.1, so a NaN is flagged), 0 otherwise.
+ *   workspace: device memory, 8-byte aligned, need not be zeroed; nfi_image_ssim_workspace_bytes reads n_images, height
+ *   and width alone (one double per block) and returns 0 for a shape the call refuses.
+ * Refused before any launch (-1, nfi_last_error()): a null argument / pred / target / ssim, n_images < 1, a side under
+ * 7, a layout other than 0 or 1, a missing, too small or misaligned workspace. */
+typedef struct nfi_ssim_args {
+  int n_images, height, width;
+  const float* pred; int pred_layout;
+  const float* target; int target_layout;
+  float* ssim;
+  float* ssim_map;
+  int* out_of_range;
+  void* workspace; size_t workspace_bytes;
+} nfi_ssim_args;
+size_t nfi_image_ssim_workspace_bytes(const nfi_ssim_args* a);
+int nfi_image_ssim(const nfi_ssim_args* a, nfi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * View-direction mapper, the per-ray trunk.  Replaces ViewDirectionMapper.__init__'s layers as forward runs them
  * (models/generator.py:194-241: fc0 .. fc6, norm1 .. norm4, two residual joins scaled by sqrt(2)/2, LeakyReLU(0.2);

@@ -8,6 +8,8 @@
 // (2) PSNR and mask IoU of lib/metrics.py:30-45 / 79-94 (the monitors of the inversion loop, run.py:2077-2090,
 //     2247): range check, clamp, per-image mean squared error -> -10 log10, clamp at 60 dB; thresholded masks ->
 //     (intersection + 1e-6) / (union + 1e-6).  One launch, one block per image, no intermediate tensors.
+// (3) SSIM of lib/metrics.py:48-76 (called beside them, run.py:2076-2088, 1275-1283): range check, clamp, the five 7 x 7
+//     box sums formed separably in LDS per tile of window centres, one partial per block, an ordered finish.
 
 struct WarpParams {
   const float* img; float* out;            // [N,C,H,W]
@@ -282,4 +284,162 @@ extern "C" int nfi_image_metrics(const nfi_metrics_args* a, nfi_stream_t stream)
                  a->psnr, a->iou, a->out_of_range};
   hipLaunchKernelGGL(image_metrics_kernel, dim3((unsigned)a->n_images), dim3(256), 0, s, k);
   return check_launch("image_metrics");
+}
+
+// ------------------------------------------------------------------------------------------------
+// SSIM (lib/metrics.py:48-76): one block per (image, channel, tile of window centres), then one wave per image
+// ------------------------------------------------------------------------------------------------
+constexpr int kSsimWin = 7, kSsimHalo = kSsimWin - 1;
+// A tile of 16 x 32 window centres: a half wave (the unit of LDS banking for 4-byte reads) walks one row of 32 consecutive
+// words in both passes, so neither pass has a bank conflict; 20.8 KB of LDS per block leaves 7 blocks (28 waves) on a CU.
+constexpr int kSsimTileH = 16, kSsimTileW = 32;
+constexpr int kSsimInH = kSsimTileH + kSsimHalo, kSsimInW = kSsimTileW + kSsimHalo;        // 22 x 38 staged pixels
+static_assert(kSsimTileW == 32 && kSsimTileH * kSsimTileW == 2 * 256, "ssim_tile_kernel: two window centres per thread, 32 per row");
+
+struct SsimParams {
+  const float* pred; const float* target;
+  size_t pred_image, pred_channel, pred_row, pred_pixel;          // element strides of (image, channel, row, column)
+  size_t target_image, target_channel, target_row, target_pixel;
+  int H, W, tiles_x, tiles;                                        // tiles = tiles_x * tiles_y, per image and channel
+  double* partial;                                                 // [B,3,tiles]
+  float* map;                                                      // [B,3,H-6,W-6] or null
+  float* ssim;                                                     // [B]
+  int* out_of_range;
+};
+
+static void ssim_strides(int layout, int H, int W, size_t& image, size_t& channel, size_t& row, size_t& pixel) {
+  image = (size_t)3 * H * W;
+  if (layout == 0) { channel = (size_t)H * W; row = (size_t)W; pixel = 1; }
+  else { channel = 1; row = (size_t)3 * W; pixel = 3; }
+}
+
+__global__ __launch_bounds__(256) void ssim_tile_kernel(SsimParams k) {
+  __shared__ float sx[kSsimInH][kSsimInW], sy[kSsimInH][kSsimInW];
+  __shared__ float rows[5][kSsimInH][kSsimTileW];                  // the five sums over 7 columns, per staged row
+  __shared__ double red[4];
+  const int tile = blockIdx.x % k.tiles, plane = blockIdx.x / k.tiles;        // plane = image * 3 + channel
+  const int img = plane / 3, ch = plane - 3 * img;
+  const int y0 = (tile / k.tiles_x) * kSsimTileH, x0 = (tile % k.tiles_x) * kSsimTileW;
+  const float* X = k.pred + (size_t)img * k.pred_image + (size_t)ch * k.pred_channel;
+  const float* Y = k.target + (size_t)img * k.target_image + (size_t)ch * k.target_channel;
+  auto unit = [](float v) { return fminf(fmaxf(v, 0.0f), 1.0f); };
+  // The sums are taken of (value - pivot), the pivot being the tile's own middle pixel: variances and the covariance do not
+  // move with a shift, and on a flat background every term is exactly 0 where sum(x^2)/49 - mean^2 would cancel to noise of
+  // the size of C2.  The pivot depends on the image and the tile alone, never on the batch.
+  const int py = min(y0 + kSsimInH / 2, k.H - 1), px = min(x0 + kSsimInW / 2, k.W - 1);
+  const float pivot_x = unit(X[(size_t)py * k.pred_row + (size_t)px * k.pred_pixel]);
+  const float pivot_y = unit(Y[(size_t)py * k.target_row + (size_t)px * k.target_pixel]);
+  int bad = 0;
+  for (int i = threadIdx.x; i < kSsimInH * kSsimInW; i += 256) {
+    const int r = i / kSsimInW, c = i - r * kSsimInW;
+    const int gy = y0 + r, gx = x0 + c;
+    float a = 0.0f, b = 0.0f;
+    if (gy < k.H && gx < k.W) {
+      const float xv = X[(size_t)gy * k.pred_row + (size_t)gx * k.pred_pixel];
+      const float yv = Y[(size_t)gy * k.target_row + (size_t)gx * k.target_pixel];
+      // lib/metrics.py range_check: values must lie in (-0.1, 1.1); a NaN fails both comparisons
+      if (!(xv < 1.1f) || !(xv > -0.1f) || !(yv < 1.1f) || !(yv > -0.1f)) bad = 1;
+      a = unit(xv) - pivot_x;
+      b = unit(yv) - pivot_y;
+    }
+    sx[r][c] = a;
+    sy[r][c] = b;
+  }
+  if (k.out_of_range && bad) atomicOr(k.out_of_range, 1);
+  __syncthreads();
+  for (int i = threadIdx.x; i < kSsimInH * kSsimTileW; i += 256) {
+    const int r = i >> 5, c = i & 31;
+    float s_x = 0.0f, s_y = 0.0f, s_xx = 0.0f, s_yy = 0.0f, s_xy = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kSsimWin; ++j) {
+      const float a = sx[r][c + j], b = sy[r][c + j];
+      s_x += a; s_y += b; s_xx += a * a; s_yy += b * b; s_xy += a * b;
+    }
+    rows[0][r][c] = s_x; rows[1][r][c] = s_y; rows[2][r][c] = s_xx; rows[3][r][c] = s_yy; rows[4][r][c] = s_xy;
+  }
+  __syncthreads();
+  // each thread: the window centres (oy, ox) and (oy + 1, ox), which share six of their seven rows
+  const int ox = threadIdx.x & 31, oy = 2 * (threadIdx.x >> 5);
+  float lo[5], hi[5];
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    float mid = rows[q][oy + 1][ox];
+#pragma unroll
+    for (int j = 2; j < kSsimWin; ++j) mid += rows[q][oy + j][ox];
+    lo[q] = rows[q][oy][ox] + mid;
+    hi[q] = mid + rows[q][oy + kSsimWin][ox];
+  }
+  const int out_h = k.H - kSsimHalo, out_w = k.W - kSsimHalo;
+  double acc = 0.0;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const float* s = t ? hi : lo;
+    const int gy = y0 + oy + t, gx = x0 + ox;
+    if (gy < out_h && gx < out_w) {
+      const float n = (float)(kSsimWin * kSsimWin), c1 = 1e-4f, c2 = 9e-4f;      // (0.01 R)^2, (0.03 R)^2 at data_range R = 1
+      const float mx = s[0] / n, my = s[1] / n;
+      const float ux = pivot_x + mx, uy = pivot_y + my;
+      const float vx = (s[2] - s[0] * mx) / (n - 1.0f), vy = (s[3] - s[1] * my) / (n - 1.0f), vxy = (s[4] - s[0] * my) / (n - 1.0f);
+      const float v = ((2.0f * ux * uy + c1) * (2.0f * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2));
+      if (k.map) k.map[((size_t)plane * out_h + gy) * out_w + gx] = v;
+      acc += (double)v;
+    }
+  }
+  acc = block_sum_f64(acc, red);
+  if (threadIdx.x == 0) k.partial[blockIdx.x] = acc;
+}
+
+// One wave per image adds that image's partials, channel by channel: lane l takes tiles l, l + 64, ... in that order, then
+// the lanes are combined by the same butterfly every time.
+__global__ __launch_bounds__(64) void ssim_finish_kernel(SsimParams k) {
+  const int img = blockIdx.x;
+  const double count = (double)(k.H - kSsimHalo) * (double)(k.W - kSsimHalo);
+  double value = 0.0;
+  for (int ch = 0; ch < 3; ++ch) {
+    const double* p = k.partial + ((size_t)img * 3 + ch) * k.tiles;
+    double v = 0.0;
+    for (int i = threadIdx.x; i < k.tiles; i += 64) v += p[i];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    value += v / count;
+  }
+  if (threadIdx.x == 0) k.ssim[img] = (float)(value / 3.0);
+}
+
+// tiles per (image, channel), or 0 for a shape nfi_image_ssim refuses
+static int64_t ssim_tiles(const nfi_ssim_args* a, int* tiles_x) {
+  if (!a || a->n_images < 1 || a->height < kSsimWin || a->width < kSsimWin) return 0;
+  const int64_t tx = (a->width - kSsimHalo + kSsimTileW - 1) / kSsimTileW, ty = (a->height - kSsimHalo + kSsimTileH - 1) / kSsimTileH;
+  if (tx * ty * 3 * a->n_images >= ((int64_t)1 << 31)) return 0;
+  if (tiles_x) *tiles_x = (int)tx;
+  return tx * ty;
+}
+
+extern "C" size_t nfi_image_ssim_workspace_bytes(const nfi_ssim_args* a) {
+  return (size_t)ssim_tiles(a, nullptr) * 3 * (a ? (size_t)a->n_images : 0) * sizeof(double);
+}
+
+extern "C" int nfi_image_ssim(const nfi_ssim_args* a, nfi_stream_t stream) {
+  REQUIRE(a && a->pred && a->target && a->ssim, "image_ssim: null pointer");
+  REQUIRE(a->n_images >= 1, "image_ssim: n_images must be at least 1");
+  REQUIRE(a->height >= kSsimWin && a->width >= kSsimWin, "image_ssim: height and width must hold one 7 x 7 window");
+  REQUIRE((a->pred_layout == 0 || a->pred_layout == 1) && (a->target_layout == 0 || a->target_layout == 1),
+          "image_ssim: layout must be 0 ([B,3,H,W]) or 1 ([B,H,W,3])");
+  SsimParams k;
+  memset(&k, 0, sizeof(k));
+  k.tiles = (int)ssim_tiles(a, &k.tiles_x);
+  REQUIRE(k.tiles > 0, "image_ssim: more than 2^31 tiles");
+  REQUIRE(a->workspace, "image_ssim: workspace missing");
+  REQUIRE(a->workspace_bytes >= nfi_image_ssim_workspace_bytes(a), "image_ssim: workspace too small");
+  REQUIRE(((uintptr_t)a->workspace & 7) == 0, "image_ssim: workspace must be 8-byte aligned");
+  k.pred = a->pred; k.target = a->target; k.H = a->height; k.W = a->width;
+  ssim_strides(a->pred_layout, k.H, k.W, k.pred_image, k.pred_channel, k.pred_row, k.pred_pixel);
+  ssim_strides(a->target_layout, k.H, k.W, k.target_image, k.target_channel, k.target_row, k.target_pixel);
+  k.partial = (double*)a->workspace; k.map = a->ssim_map; k.ssim = a->ssim; k.out_of_range = a->out_of_range;
+  hipStream_t s = (hipStream_t)stream;
+  if (a->out_of_range && hipMemsetAsync(a->out_of_range, 0, sizeof(int), s) != hipSuccess)
+    return fail(NFI_ERR_LAUNCH, "image_ssim: memset failed");
+  hipLaunchKernelGGL(ssim_tile_kernel, dim3((unsigned)(k.tiles * 3 * a->n_images)), dim3(256), 0, s, k);
+  hipLaunchKernelGGL(ssim_finish_kernel, dim3((unsigned)a->n_images), dim3(64), 0, s, k);
+  return check_launch("image_ssim");
 }

@@ -835,9 +835,22 @@ def affine_warp_bwd(g_out, rot, scale, translation, white_background=False, orde
     return g_img
 
 
-def image_metrics(pred=None, target=None, mask_pred=None, mask_real=None, check_range=True):
+def _range_flag(check_range, flag, dev):
+    """The out_of_range word of a metrics call: None, a fresh int32 [1], or the caller's own (one element of a tensor that
+    gathers the flags of several calls, so that they reach the host in one read)."""
+    if not check_range:
+        return None
+    if flag is None:
+        return torch.empty((1,), dtype=torch.int32, device=dev)
+    if not flag.is_cuda or flag.device != dev or flag.dtype != torch.int32 or flag.numel() != 1:
+        raise ValueError('out_of_range must be one int32 element on %s' % (dev,))
+    return flag
+
+
+def image_metrics(pred=None, target=None, mask_pred=None, mask_real=None, check_range=True, out_of_range=None):
     """Per-image PSNR (lib/metrics.py:30-45) of pred/target [B,...] in [0,1] and / or mask IoU (79-94) of
-    mask_pred/mask_real [B,...].  Returns (psnr [B] or None, iou [B] or None, out_of_range int32 [1] or None)."""
+    mask_pred/mask_real [B,...].  Returns (psnr [B] or None, iou [B] or None, out_of_range int32 [1] or None);
+    out_of_range: where to write the flag instead of a fresh tensor."""
     first = pred if pred is not None else mask_pred
     if first is None:
         raise ValueError('image_metrics: nothing to measure')
@@ -856,12 +869,56 @@ def image_metrics(pred=None, target=None, mask_pred=None, mask_real=None, check_
             raise ValueError('image_metrics: mask shapes %s vs %s' % (tuple(mask_pred.shape), tuple(mask_real.shape)))
         iou = torch.empty((b,), dtype=torch.float32, device=dev)
         kw.update(mask_pred=mask_pred, mask_real=mask_real, elements_per_mask=mask_pred.numel() // b, iou=iou)
-    if check_range:
-        flag = torch.empty((1,), dtype=torch.int32, device=dev)
+    flag = _range_flag(check_range, out_of_range, dev)
+    if flag is not None:
         kw['out_of_range'] = flag
     with torch.cuda.device(dev):
         _lib.call_struct('nfi_image_metrics', 'nfi_metrics_args', _stream(first), **kw)
     return psnr, iou, flag
+
+
+SSIM_BCHW = 0      # dense [B,3,H,W]
+SSIM_BHWC = 1      # dense [B,H,W,3], seen as [B,3,H,W] through permute(0,3,1,2)
+
+
+def _ssim_input(t, name):
+    """(tensor the kernel reads, its layout): t itself if it is dense in either layout, else a contiguous copy."""
+    if not t.is_cuda:
+        raise RuntimeError('%s must live on the GPU (no CPU path in nerf_from_image_amd)' % name)
+    if t.dtype != torch.float32:
+        raise TypeError('%s must be float32, got %s' % (name, t.dtype))
+    if t.is_contiguous():
+        return t, SSIM_BCHW
+    if t.permute(0, 2, 3, 1).is_contiguous():
+        return t, SSIM_BHWC
+    return t.contiguous(), SSIM_BCHW
+
+
+def image_ssim(pred, target, want_map=False, check_range=True, out_of_range=None):
+    """Per-image SSIM (lib/metrics.py:48-76) of pred / target [B,3,H,W] in [0,1], each dense as [B,3,H,W] or as [B,H,W,3]
+    behind a permute (read in place; anything else is copied).  Returns (ssim [B], the cropped map [B,3,H-6,W-6] or
+    None, out_of_range int32 [1] or None); out_of_range: where to write the flag instead of a fresh tensor."""
+    if pred.dim() != 4 or pred.shape[1] != 3 or pred.shape != target.shape:
+        raise ValueError('image_ssim: pred %s and target %s must both be [B,3,H,W]' % (tuple(pred.shape), tuple(target.shape)))
+    b, _, h, w = pred.shape
+    if b < 1 or h < 7 or w < 7:
+        raise ValueError('image_ssim: %d images of %d x %d: at least one image and one 7 x 7 window are needed' % (b, h, w))
+    pred, pred_layout = _ssim_input(pred, 'pred')
+    target, target_layout = _ssim_input(target, 'target')
+    dev = pred.device
+    ssim = torch.empty((b,), dtype=torch.float32, device=dev)
+    ssim_map = torch.empty((b, 3, h - 6, w - 6), dtype=torch.float32, device=dev) if want_map else None
+    flag = _range_flag(check_range, out_of_range, dev)
+    kw = dict(n_images=b, height=h, width=w)
+    n_ws = _lib.struct_query('nfi_image_ssim_workspace_bytes', 'nfi_ssim_args', **kw)
+    if n_ws == 0:
+        raise RuntimeError('image_ssim: shape not supported: %s' % ((b, h, w),))
+    ws = torch.empty((n_ws,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call_struct('nfi_image_ssim', 'nfi_ssim_args', _stream(pred), pred=pred, pred_layout=pred_layout, target=target,
+                         target_layout=target_layout, ssim=ssim, ssim_map=ssim_map, out_of_range=flag, workspace=ws,
+                         workspace_bytes=n_ws, **kw)
+    return ssim, ssim_map, flag
 
 
 # --------------------------------------------------------------------------- #
