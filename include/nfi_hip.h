@@ -583,6 +583,78 @@ size_t nfi_pnp_workspace_bytes(int n_images, int n_focal);
 int nfi_pose_pnp(const nfi_pnp_args* a, nfi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pose algebra of the inversion loop: lib/pose_utils.py between the optimiser's parameters (z0, t2, s, quaternion) and
+ * the cam2world matrix the render takes.  One thread per image, any n_images >= 1; no workspace, no atomics, no
+ * allocation, no synchronisation: every result is the same bits on every launch.  Each thread reads its fp32 inputs,
+ * works in float64 and rounds once on the way out, so a result is within one rounding of the exact value of the
+ * reference's formula (the reference's own fp32 chain is a few roundings off it).  Tensors are dense.
+ * Every entry refuses, with -1 and a message before any launch: a null argument struct, n_images < 1, a null required
+ * pointer, and what its own comment lists.
+ *
+ * pose_to_matrix, lib/pose_utils.py:30-70.  q [B,4] = (w, x, y, z); R = quaternion_to_matrix of q, whose ROW i is e_i
+ * rotated (lib/pose_utils.py:41-45), a polynomial in q that is evaluated as such for a non-unit q too.
+ *   normalize_q != 0: q is first replaced by q / max(|q|, 1e-12), F.normalize(q, dim=-1) of run.py:2257-2262.
+ *   z0 given (perspective): f = 1 + exp(z0), t3 = (t2 / s, f / s); cam2world = [[R, R t3], [0, 1]], focal = f / 2.
+ *   z0 NULL (orthographic): t3 = (t2, 10); cam2world = [[R, R t3], [0, 1]] / s; focal must be NULL.
+ *   camera_flipped != 0: columns 1..3 of the top three rows change sign (lib/pose_utils.py:59-60, 68-69).
+ * The forward writes cam2world [B,4,4] and focal [B] (NULL allowed in the perspective branch too).  The backward reads
+ * g_cam2world [B,4,4] and g_focal [B] (NULL: zero) and writes those of g_q [B,4], g_t2 [B,2], g_s [B], g_z0 [B] that
+ * are not NULL, through the normalisation when normalize_q is set (where |q| < 1e-12 the clamp passes no gradient to
+ * the norm, as in F.normalize).  Refused: focal / g_focal / g_z0 given together with a null z0; a backward with no
+ * gradient to write. */
+typedef struct nfi_pose_args {
+  int n_images, camera_flipped, normalize_q;
+  const float* q; const float* t2; const float* s; const float* z0;
+  float* cam2world; float* focal;                                  /* forward outputs */
+  const float* g_cam2world; const float* g_focal;                  /* backward inputs */
+  float* g_q; float* g_t2; float* g_s; float* g_z0;                /* backward outputs, each optional */
+} nfi_pose_args;
+int nfi_pose_to_matrix_fwd(const nfi_pose_args* a, nfi_stream_t stream);
+int nfi_pose_to_matrix_bwd(const nfi_pose_args* a, nfi_stream_t stream);
+
+/* matrix_to_pose, lib/pose_utils.py:98-121, with matrix_to_quaternion (73-95) inside the kernel instead of a copy to
+ * the host and a numpy loop, and matrix_to_conditioning_vector (124-145).  From cam2world [B,4,4] (columns 1..3 of the
+ * top rows change sign first when camera_flipped) W = invert_space of it, t3 = -W[:3,3];
+ *   focal given: z0 = log(2 focal - 1), s = 2 focal / t3.z;   focal NULL: s = 1 / cam2world[3,3], z0 must be NULL;
+ *   t2 = t3.xy * s;  q [B,4] = matrix_to_quaternion of W: the reference's four branches, chosen on float64 values.
+ *   cond [B,13] = (log(focal) unshifted, or 0 without focal; t2; s; the nine entries of W[:3,:3] row by row).
+ * Every output is optional, at least one must be given.  Refused: z0 without focal. */
+typedef struct nfi_matrix_to_pose_args {
+  int n_images, camera_flipped;
+  const float* cam2world; const float* focal;
+  float* z0; float* t2; float* s; float* q; float* cond;
+} nfi_matrix_to_pose_args;
+int nfi_matrix_to_pose(const nfi_matrix_to_pose_args* a, nfi_stream_t stream);
+
+/* rotation_matrix_distance, lib/pose_utils.py:148-156: degrees [B] = acos(clamp((trace(P Q^T) - 1) / 2, -1, 1)) * 180 /
+ * pi of p, q [B,dim,dim]; dim = 4: the top-left 3 x 3 of each, divided by its element [3,3].  Refused: dim not 3 or 4. */
+typedef struct nfi_rotation_distance_args {
+  int n_images, dim;
+  const float* p; const float* q;
+  float* degrees;
+} nfi_rotation_distance_args;
+int nfi_rotation_distance(const nfi_rotation_distance_args* a, nfi_stream_t stream);
+
+/* The selection inside perturb_poses, lib/pose_utils.py:159-170: index[i] = the j that minimises
+ * |distance(cam2world[i], cam2world[j]) - target[i]| (the 4 x 4 distance above; on an exact tie the lowest j), for
+ * cam2world [N,4,4] and target [N] in degrees: one launch in place of N rounds of a dozen launches and two reads each.
+ * The N x N distances exist only in registers. */
+typedef struct nfi_pose_nearest_args {
+  int n_images;
+  const float* cam2world; const float* target;
+  int32_t* index;
+} nfi_pose_nearest_args;
+int nfi_pose_nearest_by_angle(const nfi_pose_nearest_args* a, nfi_stream_t stream);
+
+/* The fix-ups after an optimiser step, run.py:2307-2310, in place: q [B,4] <- q / max(|q|, 1e-12), s [B] <- |s|,
+ * z0 [B] <- clamp(z0, -4, 4) (z0 NULL: orthographic, skipped). */
+typedef struct nfi_pose_project_args {
+  int n_images;
+  float* q; float* s; float* z0;
+} nfi_pose_project_args;
+int nfi_pose_project(const nfi_pose_project_args* a, nfi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Plane-producer hand-off: the tail of the LAST StyleGAN2 synthesis block
  * (models/stylegan.py:383-435: img = upsample2d(img_prev); y = torgb(x, w); img += y) fused into one kernel that
  * writes the result as texels in the INTERLEAVED layout [B,R,R,3,32] (= a channels-last [B,96,R,R] tensor), so

@@ -80,3 +80,33 @@ def zeros_like_or(g, ref):
     if g is None:
         return ref.zeros() if isinstance(ref, OutputMeta) else torch.zeros_like(ref)
     return g.contiguous()
+
+
+class PoseToMatrix(torch.autograd.Function):
+    """lib/pose_utils.py:48-70 as ONE node: (z0 or None, t2, s, q, camera_flipped, normalize) -> (cam2world, focal or None).
+    One launch forward, one backward (ops.pose_to_matrix / pose_to_matrix_bwd: thread = image, no atomics, so the pose
+    gradients repeat bit for bit); inputs that need no gradient get None.  First-order only, like every node here."""
+
+    @staticmethod
+    def forward(ctx, z0, t2, s, q, camera_flipped, normalize):
+        from . import ops
+        ctx.flags = (bool(camera_flipped), bool(normalize))
+        ctx.perspective = z0 is not None
+        ctx.save_for_backward(*(t for t in (z0, t2, s, q) if t is not None))
+        cam2world, focal = ops.pose_to_matrix(q, t2, s, z0, *ctx.flags)
+        return cam2world, focal
+
+    @staticmethod
+    def backward(ctx, g_cam2world, g_focal):
+        from . import ops
+        if torch.is_grad_enabled():
+            raise RuntimeError('nerf_from_image_amd: pose_to_matrix is first-order only - torch.autograd.grad(..., '
+                               'create_graph=True) / a double backward through a HIP node is not supported')
+        z0, t2, s, q = ctx.saved_tensors if ctx.perspective else (None,) + tuple(ctx.saved_tensors)
+        with torch.no_grad():
+            if g_cam2world is None:
+                g_cam2world = torch.zeros((q.shape[0], 4, 4), dtype=torch.float32, device=q.device)
+            need_z0, need_t2, need_s, need_q = ctx.needs_input_grad[:4]
+            g_q, g_t2, g_s, g_z0 = ops.pose_to_matrix_bwd(g_cam2world, g_focal, q, t2, s, z0, *ctx.flags,
+                                                          needs=(need_q, need_t2, need_s, need_z0))
+        return g_z0, g_t2, g_s, g_q, None, None

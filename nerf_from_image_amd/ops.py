@@ -922,6 +922,110 @@ def image_ssim(pred, target, want_map=False, check_range=True, out_of_range=None
 
 
 # --------------------------------------------------------------------------- #
+# pose algebra of the inversion loop (lib/pose_utils.py; csrc/nfi_pose.inc): thread = image, one launch per call
+# --------------------------------------------------------------------------- #
+def _pose_rows(t, tail, name, b=None):
+    """t as dense float32 [B, *tail] on the GPU (B = its own, or the given one)."""
+    t = _f32c(t, name)
+    if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or t.shape[0] < 1 or (b is not None and t.shape[0] != b):
+        raise ValueError('%s must be [%s], got %s' % (name, ', '.join(['B' if b is None else str(b)] + [str(v) for v in tail]),
+                                                      tuple(t.shape)))
+    return t
+
+
+def _pose_params(q, t2, s, z0):
+    q = _pose_rows(q, (4,), 'q')
+    b = q.shape[0]
+    return q, _pose_rows(t2, (2,), 't2', b), _pose_rows(s, (), 's', b), None if z0 is None else _pose_rows(z0, (), 'z0', b)
+
+
+def pose_to_matrix(q, t2, s, z0=None, camera_flipped=False, normalize_q=False):
+    """lib/pose_utils.py:48-70 for q [B,4], t2 [B,2], s [B], z0 [B] or None (orthographic): (cam2world [B,4,4], focal [B]
+    or None).  normalize_q: F.normalize(q, dim=-1) inside the launch."""
+    q, t2, s, z0 = _pose_params(q, t2, s, z0)
+    b, dev = q.shape[0], q.device
+    cam2world = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
+    focal = None if z0 is None else torch.empty((b,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call_struct('nfi_pose_to_matrix_fwd', 'nfi_pose_args', _stream(q), n_images=b, camera_flipped=int(bool(camera_flipped)),
+                         normalize_q=int(bool(normalize_q)), q=q, t2=t2, s=s, z0=z0, cam2world=cam2world, focal=focal)
+    return cam2world, focal
+
+
+def pose_to_matrix_bwd(g_cam2world, g_focal, q, t2, s, z0=None, camera_flipped=False, normalize_q=False,
+                       needs=(True, True, True, True)):
+    """Gradients (g_q, g_t2, g_s, g_z0) of the above from g_cam2world [B,4,4] and g_focal [B] or None; needs: which of the
+    four to compute (the others, and g_z0 without z0, are None)."""
+    q, t2, s, z0 = _pose_params(q, t2, s, z0)
+    b, dev = q.shape[0], q.device
+    g_cam2world = _pose_rows(g_cam2world, (4, 4), 'g_cam2world', b)
+    g_focal = None if g_focal is None or z0 is None else _pose_rows(g_focal, (), 'g_focal', b)
+    needs = tuple(needs[:3]) + (needs[3] and z0 is not None,)
+    outs = [torch.empty_like(t) if need else None for t, need in zip((q, t2, s, z0), needs)]
+    if any(needs):
+        with torch.cuda.device(dev):
+            _lib.call_struct('nfi_pose_to_matrix_bwd', 'nfi_pose_args', _stream(q), n_images=b, camera_flipped=int(bool(camera_flipped)),
+                             normalize_q=int(bool(normalize_q)), q=q, t2=t2, s=s, z0=z0, g_cam2world=g_cam2world, g_focal=g_focal,
+                             g_q=outs[0], g_t2=outs[1], g_s=outs[2], g_z0=outs[3])
+    return tuple(outs)
+
+
+def matrix_to_pose(cam2world, focal=None, camera_flipped=False, want_pose=True, want_cond=False):
+    """lib/pose_utils.py:98-145 on the device: (z0 [B] or None, t2 [B,2], s [B], q [B,4], cond [B,13]); the first four are
+    None without want_pose, the last without want_cond."""
+    cam2world = _pose_rows(cam2world, (4, 4), 'cam2world')
+    b, dev = cam2world.shape[0], cam2world.device
+    focal = None if focal is None else _pose_rows(focal, (), 'focal', b)
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    z0 = new(b) if want_pose and focal is not None else None
+    t2, s, q = (new(b, 2), new(b), new(b, 4)) if want_pose else (None, None, None)
+    cond = new(b, 13) if want_cond else None
+    with torch.cuda.device(dev):
+        _lib.call_struct('nfi_matrix_to_pose', 'nfi_matrix_to_pose_args', _stream(cam2world), n_images=b,
+                         camera_flipped=int(bool(camera_flipped)), cam2world=cam2world, focal=focal, z0=z0, t2=t2, s=s, q=q, cond=cond)
+    return z0, t2, s, q, cond
+
+
+def rotation_distance(p, q):
+    """lib/pose_utils.py:148-156: degrees [B] between p, q [B,3,3] or [B,4,4] (4 x 4: each over its element [3,3])."""
+    dim = p.shape[-1]
+    if dim not in (3, 4):
+        raise ValueError('rotation_distance: [B,3,3] or [B,4,4] matrices, got %s' % (tuple(p.shape),))
+    p = _pose_rows(p, (dim, dim), 'p')
+    q = _pose_rows(q, (dim, dim), 'q', p.shape[0])
+    degrees = torch.empty((p.shape[0],), dtype=torch.float32, device=p.device)
+    with torch.cuda.device(p.device):
+        _lib.call_struct('nfi_rotation_distance', 'nfi_rotation_distance_args', _stream(p), n_images=p.shape[0], dim=dim, p=p, q=q,
+                         degrees=degrees)
+    return degrees
+
+
+def pose_nearest_by_angle(cam2world, target):
+    """The selection of lib/pose_utils.py:159-170: int32 [N], for each pose the index of the pose whose distance to it is
+    closest to target [N] degrees (the lowest index on a tie)."""
+    cam2world = _pose_rows(cam2world, (4, 4), 'cam2world')
+    n = cam2world.shape[0]
+    target = _pose_rows(target, (), 'target', n)
+    index = torch.empty((n,), dtype=torch.int32, device=cam2world.device)
+    with torch.cuda.device(cam2world.device):
+        _lib.call_struct('nfi_pose_nearest_by_angle', 'nfi_pose_nearest_args', _stream(cam2world), n_images=n, cam2world=cam2world,
+                         target=target, index=index)
+    return index
+
+
+def pose_project_(q, s, z0=None):
+    """run.py:2307-2310 in place on dense float32 tensors: q [B,4] normalised, s [B] made non-negative, z0 [B] (if given)
+    clamped to [-4, 4]."""
+    for t, tail, name in ((q, (4,), 'q'), (s, (), 's'), (z0, (), 'z0')):
+        if t is not None and _pose_rows(t, tail, name, None if t is q else q.shape[0]) is not t:
+            raise ValueError('pose_project_: %s must be contiguous to be changed in place' % name)
+    with torch.cuda.device(q.device):
+        _lib.call_struct('nfi_pose_project', 'nfi_pose_project_args', _stream(q), n_images=q.shape[0], q=q, s=s, z0=z0)
+
+
+# --------------------------------------------------------------------------- #
 # plane-producer hand-off (SURVEY.md 8(f)3)
 # --------------------------------------------------------------------------- #
 def torgb_texels(x, styles, weight, bias, previous_image=None):
