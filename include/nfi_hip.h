@@ -764,6 +764,38 @@ typedef struct nfi_ssim_args {
 size_t nfi_image_ssim_workspace_bytes(const nfi_ssim_args* a);
 int nfi_image_ssim(const nfi_ssim_args* a, nfi_stream_t stream);
 
+/* Separable image filter, the progressive discriminator blur: lib/ops.py:29-55 (filt2d with a 1-D kernel, and blur, which
+ * run.py:998 and run.py:1090-1093 call for the first blur_warmup_iters iterations).  With f the 2 radius + 1 taps:
+ *   out[y,x] = background + sum_{a,b} f[a] f[b] (image[y + a - radius, x + b - radius] - background),
+ * samples outside the image contributing 0 - lib/ops.py:29-55's conv2d with padding radius on image - 1 (white background)
+ * or on image itself, a cross-correlation, same size out as in.  ONE launch: a block per (image, channel, tile of 32 x 32
+ * pixels) stages its tile and halo in LDS, filters the rows, then the columns.  Exact fp32: one accumulator per output, the
+ * taps applied in index order with fmaf, rows first.  No atomics, no workspace, no allocation, no synchronisation: the same
+ * bits on every launch.
+ *   n_images, channels, height, width: B, C, H, W, each >= 1 (images smaller than the radius included).
+ *   image: B x C x H x W values, dense in `layout`: NFI_FILTER_BCHW = [B,C,H,W], NFI_FILTER_BHWC = [B,H,W,C] (what run.py's
+ *   target_img.permute(0,3,1,2) is in memory).  out: dense [B,C,H,W], always; must not overlap image.
+ *   radius: 1 .. 30 (lib/ops.py:29-55's blur has sigma <= 10, hence at most 61 taps).
+ *   taps: float[2 radius + 1] on the device, used as given (filt2d), or NULL: every block computes lib/ops.py:29-55's own,
+ *   f[j] = exp2(-((j - radius) / sigma)^2) - base 2 - added in the order j = 0 .. 2 radius and divided by that sum.
+ *   background: subtracted from every sample as it is read and added to every output (1 = white, 0 = none).
+ *   flip: nonzero applies the taps reversed - the adjoint of the same call, i.e. its backward with background 0.
+ * Refused before any launch (-1, nfi_last_error()): a null argument / image / out; n_images, channels, height or width
+ * under 1; a layout other than the two; radius outside 1 .. 30; null taps with sigma <= 0 (or NaN); a grid over the launch
+ * limit: n_images * channels * ceil(height / 32) * ceil(width / 32) must be below 2^31. */
+enum { NFI_FILTER_BCHW = 0, NFI_FILTER_BHWC = 1 };
+typedef struct nfi_filter_args {
+  int n_images, channels, height, width;
+  int layout;
+  const float* image;
+  float* out;
+  int radius;
+  const float* taps;
+  float sigma, background;
+  int flip;
+} nfi_filter_args;
+int nfi_separable_filter(const nfi_filter_args* a, nfi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * View-direction mapper, the per-ray trunk.  Replaces ViewDirectionMapper.__init__'s layers as forward runs them
  * (models/generator.py:194-241: fc0 .. fc6, norm1 .. norm4, two residual joins scaled by sqrt(2)/2, LeakyReLU(0.2);

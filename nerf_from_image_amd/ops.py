@@ -921,6 +921,49 @@ def image_ssim(pred, target, want_map=False, check_range=True, out_of_range=None
     return ssim, ssim_map, flag
 
 
+FILTER_BCHW = 0        # dense [B,C,H,W]
+FILTER_BHWC = 1        # dense [B,H,W,C], seen as [B,C,H,W] through permute(0,3,1,2)
+FILTER_MAX_RADIUS = 30
+FILTER_TILE = (32, 32)    # kFilterTileH, kFilterTileW of csrc/nfi_filter.inc: output pixels per block
+
+
+def separable_filter(image, radius, taps=None, sigma=0.0, background=0.0, flip=False):
+    """Zero-padded, same-size separable correlation of image [B,C,H,W] (lib/ops.py:29-55: filt2d with a 1-D kernel, blur):
+    out = background + (f (x) f) * (image - background), dense [B,C,H,W].  taps: float32 [2 radius + 1] on the image's
+    device, used as given, or None: the kernel computes blur's own from sigma.  flip=True applies the taps reversed (the
+    adjoint).  image is read in place if it is dense as [B,C,H,W] or as [B,H,W,C] behind a permute; anything else is
+    copied.  One launch on the current stream."""
+    if not image.is_cuda:
+        raise RuntimeError('image must live on the GPU (no CPU path in nerf_from_image_amd)')
+    if image.dtype != torch.float32:
+        raise TypeError('image must be float32, got %s' % image.dtype)
+    if image.dim() != 4 or image.numel() == 0:
+        raise ValueError('separable_filter: image must be a non-empty [B,C,H,W], got %s' % (tuple(image.shape),))
+    radius = int(radius)
+    if not 1 <= radius <= FILTER_MAX_RADIUS:
+        raise ValueError('separable_filter: radius %d outside 1 .. %d' % (radius, FILTER_MAX_RADIUS))
+    if taps is None:
+        if not sigma > 0:
+            raise ValueError('separable_filter: sigma must be positive when no taps are given, got %r' % (sigma,))
+    else:
+        taps = _f32c(taps, 'taps')
+        if taps.device != image.device or tuple(taps.shape) != (2 * radius + 1,):
+            raise ValueError('separable_filter: taps must be [%d] on %s, got %s on %s' % (2 * radius + 1, image.device, tuple(taps.shape), taps.device))
+    if image.is_contiguous():
+        layout = FILTER_BCHW
+    elif image.permute(0, 2, 3, 1).is_contiguous():
+        layout = FILTER_BHWC
+    else:
+        image, layout = image.contiguous(), FILTER_BCHW
+    b, c, h, w = image.shape
+    out = torch.empty((b, c, h, w), dtype=torch.float32, device=image.device)
+    with torch.cuda.device(image.device):
+        _lib.call_struct('nfi_separable_filter', 'nfi_filter_args', _stream(image), n_images=b, channels=c, height=h, width=w,
+                         layout=layout, image=image, out=out, radius=radius, taps=taps, sigma=float(sigma),
+                         background=float(background), flip=int(bool(flip)))
+    return out
+
+
 # --------------------------------------------------------------------------- #
 # pose algebra of the inversion loop (lib/pose_utils.py; csrc/nfi_pose.inc): thread = image, one launch per call
 # --------------------------------------------------------------------------- #
