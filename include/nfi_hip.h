@@ -796,6 +796,44 @@ typedef struct nfi_filter_args {
 } nfi_filter_args;
 int nfi_separable_filter(const nfi_filter_args* a, nfi_stream_t stream);
 
+/* The distance head of LPIPS, one layer per call: lib/metrics.py:104-110, 130-133 - what LPIPSLoss does to each of the five
+ * feature maps AFTER the VGG convolutions (which stay with the library that runs them).  With p over the H W pixels:
+ *   rx[b,p] = sqrt(sum_c x[b,c,p]^2),  xh = x / (rx + eps)      (normalize_tensor: eps added to the norm, not under the root)
+ *   ry, yh likewise; y_normalized != 0: yh = y as given         (cached features, lib/metrics.py:126-128)
+ *   out[b]  = (1 / (H W)) sum_p sum_c weight[c] (xh[b,c,p] - yh[b,c,p])^2
+ * The difference is formed per element and then squared, in float64 like the channel sums: identical x and y give exactly
+ * 0.0f and exactly zero gradients.  A block owns one image and 64 consecutive pixels; channels 64 and 128 are read once
+ * (kept in registers between the sweeps), any other count >= 1 is read again per sweep.
+ *   fwd: every block writes one float64 partial to the workspace; a second kernel adds an image's partials in index order
+ *     and stores out[b], or adds to it in float32 with accumulate != 0 (chaining the layers as lib/metrics.py:130-133's sum
+ *     does).  No float atomics, no memset, no allocation: the same bits on every launch, whatever the batch around an image.
+ *   bwd: ONE launch; the norms are recomputed, the forward stashes nothing.  g = g_out[b] / (H W), q[c] = 2 weight[c] (xh - yh):
+ *       g_x[b,k,p] = g (q[k] / (rx + eps) - x[k] (sum_c q[c] x[c]) / ((rx + eps)^2 rx))
+ *       g_y: the same with x <-> y and q -> -q;  y_normalized: g_y = -g q[k]
+ *     Either of g_x / g_y may be NULL (skipped).  Every element is written exactly once, no atomics.  Where a pixel's whole
+ *     channel vector is zero the second term is taken as 0: the gradient is the finite g q[k] / eps there, where the
+ *     reference's autograd gives NaN (a stated deviation).
+ *   x, y: dense [B,C,H,W]; weight [C], the lin layer's weight[0,:,0,0]; eps >= 0 (1e-10 in the reference); out, g_out [B];
+ *   g_x, g_y dense [B,C,H,W].  All element offsets are 64-bit.  The forward-only fields (out, accumulate, the workspace) are
+ *   ignored by bwd and the g_* fields by fwd.
+ *   workspace: device memory, 8-byte aligned, need not be zeroed; nfi_lpips_head_workspace_bytes reads n_images, channels,
+ *   height and width alone (one double per block) and returns 0 for a shape the calls refuse.
+ * Refused before any launch (-1, nfi_last_error()): a null argument / x / y / weight; out null (fwd); g_out null or both
+ * gradients null (bwd); a gradient overlapping x, y or the other gradient; a dimension under 1; eps negative or NaN; a
+ * missing, too small or misaligned workspace (fwd); a grid over the launch limit: n_images * ceil(height * width / 64) must
+ * be below 2^31. */
+typedef struct nfi_lpips_head_args {
+  int n_images, channels, height, width;
+  const float* x; const float* y; int y_normalized;
+  const float* weight; float eps;
+  float* out; int accumulate;                    /* forward */
+  const float* g_out; float* g_x; float* g_y;    /* backward */
+  void* workspace; size_t workspace_bytes;       /* forward only */
+} nfi_lpips_head_args;
+size_t nfi_lpips_head_workspace_bytes(const nfi_lpips_head_args* a);
+int nfi_lpips_head_fwd(const nfi_lpips_head_args* a, nfi_stream_t stream);
+int nfi_lpips_head_bwd(const nfi_lpips_head_args* a, nfi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * View-direction mapper, the per-ray trunk.  Replaces ViewDirectionMapper.__init__'s layers as forward runs them
  * (models/generator.py:194-241: fc0 .. fc6, norm1 .. norm4, two residual joins scaled by sqrt(2)/2, LeakyReLU(0.2);

@@ -110,3 +110,32 @@ class PoseToMatrix(torch.autograd.Function):
             g_q, g_t2, g_s, g_z0 = ops.pose_to_matrix_bwd(g_cam2world, g_focal, q, t2, s, z0, *ctx.flags,
                                                           needs=(need_q, need_t2, need_s, need_z0))
         return g_z0, g_t2, g_s, g_q, None, None
+
+
+class LpipsHead(torch.autograd.Function):
+    """One layer of the LPIPS distance head as ONE node (ops.lpips_head / lpips_head_bwd; lib/metrics.py:104-110, 130-133):
+    (x, y [B,C,H,W], weight [C], y_normalized, eps) -> [B].  Saves x, y and weight - the forward stashes nothing else, the
+    backward recomputes the norms - and returns gradients for whichever of x / y need them, in one launch.  The weight
+    is frozen, as the reference freezes the net (lib/metrics.py:102): one that requires grad raises.  First-order only."""
+
+    @staticmethod
+    def forward(ctx, x, y, weight, y_normalized, eps):
+        from . import ops
+        if weight.requires_grad:
+            raise RuntimeError('nerf_from_image_amd: lpips_head has no gradient for the lin weights (the reference freezes '
+                               'the net, lib/metrics.py:102): call requires_grad_(False) on the LPIPS module')
+        ctx.flags = (bool(y_normalized), float(eps))
+        ctx.save_for_backward(x, y, weight)
+        return ops.lpips_head(x, y, weight, *ctx.flags)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        from . import ops
+        if torch.is_grad_enabled():
+            raise RuntimeError('nerf_from_image_amd: lpips_head is first-order only - torch.autograd.grad(..., '
+                               'create_graph=True) / a double backward through a HIP node is not supported')
+        x, y, weight = ctx.saved_tensors
+        need_x, need_y = ctx.needs_input_grad[:2]
+        with torch.no_grad():
+            g_x, g_y = ops.lpips_head_bwd(g_out, x, y, weight, *ctx.flags, need_x=need_x, need_y=need_y)
+        return g_x, g_y, None, None, None

@@ -15,7 +15,7 @@ using namespace nfi;
 // error plumbing, argument checks and the LDS staging helpers shared with nfi_backward_field.hip: nfi_host.hpp
 thread_local char nfi_err_buf[256] = "";
 extern "C" const char* nfi_last_error(void) { return nfi_err_buf; }
-extern "C" int nfi_version(void) { return 104; }
+extern "C" int nfi_version(void) { return 105; }
 
 
 // ------------------------------------------------------------------------------------------------
@@ -1340,6 +1340,7 @@ extern "C" int nfi_composite_fwd(const nfi_composite_args* a, nfi_stream_t strea
 #include "nfi_pnp.inc"
 #include "nfi_pose.inc"
 #include "nfi_filter.inc"
+#include "nfi_lpips.inc"
 #include "nfi_viewdir_mapper.inc"
 
 // ------------------------------------------------------------------------------------------------

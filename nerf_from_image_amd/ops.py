@@ -965,6 +965,65 @@ def separable_filter(image, radius, taps=None, sigma=0.0, background=0.0, flip=F
 
 
 # --------------------------------------------------------------------------- #
+# LPIPS distance head (lib/metrics.py:104-110, 130-133; csrc/nfi_lpips.inc): one layer per call
+# --------------------------------------------------------------------------- #
+def _lpips_inputs(x, y, weight, where):
+    """x, y as dense NCHW float32 on one GPU, weight as dense [C].  Dense NCHW tensors are read in place; anything else -
+    channels-last included - is copied to dense NCHW first (the kernels have no other layout)."""
+    x, y, weight = _f32c(x, 'x'), _f32c(y, 'y'), _f32c(weight, 'weight')
+    if x.dim() != 4 or x.numel() == 0 or x.shape != y.shape:
+        raise ValueError('%s: x %s and y %s must be the same non-empty [B,C,H,W]' % (where, tuple(x.shape), tuple(y.shape)))
+    if weight.numel() != x.shape[1]:
+        raise ValueError('%s: weight must hold %d values, got %s' % (where, x.shape[1], tuple(weight.shape)))
+    if y.device != x.device or weight.device != x.device:
+        raise ValueError('%s: x, y and weight must live on one device' % where)
+    b, c, h, w = x.shape
+    return x, y, weight, dict(n_images=b, channels=c, height=h, width=w)
+
+
+def lpips_head(x, y, weight, y_normalized=False, eps=1e-10, out=None, accumulate=False):
+    """One layer of the LPIPS distance (lib/metrics.py:104-110, 130-133): x, y [B,C,H,W] feature maps, weight [C] (the lin
+    layer's weight[0,:,0,0]) -> out [B] = mean_p sum_c weight[c] (x / (|x| + eps) - y / (|y| + eps))^2; y_normalized=True
+    takes y as already normalised (cached features).  out: a float32 [B] to write instead of a fresh tensor;
+    accumulate=True adds to it (float32), which chains the layers into one vector.  Two launches on the current stream."""
+    x, y, weight, kw = _lpips_inputs(x, y, weight, 'lpips_head')
+    b = kw['n_images']
+    if out is None:
+        if accumulate:
+            raise ValueError('lpips_head: accumulate=True needs the out tensor to add to')
+        out = torch.empty((b,), dtype=torch.float32, device=x.device)
+    elif not (out.is_cuda and out.device == x.device and out.dtype == torch.float32 and tuple(out.shape) == (b,) and out.is_contiguous()):
+        raise ValueError('lpips_head: out must be a dense float32 [%d] on %s' % (b, x.device))
+    n_ws = _lib.struct_query('nfi_lpips_head_workspace_bytes', 'nfi_lpips_head_args', **kw)
+    if n_ws == 0:
+        raise RuntimeError('lpips_head: shape not supported: %s' % (tuple(x.shape),))
+    ws = torch.empty((n_ws,), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call_struct('nfi_lpips_head_fwd', 'nfi_lpips_head_args', _stream(x), x=x, y=y, y_normalized=int(bool(y_normalized)),
+                         weight=weight, eps=float(eps), out=out, accumulate=int(bool(accumulate)), workspace=ws,
+                         workspace_bytes=n_ws, **kw)
+    return out
+
+
+def lpips_head_bwd(g_out, x, y, weight, y_normalized=False, eps=1e-10, need_x=True, need_y=False):
+    """Gradients of lpips_head for the upstream g_out [B]: (g_x or None, g_y or None), each dense [B,C,H,W] and written
+    whole by ONE launch (no atomics).  At a pixel of x whose channels are all zero g_x is the finite g q / eps where the
+    reference's autograd has NaN."""
+    x, y, weight, kw = _lpips_inputs(x, y, weight, 'lpips_head_bwd')
+    g_out = _f32c(g_out, 'g_out')
+    if g_out.numel() != kw['n_images'] or g_out.device != x.device:
+        raise ValueError('lpips_head_bwd: g_out must hold %d values on %s, got %s' % (kw['n_images'], x.device, tuple(g_out.shape)))
+    if not (need_x or need_y):
+        raise ValueError('lpips_head_bwd: neither gradient is wanted')
+    g_x = torch.empty_like(x) if need_x else None
+    g_y = torch.empty_like(y) if need_y else None
+    with torch.cuda.device(x.device):
+        _lib.call_struct('nfi_lpips_head_bwd', 'nfi_lpips_head_args', _stream(x), x=x, y=y, y_normalized=int(bool(y_normalized)),
+                         weight=weight, eps=float(eps), g_out=g_out, g_x=g_x, g_y=g_y, **kw)
+    return g_x, g_y
+
+
+# --------------------------------------------------------------------------- #
 # pose algebra of the inversion loop (lib/pose_utils.py; csrc/nfi_pose.inc): thread = image, one launch per call
 # --------------------------------------------------------------------------- #
 def _pose_rows(t, tail, name, b=None):
