@@ -834,6 +834,48 @@ size_t nfi_lpips_head_workspace_bytes(const nfi_lpips_head_args* a);
 int nfi_lpips_head_fwd(const nfi_lpips_head_args* a, nfi_stream_t stream);
 int nfi_lpips_head_bwd(const nfi_lpips_head_args* a, nfi_stream_t stream);
 
+/* The tail of a synthesis layer: everything SynthesisLayer.forward (models/stylegan.py:325-356) does AFTER its convolution -
+ * filter2d(x, f, gain=4) of an `up` layer (stylegan.py:58-69, 101-105), addcmul(noise, x, dcoefs) (139-140), + bias (351),
+ * * act_gain (352-353), leaky_relu (354-355).  All tensors dense float32, NCHW.  With R = resolution:
+ *   f   = up ? sum_{a,b in 0..3} (4 taps[a][b]) y[i + a - 1, j + b - 1]   (0 outside y, which is [B,C,R+1,R+1])
+ *            : y                                                          (y is [B,C,R,R])
+ *   out = lrelu_slope(((noise + f * dcoefs[b,c]) + bias[c]) * act_gain)   [B,C,R,R]; no lrelu with activate == 0
+ * Every operation after the filter is rounded on its own, in that order; the filter adds its 16 products in float64, in the
+ * order a, b, and rounds once.  taps: the layer's resample_filter buffer, 16 floats ON THE DEVICE, any values (read by the kernels, never
+ * copied to the host; not read without up).  noise: NULL, or [B,1,R,R] (noise_shared == 0), or [R,R] for the whole batch
+ * (noise_shared != 0).
+ *   fwd (stylegan.py:101-105, 139-140, 351-355): ONE launch; y is read once (an up layer stages 64 x 64 tiles with their halo
+ *     in LDS) and out written once.
+ *   bwd (what autograd records for those lines): out is the forward's result, read for the sign of the pre-activation (hence
+ *     act_gain > 0, slope >= 0).  gu = g_out * (out > 0 ? 1 : slope) * act_gain;
+ *       g_y      = dcoefs[b,c] * (the adjoint filter of gu, on the R+1 grid)   - or dcoefs * gu without up
+ *       g_dcoefs [B,C] = sum_ij gu f   (f recomputed from y),  g_bias [C] = sum_b,ij gu,
+ *       g_noise  = sum_c gu [B,1,R,R], or sum_b,c gu [R,R] with noise_shared.
+ *     Each may be NULL (skipped), not all four.  One launch for g_y and the per-block float64 sums, one that adds those in
+ *     index order into g_dcoefs / g_bias (only when either is asked for), one for g_noise (only when asked for).  No float
+ *     atomics: the same bits on every launch.  No gradient for the taps, no second order.
+ *   workspace (bwd, only with g_dcoefs or g_bias): device memory, 8-byte aligned, need not be zeroed;
+ *   nfi_synth_tail_bwd_workspace_bytes reads batch, channels, resolution and up and returns 0 for a shape the calls refuse.
+ * Refused before any launch (-1, nfi_last_error() names the argument): a null argument struct / y / dcoefs / bias / out, null
+ * taps with up, null g_out or no gradient pointer (bwd); batch, channels or resolution under 1, resolution over 16384;
+ * in_size other than resolution + 1 with up and resolution without; act_gain <= 0 or NaN; slope < 0 or NaN; an element
+ * count the index arithmetic cannot hold: batch * channels * blocks per plane (ceil(side / 64)^2 with up, ceil(R R / 4096)
+ * without) must be below 2^31; a missing, misaligned or too small workspace (bwd). */
+typedef struct nfi_synth_tail_args {
+  int batch, channels, resolution;               /* B, C, R */
+  int in_size;                                   /* side of y */
+  int up, activate;
+  float act_gain, slope;
+  const float* y; const float* dcoefs; const float* bias; const float* taps;
+  const float* noise; int noise_shared;
+  float* out;                                    /* written by fwd, read by bwd */
+  const float* g_out; float* g_y; float* g_dcoefs; float* g_bias; float* g_noise;    /* backward */
+  void* workspace; size_t workspace_bytes;       /* backward */
+} nfi_synth_tail_args;
+size_t nfi_synth_tail_bwd_workspace_bytes(const nfi_synth_tail_args* a);
+int nfi_synth_tail_fwd(const nfi_synth_tail_args* a, nfi_stream_t stream);
+int nfi_synth_tail_bwd(const nfi_synth_tail_args* a, nfi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * View-direction mapper, the per-ray trunk.  Replaces ViewDirectionMapper.__init__'s layers as forward runs them
  * (models/generator.py:194-241: fc0 .. fc6, norm1 .. norm4, two residual joins scaled by sqrt(2)/2, LeakyReLU(0.2);

@@ -9,9 +9,13 @@ second-order path of the reference that touches the renderer's neighbourhood, th
 regulariser of the plane producer, is kept off the fused hand-off node: generator.hip_forward).
 
 Lifetime: the node keeps its INPUTS through ``save_for_backward`` and, of its outputs, only their
-shape/dtype/device (:class:`OutputMeta`).  Keeping an output tensor on ``ctx`` would close the
-cycle output -> grad_fn -> ctx -> output, which the reference-counting of autograd never frees:
-every step would leak its per-sample tensors.
+shape/dtype/device (:class:`OutputMeta`).  Keeping an output tensor as an attribute on ``ctx`` would
+close the cycle output -> grad_fn -> ctx -> output, which the reference-counting of autograd never
+frees: every step would leak its per-sample tensors.  An op whose backward reads an output (the
+synthesis tail takes the sign of the pre-activation from it) names it in ``saved_outputs``: it then
+goes through ``save_for_backward`` too, where autograd stores an output WITHOUT its ``grad_fn`` and
+re-attaches it on unpacking, so no cycle forms; the backward closure gets those tensors as its
+fifth argument.
 """
 import torch
 
@@ -32,10 +36,14 @@ class _HipNode(torch.autograd.Function):
     def forward(ctx, name, fn, bwd, nondiff, *tensors):
         ctx.name = name
         ctx.bwd = bwd
+        nondiff, keep = nondiff
         with torch.no_grad():
             out = fn(*tensors)
         outs = (out,) if not isinstance(out, tuple) else out
-        ctx.save_for_backward(*tensors)
+        # outputs in `keep` go through save_for_backward as well: autograd holds a saved OUTPUT without its grad_fn, so no
+        # cycle forms (an attribute on ctx would close one, see the module docstring)
+        ctx.n_inputs = len(tensors)
+        ctx.save_for_backward(*tensors, *(outs[i] for i in keep))
         ctx.out_meta = tuple(None if o is None else OutputMeta(o) for o in outs)
         nd = [outs[i] for i in nondiff if i < len(outs) and outs[i] is not None]
         nd += [o for o in outs if o is not None and not o.dtype.is_floating_point]
@@ -58,21 +66,25 @@ class _HipNode(torch.autograd.Function):
                 'nerf_from_image_amd: %s has no HIP backward (forward-only op); wrap the call in '
                 'torch.no_grad() or detach its inputs' % ctx.name)
         with torch.no_grad():
-            gin = ctx.bwd(ctx.saved_tensors, ctx.out_meta, grads, ctx.needs_input_grad[4:])
+            saved = ctx.saved_tensors
+            kept = (saved[ctx.n_inputs:],) if len(saved) > ctx.n_inputs else ()
+            gin = ctx.bwd(saved[:ctx.n_inputs], ctx.out_meta, grads, ctx.needs_input_grad[4:], *kept)
         gin = tuple(g if need else None for g, need in zip(gin, ctx.needs_input_grad[4:]))
         return (None, None, None, None) + gin
 
 
-def differentiable(name, fn, *tensors, bwd=None, non_differentiable_outputs=()):
+def differentiable(name, fn, *tensors, bwd=None, non_differentiable_outputs=(), saved_outputs=()):
     """Runs fn(*tensors) (HIP kernels).  Records an autograd node only when a gradient can be asked for.
 
     bwd(inputs, output_meta, grad_outputs, needs) -> tuple of gradients, one per input (None allowed);
-    output_meta[i] is an :class:`OutputMeta` (shape / dtype / device of output i), never the tensor."""
+    output_meta[i] is an :class:`OutputMeta` (shape / dtype / device of output i), never the tensor.
+    saved_outputs: indices of outputs the backward reads (saved the way autograd saves an output, which forms no cycle);
+    bwd then gets them as a fifth argument, a tuple in that order."""
     needs = torch.is_grad_enabled() and any(t is not None and torch.is_tensor(t) and t.requires_grad for t in tensors)
     if not needs:
         with torch.no_grad():
             return fn(*tensors)
-    return _HipNode.apply(name, fn, bwd, tuple(non_differentiable_outputs), *tensors)
+    return _HipNode.apply(name, fn, bwd, (tuple(non_differentiable_outputs), tuple(saved_outputs)), *tensors)
 
 
 def zeros_like_or(g, ref):

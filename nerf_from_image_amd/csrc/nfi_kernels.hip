@@ -15,7 +15,7 @@ using namespace nfi;
 // error plumbing, argument checks and the LDS staging helpers shared with nfi_backward_field.hip: nfi_host.hpp
 thread_local char nfi_err_buf[256] = "";
 extern "C" const char* nfi_last_error(void) { return nfi_err_buf; }
-extern "C" int nfi_version(void) { return 105; }
+extern "C" int nfi_version(void) { return 106; }
 
 
 // ------------------------------------------------------------------------------------------------
@@ -2719,4 +2719,7 @@ extern "C" int nfi_render_fwd(const nfi_render_args* a, nfi_stream_t stream) {
   if (a->event_stop) (void)hipEventRecord((hipEvent_t)a->event_stop, s);
   return check_launch("render_fwd");
 }
+
+// the synthesis-layer tail comes last: the code object keeps every earlier kernel where it was
+#include "nfi_synth_tail.inc"
 #endif  // NFI_SINGLE_KERNEL

@@ -339,8 +339,8 @@ def hip_forward(self, viewdir, c, request_model_outputs=['sampler'], model_input
     kwargs = {'noise_mode': 'const'} if model_inputs.get('freeze_noise') else {}
     if 'path_length' in request_model_outputs:
         # second-order output: keep the (once-differentiable) fused hand-off node out of this call's graph
-        from . import handoff
-        with handoff.unfused(self.synthesis_network):
+        from . import handoff, synthesis
+        with handoff.unfused(self.synthesis_network), synthesis.unfused(self.synthesis_network):
             planes = self.synthesis_network(w_syn, **kwargs)
     else:
         planes = self.synthesis_network(w_syn, **kwargs)
@@ -492,12 +492,13 @@ def wrapped_forward(self, viewdir, c, request_model_outputs=['sampler'], model_i
     use_vd = bool(self.use_viewdir) and viewdir is not None
     hip_vd = use_vd and getattr(self, 'nfi_hip_viewdir_mapper', False)
     import contextlib
-    from . import handoff
+    from . import handoff, synthesis
     with contextlib.ExitStack() as stack:
         stack.callback(hook.remove)
         if 'path_length' in req:
             # differentiated twice (generator.py:484-499): the fused hand-off node is first-order only
             stack.enter_context(handoff.unfused(self.synthesis_network))
+            stack.enter_context(synthesis.unfused(self.synthesis_network))
         cap = stack.enter_context(_capture_ray_feature(self.viewdir_mapper)) if use_vd and not hip_vd else None
         if hip_vd:
             # the mapper's forward was replaced at attach time (_hip_mapper_forward): it puts its HIP node's output here
@@ -547,7 +548,7 @@ def bake(model, model_input, model_inputs={}):
 
 
 def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_handoff=False, hip_viewdir_mapper=False,
-           deterministic_backward=False):
+           deterministic_backward=False, fused_synthesis_tail=False):
     """Gives a reference-style Generator the HIP sampler.  Returns the same module.
 
     deterministic_backward: the sampler closure's backward (the staged path) runs the field backward in its ordered mode
@@ -568,6 +569,12 @@ def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_hando
 
     fused_handoff: also fuse the tail of the last synthesis block (upsample + torgb + add, stylegan.py:424-433) into
     the HIP kernel that writes texels directly (nerf_from_image_amd.handoff): no NCHW <-> channel-last pass remains.
+
+    fused_synthesis_tail (off by default): everything each synthesis layer does after its convolution (resample filter of
+    the up layers, noise, demodulation, bias, gain, leaky ReLU; stylegan.py:101-105, 139-140, 351-355) runs as one HIP node
+    per layer (nerf_from_image_amd.synthesis.fuse_layers).  Its sums run in a fixed order, with or without
+    deterministic_backward.  First-order only: a forward that asks for path_length runs the layers' own forwards.  Layers
+    fused by an earlier call stay fused (synthesis.unfuse_layers undoes it).
 
     hip_regularisers: also serve sdf_eikonal / sdf_distance / total_variation / entropy losses of a module that has
     its own forward from the HIP kernels (bare containers always do).
@@ -593,6 +600,9 @@ def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_hando
     from . import handoff
     if fused_handoff or handoff.fused_block(model.synthesis_network) is not None:    # fused earlier: stays fused, follows the switch
         handoff.fuse_last_block(model.synthesis_network, deterministic_backward=deterministic_backward)
+    if fused_synthesis_tail:
+        from . import synthesis
+        synthesis.fuse_layers(model.synthesis_network)
     if type(model).forward is not torch.nn.Module.forward and not hasattr(model, '_nfi_original_forward'):
         model._nfi_original_forward = model.forward          # bound method of the reference class
         model.forward = types.MethodType(wrapped_forward, model)

@@ -5,6 +5,7 @@ its inputs, allocates the outputs as torch tensors, and passes raw device
 pointers plus ``torch.cuda.current_stream()`` to libnfi_hip.so.  Nothing here
 computes on the CPU and nothing falls back to ATen ops.
 """
+import functools
 import math
 
 import torch
@@ -1021,6 +1022,115 @@ def lpips_head_bwd(g_out, x, y, weight, y_normalized=False, eps=1e-10, need_x=Tr
         _lib.call_struct('nfi_lpips_head_bwd', 'nfi_lpips_head_args', _stream(x), x=x, y=y, y_normalized=int(bool(y_normalized)),
                          weight=weight, eps=float(eps), g_out=g_out, g_x=g_x, g_y=g_y, **kw)
     return g_x, g_y
+
+
+# --------------------------------------------------------------------------- #
+# tail of a synthesis layer (models/stylegan.py:101-105, 139-140, 351-355; csrc/nfi_synth_tail.inc)
+# --------------------------------------------------------------------------- #
+def synth_tail_args(y, dcoefs, noise, bias, taps, act_gain, up, activate=True, slope=0.2, where='synth_tail'):
+    """The checked, dense arguments of nfi_synth_tail_args shared by the forward and the backward, as a dict.  A caller that
+    runs both on the same tensors (synthesis.layer_tail) checks once and hands the dict to synth_tail_launch /
+    synth_tail_bwd_launch."""
+    y, dcoefs, bias = _f32c(y, 'y'), _f32c(dcoefs, 'dcoefs'), _f32c(bias, 'bias')
+    if y.dim() != 4 or y.numel() == 0 or y.shape[2] != y.shape[3]:
+        raise ValueError('%s: y must be a non-empty square [B,C,N,N], got %s' % (where, tuple(y.shape)))
+    b, c, n = y.shape[0], y.shape[1], y.shape[2]
+    r = n - 1 if up else n
+    if r < 1:
+        raise ValueError('%s: an up layer needs y of side R + 1 >= 2, got %s' % (where, tuple(y.shape)))
+    if tuple(dcoefs.shape) != (b, c) or bias.numel() != c:
+        raise ValueError('%s: dcoefs must be [%d,%d] and bias [%d], got %s and %s' % (where, b, c, c, tuple(dcoefs.shape), tuple(bias.shape)))
+    if not act_gain > 0:
+        raise ValueError('%s: act_gain must be positive, got %r' % (where, act_gain))
+    if not slope >= 0:
+        raise ValueError('%s: slope must not be negative, got %r' % (where, slope))
+    shared = 0
+    if noise is not None:
+        noise = _f32c(noise, 'noise')
+        if tuple(noise.shape) == (r, r):
+            shared = 1
+        elif tuple(noise.shape) != (b, 1, r, r):
+            raise ValueError('%s: noise must be [%d,1,%d,%d] or [%d,%d], got %s' % (where, b, r, r, r, r, tuple(noise.shape)))
+    if up:
+        if taps is None:
+            raise ValueError('%s: an up layer needs its resample_filter' % where)
+        taps = _f32c(taps, 'resample_filter')
+        if tuple(taps.shape) != (4, 4):
+            raise ValueError('%s: resample_filter must be [4,4], got %s' % (where, tuple(taps.shape)))
+    else:
+        taps = None
+    for t, name in ((dcoefs, 'dcoefs'), (bias, 'bias'), (noise, 'noise'), (taps, 'resample_filter')):
+        if t is not None and t.device != y.device:
+            raise ValueError('%s: %s lives on %s, y on %s' % (where, name, t.device, y.device))
+    kw = dict(batch=b, channels=c, resolution=r, in_size=n, up=int(bool(up)), activate=int(bool(activate)), act_gain=float(act_gain),
+              slope=float(slope), y=y, dcoefs=dcoefs, bias=bias, taps=taps, noise=noise, noise_shared=shared)
+    return kw
+
+
+@functools.lru_cache(maxsize=None)
+def _synth_tail_workspace_bytes(b, c, r, up):
+    return _lib.struct_query('nfi_synth_tail_bwd_workspace_bytes', 'nfi_synth_tail_args', batch=b, channels=c, resolution=r, up=up)
+
+
+def synth_tail(y, dcoefs, noise, bias, resample_filter, act_gain, up, activate=True, slope=0.2):
+    """Everything SynthesisLayer.forward does after its convolution (models/stylegan.py:101-105, 139-140, 351-355), one launch:
+    y [B,C,R+1,R+1] with up (the transposed convolution's output; filtered by 4 * resample_filter [4,4], zero padded) or
+    [B,C,R,R] without; dcoefs [B,C]; noise None, [B,1,R,R] or [R,R]; bias [C] ->
+    lrelu_slope(((noise + f * dcoefs) + bias) * act_gain), dense [B,C,R,R] (no lrelu with activate=False).  The filter's
+    taps are read on the device."""
+    return synth_tail_launch(synth_tail_args(y, dcoefs, noise, bias, resample_filter, act_gain, up, activate, slope))
+
+
+def synth_tail_launch(kw):
+    """synth_tail on arguments synth_tail_args has checked."""
+    r = kw['resolution']
+    out = torch.empty((kw['batch'], kw['channels'], r, r), dtype=torch.float32, device=kw['y'].device)
+    with torch.cuda.device(out.device):
+        _lib.call_struct('nfi_synth_tail_fwd', 'nfi_synth_tail_args', _stream(out), out=out, **kw)
+    return out
+
+
+def synth_tail_bwd(g_out, out, y, dcoefs, noise, bias, resample_filter, act_gain, up, activate=True, slope=0.2,
+                   need_y=True, need_dcoefs=True, need_bias=True, need_noise=False):
+    """Gradients of synth_tail for the upstream g_out [B,C,R,R]; out is the forward's result (the sign of the
+    pre-activation is read from it).  Returns a dict with whichever of g_y (y's shape), g_dcoefs [B,C], g_bias [C] and
+    g_noise (noise's shape) were asked for.  Every sum runs in a fixed order (no atomics): the same bits on every call."""
+    kw = synth_tail_args(y, dcoefs, noise, bias, resample_filter, act_gain, up, activate, slope, 'synth_tail_bwd')
+    b, c, r = kw['batch'], kw['channels'], kw['resolution']
+    g_out, out = _f32c(g_out, 'g_out'), _f32c(out, 'out')
+    if tuple(g_out.shape) != (b, c, r, r) or tuple(out.shape) != (b, c, r, r) or g_out.device != out.device or out.device != kw['y'].device:
+        raise ValueError('synth_tail_bwd: g_out and out must be [%d,%d,%d,%d] on %s, got %s and %s' % (
+            b, c, r, r, kw['y'].device, tuple(g_out.shape), tuple(out.shape)))
+    if need_noise and noise is None:
+        raise ValueError('synth_tail_bwd: need_noise without a noise input')
+    if not (need_y or need_dcoefs or need_bias or need_noise):
+        raise ValueError('synth_tail_bwd: no gradient is wanted')
+    return synth_tail_bwd_launch(kw, g_out, out, need_y, need_dcoefs, need_bias, need_noise)
+
+
+def synth_tail_bwd_launch(kw, g_out, out, need_y, need_dcoefs, need_bias, need_noise):
+    """synth_tail_bwd on arguments synth_tail_args has checked; g_out and out dense float32 [B,C,R,R] on their device."""
+    b, c, r = kw['batch'], kw['channels'], kw['resolution']
+    dev = out.device
+    res = {}
+    if need_y:
+        res['g_y'] = torch.empty_like(kw['y'])
+    if need_dcoefs:
+        res['g_dcoefs'] = torch.empty((b, c), dtype=torch.float32, device=dev)
+    if need_bias:
+        res['g_bias'] = torch.empty((c,), dtype=torch.float32, device=dev)
+    if need_noise:
+        res['g_noise'] = torch.empty(kw['noise'].shape, dtype=torch.float32, device=dev)
+    ws, n_ws = None, 0
+    if need_dcoefs or need_bias:
+        n_ws = _synth_tail_workspace_bytes(b, c, r, kw['up'])
+        if n_ws == 0:
+            raise RuntimeError('synth_tail_bwd: shape not supported: %s' % (tuple(kw['y'].shape),))
+        ws = torch.empty((n_ws // 8,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call_struct('nfi_synth_tail_bwd', 'nfi_synth_tail_args', _stream(out), out=out, g_out=g_out, workspace=ws,
+                         workspace_bytes=n_ws, **dict(kw, **res))
+    return res
 
 
 # --------------------------------------------------------------------------- #

@@ -100,7 +100,8 @@ def _time_steps(step, iters, warmup):
     return {'ms_median': per[len(per) // 2], 'ms_min': per[0], 'ms_max': per[-1], 'iters': iters}
 
 
-def _scene(geometry, batch, dev, impl, texels, fused_handoff=False, hip_regularisers=False, channels_last=False):
+def _scene(geometry, batch, dev, impl, texels, fused_handoff=False, hip_regularisers=False, channels_last=False,
+           fused_synthesis_tail=False):
     import copy
     import reference_cases as rc
     import nerf_from_image_amd.generator as nfi_gen
@@ -109,7 +110,7 @@ def _scene(geometry, batch, dev, impl, texels, fused_handoff=False, hip_regulari
     sc = rc.build_scene(geometry, batch, dev)
     if impl == 'hip':
         model = nfi_gen.attach(copy.deepcopy(sc.gen), texel_dtype=rc.texel_code(texels), hip_regularisers=hip_regularisers,
-                               fused_handoff=fused_handoff)
+                               fused_handoff=fused_handoff, fused_synthesis_tail=fused_synthesis_tail)
         ren = nfi_render.make_render(sc.args, sc.dcfg)
     else:
         model = sc.gen
@@ -159,9 +160,10 @@ def leg_render(dev, impl, batch=8, texels='fp32', iters=20, warmup=3, markers=Fa
     return r
 
 
-def leg_inversion(dev, impl, batch=4, texels='fp32', iters=12, warmup=3, markers=False, res=128, samples=64):
+def leg_inversion(dev, impl, batch=4, texels='fp32', iters=12, warmup=3, markers=False, res=128, samples=64,
+                  fused_synthesis_tail=False):
     import reference_cases as rc
-    sc, model, ren = _scene('p3d', batch, dev, impl, texels)
+    sc, model, ren = _scene('p3d', batch, dev, impl, texels, fused_synthesis_tail=fused_synthesis_tail)
     model.requires_grad_(False)
     with torch.no_grad():
         tgt = rc.reference_render(sc, res, samples, None)
@@ -193,8 +195,9 @@ def leg_inversion(dev, impl, batch=4, texels='fp32', iters=12, warmup=3, markers
 
 
 def leg_gstep(dev, impl, batch=4, texels='fp32', iters=12, warmup=3, markers=False, res=128, samples=64, fused_handoff=False,
-              path_length=False, hip_regularisers=True):
-    sc, model, ren = _scene('cub', batch, dev, impl, texels, fused_handoff=fused_handoff, hip_regularisers=hip_regularisers)
+              path_length=False, hip_regularisers=True, fused_synthesis_tail=False):
+    sc, model, ren = _scene('cub', batch, dev, impl, texels, fused_handoff=fused_handoff, hip_regularisers=hip_regularisers,
+                            fused_synthesis_tail=fused_synthesis_tail)
     model.train().requires_grad_(True)
     g = torch.Generator().manual_seed(77)
     t_img = torch.cat([torch.rand(batch, res, res, 3, generator=g) * 2 - 1, (torch.rand(batch, res, res, 1, generator=g) > 0.5).float()],
@@ -280,6 +283,8 @@ def main():
     ap.add_argument('--markers', action='store_true')
     ap.add_argument('--fused-handoff', action='store_true')
     ap.add_argument('--path-length', action='store_true')
+    ap.add_argument('--fused-synthesis-tail', action='store_true',
+                    help='inversion and gstep legs, hip: attach(fused_synthesis_tail=True), every synthesis layer\'s tail as one HIP node')
     ap.add_argument('--reference-regularisers', action='store_true', help='hip: leave the regulariser branch to the original forward')
     ap.add_argument('--sidecar', help='JSON written for tools/phase_split.py (marker table, steps, warm-up)')
     ap.add_argument('--quick', action='store_true')
@@ -298,6 +303,9 @@ def main():
         kw.update(channels_last=a.channels_last, graph=a.graph, views=a.views)
     if a.leg == 'gstep':
         kw.update(fused_handoff=a.fused_handoff, path_length=a.path_length, hip_regularisers=not a.reference_regularisers)
+    if a.fused_synthesis_tail:                                      # the key appears in the result only with the flag
+        assert a.leg in ('inversion', 'gstep') and a.impl == 'hip', '--fused-synthesis-tail is an option of the drop-in\'s producer legs'
+        kw['fused_synthesis_tail'] = True
     r = LEGS[a.leg](dev, a.impl, **kw)
     r.update(leg=a.leg, impl=a.impl, **{k: v for k, v in kw.items() if k not in ('iters', 'warmup')})
     if a.sidecar:
