@@ -1,4 +1,4 @@
-// nfi_backward_field.inc — backward of the triplane field query (included by nfi_kernels.hip).
+// nfi_backward_field.inc — backward of the triplane field query (included by nfi_backward_field.hip).
 //
 // Reference: autograd through the sampler closure (models/generator.py:587-681): grid_sample
 // backward (atomic scatter-add into the planes + coordinate gradients), the decoder MLP, the

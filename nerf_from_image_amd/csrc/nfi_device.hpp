@@ -174,6 +174,18 @@ __device__ __forceinline__ float row_allreduce_sum(float v) {
   return v;
 }
 __device__ __forceinline__ float wave_sum(float v) { return sum_xor32(sum_xor16(row_allreduce_sum(v))); }
+// sum over a block of 256 threads in double, every thread gets it; red: 4 doubles of LDS (image metrics, LPIPS head)
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  (void)b;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[wave] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
 __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, dpp_f32<kDppQuadXor1>(v, v));
   v = fmaxf(v, dpp_f32<kDppQuadXor2>(v, v));

@@ -1,5 +1,5 @@
 // nfi_filter.inc — zero-padded, same-size separable correlation of an image batch: the progressive discriminator blur,
-// lib/ops.py:29-55 (filt2d with a 1-D kernel, blur).  Included by nfi_kernels.hip.
+// lib/ops.py:29-55 (filt2d with a 1-D kernel, blur).  Included by nfi_modules.hip.
 //
 // One launch does both passes.  A block owns one tile of kFilterTileH x kFilterTileW output pixels of one (image, channel)
 // plane: it stages the tile and its halo of `radius` pixels (input - background, 0 outside the image) in LDS, filters the

@@ -1,4 +1,4 @@
-// nfi_handoff.inc — the plane producer's last step written straight into texel layout (included by nfi_kernels.hip;
+// nfi_handoff.inc — the plane producer's last step written straight into texel layout (included by nfi_modules.hip;
 // SURVEY.md 8(f)3).
 //
 // Reference: the tail of the last StyleGAN2 synthesis block (models/stylegan.py:383-435, SynthesisBlock.forward):

@@ -1,4 +1,4 @@
-// Host-side plumbing shared by the translation units of libnfi_hip.so (nfi_kernels.hip, nfi_backward_field.hip):
+// Host-side plumbing shared by the translation units of libnfi_hip.so (nfi_kernels.hip, nfi_backward_field.hip, nfi_modules.hip):
 // error buffer behind nfi_last_error(), argument checks, and the device helpers that stage the decoder image in LDS.
 #pragma once
 #include "nfi_device.hpp"

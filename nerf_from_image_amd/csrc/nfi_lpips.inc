@@ -1,6 +1,6 @@
 // nfi_lpips.inc — the distance head of LPIPS, everything lib/metrics.py:104-110, 130-133 does AFTER the VGG convolutions, one
 // layer per call: unit-normalise both feature maps over the channels, subtract, square, weigh the channels (the lin layer's
-// 1x1 convolution to one channel) and take the spatial mean.  Included by nfi_kernels.hip.
+// 1x1 convolution to one channel) and take the spatial mean.  Included by nfi_modules.hip.
 //
 //   rx[b,p] = sqrt(sum_c x[b,c,p]^2)     xh = x / (rx + eps)        (eps is added to the norm, not put under the root)
 //   ry, yh likewise; with y_normalized:  yh = y as given            (lib/metrics.py:126-128, cached features)

@@ -1,4 +1,4 @@
-// nfi_neighbours.inc — the inversion loop's neighbours of the renderer (included by nfi_kernels.hip; SURVEY.md 8(f)4).
+// nfi_neighbours.inc — the inversion loop's neighbours of the renderer (included by nfi_modules.hip; SURVEY.md 8(f)4).
 //
 // (1) The 2-D augmentation warp of run.py:720-769 (augment_impl): per image a rotation / isotropic scale /
 //     translation drawn on the host, F.affine_grid(align_corners=False) + F.grid_sample(bilinear, zeros padding,
@@ -218,18 +218,6 @@ struct MetricParams {
   const float* mask_pred; const float* mask_real; int64_t per_mask;   // iou
   float* psnr; float* iou; int* out_of_range;
 };
-
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, v);
-  (void)b;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 __global__ __launch_bounds__(256) void image_metrics_kernel(MetricParams k) {
   __shared__ double red[4];

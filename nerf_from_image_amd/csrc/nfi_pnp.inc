@@ -1,4 +1,4 @@
-// nfi_pnp.inc — camera pose from a canonical-coordinate map (included by nfi_kernels.hip).
+// nfi_pnp.inc — camera pose from a canonical-coordinate map (included by nfi_modules.hip).
 //
 // Reference: lib/pose_estimation.py:30-131 (compute_pose_pnp), called per inversion batch through
 // run.py:1709-1740 (estimate_poses_batch) with a .cpu().numpy() round trip and OpenCV's solvePnPGeneric

@@ -1,4 +1,4 @@
-// nfi_pose.inc — the pose algebra of the inversion loop, lib/pose_utils.py (included by nfi_kernels.hip).
+// nfi_pose.inc — the pose algebra of the inversion loop, lib/pose_utils.py (included by nfi_modules.hip).
 //
 // Thread = image in every kernel; 64-thread blocks, a grid that covers n_images, a tail guard.  The work per image is a
 // few hundred flops, so what a call costs is its launch: each entry is ONE launch where the reference runs a chain of

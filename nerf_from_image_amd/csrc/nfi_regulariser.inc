@@ -1,5 +1,5 @@
 // nfi_regulariser.inc — the distance field and its spatial gradient as ONE differentiable operator
-// (included by nfi_kernels.hip).
+// (included by nfi_modules.hip).
 //
 // Reference: the regulariser branch of Generator.forward (models/generator.py:505-585).  The eikonal term needs
 // x_grad = d(sdf)/d(x_in) WITH a graph (torch.autograd.grad(..., create_graph=True), 534-540), which is why the

@@ -1,6 +1,6 @@
 // nfi_synth_tail.inc — everything SynthesisLayer.forward does AFTER its convolution, models/stylegan.py:101-105 (the 4x4
 // resample filter of an `up` layer, filter2d with gain 4), 139-140 (addcmul(noise, x, dcoefs)), 351-355 (+ bias, * act_gain,
-// leaky_relu), as one launch forward and at most two (+ one for the noise gradient) backward.  Included by nfi_kernels.hip.
+// leaky_relu), as one launch forward and at most two (+ one for the noise gradient) backward.  Included by nfi_modules.hip.
 //
 //   f   = up ? sum_{a,b} (4 taps[a][b]) y[i + a - 1, j + b - 1]  (0 outside y, which is [R+1, R+1])  :  y
 //   out = lrelu(((noise + f * dcoefs[b,c]) + bias[c]) * act_gain)

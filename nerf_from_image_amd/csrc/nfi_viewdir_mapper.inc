@@ -1,5 +1,5 @@
 // nfi_viewdir_mapper.inc — the per-ray trunk of ViewDirectionMapper (models/generator.py:194-241) as one kernel forward and
-// one kernel backward (included by nfi_kernels.hip).
+// one kernel backward (included by nfi_modules.hip).
 //
 //   x = lrelu(fc0 v);  x = (lrelu(norm2 fc2 lrelu(norm1 fc1 x)) + x) c;  x = (lrelu(norm4 fc4 lrelu(norm3 fc3 x)) + x) c;
 //   feature = fc6 lrelu(fc5 x)          c = sqrt(2)/2, lrelu slope 0.2, LayerNorm(64) with biased variance and eps 1e-5,

@@ -1,5 +1,6 @@
 """CPU tests of the measurement tooling: tools/phase_split.py on a synthetic kernel trace (the renderer / producer / other
-split of profiles/r6/e2e is only as good as this parser), and the limits DESIGN.md is held to."""
+split of profiles/r6/e2e is only as good as this parser), tools/isa_diff.py on synthetic device assembly, and the limits
+DESIGN.md is held to."""
 import csv
 import json
 import os
@@ -67,6 +68,48 @@ def test_phase_split_on_a_synthetic_trace(tmp_path):
     assert g['forward_rest'] == 0.0
     assert abs(d['libnfi_kernels_ms_per_step'] - 2.7) < 1e-6 and d['steps'] == 3
     assert abs(sum(d['group_share_of_gpu_time'].values()) - 1.0) < 1e-9
+
+
+def _asm(kernels, first=0):
+    """Device assembly in the compiler's form: per (name, operand) one kernel with a branch label, a .Ltmp, a comment, its
+    descriptor block and .Lfunc_end; the label counters start at `first`, as they would further down a larger file."""
+    out = ['\t.text', '\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"']
+    for i, (name, operand) in enumerate(kernels, first):
+        out += ['\t.protected\t%s ; -- Begin function %s' % (name, name), '\t.globl\t%s' % name, '\t.p2align\t8',
+                '\t.type\t%s,@function' % name, '%s:   ; @%s' % (name, name), '; %%bb.0:',
+                '\ts_load_dwordx2 s[0:1], s[0:1], 0x0', '.Ltmp%d:' % (7 * i), '\tv_mov_b32_e32 v1, %s' % operand,
+                '\ts_cbranch_execz .LBB%d_2' % i, '.LBB%d_2:        ;   in Loop: Header=BB%d_1 Depth=1' % (i, i), '\ts_endpgm',
+                '\t.section\t.rodata,"a",@progbits', '\t.amdhsa_kernel %s' % name, '\t\t.amdhsa_next_free_vgpr 10',
+                '\t.end_amdhsa_kernel', '\t.text', '.Lfunc_end%d:' % i,
+                '\t.size\t%s, .Lfunc_end%d-%s' % (name, i, name), '; codeLenInByte = %d' % (512 + i)]
+    return '\n'.join(out) + '\n'
+
+
+def test_isa_diff_compares_kernels_by_name_whatever_their_place(tmp_path):
+    """tools/isa_diff.py: label renumbering and comments are no difference; a changed operand, a changed descriptor and a
+    kernel on one side only are each reported by name, with exit status 1."""
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import isa_diff
+    a, b, c = ('_Z1aPf', '0x3e000000'), ('_Z1bPf', 'v7'), ('_Z1cPf', 'v9')
+    old = isa_diff.functions(_asm([a, b, c]))
+    assert sorted(old) == ['_Z1aPf', '_Z1bPf', '_Z1cPf'] and all(kernel for _, kernel in old.values())
+    assert ';' not in old['_Z1bPf'][0] and '.amdhsa_next_free_vgpr 10' in old['_Z1bPf'][0]
+    # the same kernels in another order and from another place in their file, an extra comment line: nothing to report
+    moved = isa_diff.functions(_asm([c, a, b], first=40).replace('\ts_endpgm', '; a remark\n\ts_endpgm'))
+    assert isa_diff.diff(old, moved) == []
+    assert isa_diff.diff(old, isa_diff.functions(_asm([a, ('_Z1bPf', 'v8'), c]))) == ['differs: _Z1bPf']
+    assert isa_diff.diff(old, isa_diff.functions(_asm([a, b, c]).replace('vgpr 10', 'vgpr 12', 1))) == ['differs: _Z1aPf']
+    assert isa_diff.diff(old, isa_diff.functions(_asm([a, b]))) == ['missing (old side only): _Z1cPf']
+    assert isa_diff.diff(isa_diff.functions(_asm([a, b])), old) == ['extra (new side only): _Z1cPf']
+    # the command line: two files against one, counts printed, exit status
+    for name, text in (('ab.s', _asm([a, b])), ('c.s', _asm([c])), ('all.s', _asm([c, b, a], first=3)), ('short.s', _asm([a, b]))):
+        (tmp_path / name).write_text(text)
+    run = lambda *args: subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'isa_diff.py')] + [str(tmp_path / x) if x != '--' else x for x in args],
+                                       capture_output=True, text=True, timeout=60)
+    p = run('ab.s', 'c.s', '--', 'all.s')
+    assert p.returncode == 0 and p.stdout.splitlines()[:2] == ['old: 3 kernels, 3 functions in all', 'new: 3 kernels, 3 functions in all'], p.stdout + p.stderr
+    p = run('ab.s', 'c.s', '--', 'short.s')
+    assert p.returncode == 1 and 'missing (old side only): _Z1cPf' in p.stdout and 'new: 2 kernels' in p.stdout, p.stdout + p.stderr
 
 
 def test_design_md_stays_a_current_state_document():

@@ -1,4 +1,4 @@
-"""A/B builds of the CURRENT tree's forward translation unit with extra compiler flags, timed on the render workloads.
+"""A/B builds of the CURRENT tree's forward translation unit (nfi_kernels.hip) with extra compiler flags, timed on the render workloads.
 
     python tools/probes/ab_render.py build name=-DFLAG[,-DFLAG2] [name2=...]     # here: build/ab/libnfi_<name>.so
     python tools/probes/ab_render.py build-bwd name=-DFLAG ...                   # the same for the backward unit
@@ -20,8 +20,8 @@ def build(specs, unit=0):
     from concurrent.futures import ThreadPoolExecutor
     os.makedirs(OUT, exist_ok=True)
     units = [u for u, _ in entry.UNITS]
-    bwd_obj = os.path.join(ROOT, 'build', units[1 - unit].replace('.hip', '.o'))      # the OTHER unit, as built for the product
-    assert os.path.exists(bwd_obj), 'run python __graft_entry__.py first'
+    other_objs = [os.path.join(ROOT, 'build', u.replace('.hip', '.o')) for u in units if u != units[unit]]      # the OTHER units, as built for the product
+    assert all(os.path.exists(o) for o in other_objs), 'run python __graft_entry__.py first'
     src = os.path.join(entry.CSRC, units[unit])
     unit_flags = entry.UNITS[unit][1]
 
@@ -29,8 +29,8 @@ def build(specs, unit=0):
         name, _, flags = spec.partition('=')
         obj = os.path.join(OUT, '%s.o' % name)
         entry.compile_unit(src, unit_flags + [f for f in flags.split(',') if f], obj)
-        subprocess.check_call([os.environ.get('HIPCC', '/opt/rocm/bin/hipcc'), '--offload-arch=gfx950', '-fPIC', '-shared', obj,
-                               bwd_obj, '-o', os.path.join(OUT, 'libnfi_%s.so' % name)])
+        subprocess.check_call([os.environ.get('HIPCC', '/opt/rocm/bin/hipcc'), '--offload-arch=gfx950', '-fPIC', '-shared', obj] +
+                              other_objs + ['-o', os.path.join(OUT, 'libnfi_%s.so' % name)])
         os.remove(obj)
         return name
     with ThreadPoolExecutor(3) as pool:

@@ -88,8 +88,8 @@ VARIANTS = ['noslp', 'slp', 'slp_nop_dpp', 'slp_nop_mul', 'slp_scalar', 'slp_bpe
 
 def build(names=None):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    main_obj = os.path.join(ROOT, 'build', 'nfi_kernels.o')
-    assert os.path.exists(main_obj), 'run python __graft_entry__.py first (build/nfi_kernels.o)'
+    main_objs = [os.path.join(ROOT, 'build', o) for o in ('nfi_kernels.o', 'nfi_modules.o')]      # the other units, as built for the product
+    assert all(os.path.exists(o) for o in main_objs), 'run python __graft_entry__.py first (build/nfi_kernels.o, build/nfi_modules.o)'
     src = open(os.path.join(CSRC, 'nfi_backward_field.inc')).read()
     procs = []
     for name in (names or VARIANTS):
@@ -107,7 +107,7 @@ def build(names=None):
             [hipcc] + FLAGS + extra + ['-c', os.path.join(d, 'nerf_from_image_amd', 'csrc', 'nfi_backward_field.hip'), '-o', obj])))
     for name, obj, p in procs:
         assert p.wait() == 0, name
-        subprocess.check_call([hipcc, '--offload-arch=gfx950', '-fPIC', '-shared', main_obj, obj, '-o',
+        subprocess.check_call([hipcc, '--offload-arch=gfx950', '-fPIC', '-shared'] + main_objs + [obj, '-o',
                                os.path.join(OUT, 'libnfi_%s.so' % name)])
         shutil.rmtree(os.path.join(OUT, name))
         print('built', name)

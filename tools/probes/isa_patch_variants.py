@@ -64,7 +64,8 @@ def main():
            '-output=' + fb)
         sh('/opt/rocm/bin/hipcc', *FLAGS, '--cuda-host-only', '-Xclang', '-fcuda-include-gpubinary', '-Xclang', fb, '-c', src,
            '-o', host)
-        sh('/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-fPIC', '-shared', os.path.join(ROOT, 'build', 'nfi_kernels.o'), host,
+        sh('/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-fPIC', '-shared', os.path.join(ROOT, 'build', 'nfi_kernels.o'),
+           os.path.join(ROOT, 'build', 'nfi_modules.o'), host,
            '-o', os.path.join(OUT, 'libnfi_%s.so' % name))
         print('built', name, flush=True)
 

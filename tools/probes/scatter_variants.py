@@ -34,16 +34,16 @@ def build(names):
     import __graft_entry__ as entry
     from concurrent.futures import ThreadPoolExecutor
     os.makedirs(OUT, exist_ok=True)
-    fwd_obj = os.path.join(ROOT, 'build', 'nfi_kernels.o')
-    assert os.path.exists(fwd_obj), 'run python __graft_entry__.py first'
+    fwd_objs = [os.path.join(ROOT, 'build', o) for o in ('nfi_kernels.o', 'nfi_modules.o')]      # the other units, as built for the product
+    assert all(os.path.exists(o) for o in fwd_objs), 'run python __graft_entry__.py first'
     src = os.path.join(entry.CSRC, 'nfi_backward_field.hip')
     base = dict(entry.UNITS)['nfi_backward_field.hip']
 
     def one(name):
         obj = os.path.join(OUT, 'bwd_%s.o' % name)
         seen, n = entry.compile_unit(src, base + VARIANTS[name], obj)
-        subprocess.check_call([os.environ.get('HIPCC', '/opt/rocm/bin/hipcc'), '--offload-arch=gfx950', '-fPIC', '-shared',
-                               fwd_obj, obj, '-o', os.path.join(OUT, 'libnfi_bwd_%s.so' % name)])
+        subprocess.check_call([os.environ.get('HIPCC', '/opt/rocm/bin/hipcc'), '--offload-arch=gfx950', '-fPIC', '-shared'] +
+                              fwd_objs + [obj, '-o', os.path.join(OUT, 'libnfi_bwd_%s.so' % name)])
         os.remove(obj)
         return name, n
     with ThreadPoolExecutor(4) as pool:

@@ -1,7 +1,9 @@
 """Per-kernel register / scratch / LDS / occupancy table from `hipcc -Rpass-analysis=kernel-resource-usage`.
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -c nerf_from_image_amd/csrc/nfi_kernels.hip \
         -o /tmp/nfi.o -Rpass-analysis=kernel-resource-usage 2> /tmp/res_usage.txt
-  python tools/resource_usage.py /tmp/res_usage.txt [substring ...]"""
+  python tools/resource_usage.py /tmp/res_usage.txt [substring ...]
+(nfi_kernels.hip: render, stage and field-query kernels; nfi_backward_field.hip - with its flags of __graft_entry__.UNITS -
+and nfi_modules.hip, every other family, are the library's other two translation units: same recipe, one run each)"""
 import re
 import subprocess
 import sys
