@@ -55,6 +55,13 @@ enum { NFI_TEXEL_F32 = 0, NFI_TEXEL_BF16 = 1, NFI_TEXEL_F16 = 2 };
  *                               torch.channels_last - or nfi_torgb_texels_fwd - leaves in memory: read in place,
  *                               no hand-off kernel; gradient images use the layout of their texels. */
 enum { NFI_TEXELS_PLANAR = 0, NFI_TEXELS_INTERLEAVED = 1 };
+/* Pointers.  The ABI sees addresses, not strides: every array is DENSE in the shape its comment gives, on the device of
+ * the stream, and as long as that shape says - none of which an entry can check.  Alignment: `texels` and `g_texels`
+ * (every entry that has them: the field query, the fused render, the distance-gradient operator, their backwards) are
+ * gathered and scattered as 16-byte vectors and must be 16-byte aligned, as must the arguments named under "Alignment"
+ * at an entry; for every other float array, 16-byte alignment is the only one the kernels are tested with (a row of a
+ * fresh allocation).  nerf_from_image_amd/ops.py guarantees all of this for its callers: it refuses a tensor of the
+ * wrong type, device or length and copies one that is not dense or whose first byte is not on a multiple of 16. */
 
 const char* nfi_last_error(void);
 int nfi_version(void);
@@ -65,6 +72,7 @@ int nfi_version(void);
  * 501-503: planes.view(B,3,32,R,R); F.grid_sample reads NCHW).  A texel (32 channels) becomes
  * one 128-byte line (fp32) / 64-byte line (bf16).
  *   planes  [B,3,32,R,R] fp32      texels  [B,3,R,R,32] fp32|bf16
+ *   Alignment: planes and texels (both entries) are accessed as 16-byte vectors and must be 16-byte aligned.
  * ------------------------------------------------------------------------------------------ */
 int nfi_planes_to_texels(const float* planes, void* texels, int n_scenes, int plane_res,
                          int texel_dtype, nfi_stream_t stream);
@@ -665,6 +673,7 @@ int nfi_pose_project(const nfi_pose_project_args* a, nfi_stream_t stream);
  *   bwd: g_texels [B,R,R,96] -> g_x [B,Cin,R,R], g_styles [B,Cin], optional g_weight [96,Cin] + g_bias [96] (both
  *        or neither), optional g_previous_image [B,96,R/2,R/2]; all written (zeroed inside where accumulated).
  * Cin: multiple of 16, <= 256; R: multiple of 8.
+ *   Alignment: x, texels and g_texels are accessed as 16-byte vectors and must be 16-byte aligned.
  * ------------------------------------------------------------------------------------------ */
 typedef struct nfi_torgb_args {
   int n_scenes, in_channels, resolution;

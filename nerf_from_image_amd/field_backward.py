@@ -21,12 +21,17 @@ def field_query_bwd(points, texels, decoder_image, w1, w2, scene_range, n_attent
     if scatter_mode is not None and int(scatter_mode) == 2 and (viewdir is not None or points_only):
         raise NotImplementedError('field_query_bwd: scatter_mode 2 (ordered) covers the plain decoder with parameter '
                                   'gradients: not the view-direction decoder, not points_only')
-    f = ops._f32c
-    points = f(points, 'points')
+    where = 'field_query_bwd'
+    points = ops._points(points, where)
     B, P = points.shape[0], points.shape[1]
     dev = points.device
+
+    def f(t, name, n=None):
+        return ops._f32c(t, name, points, n, where)
     if texels.dtype != torch.float32 and viewdir is not None:
         raise NotImplementedError('field_query_bwd: the view-direction decoder needs fp32 texels')
+    texels, tdt, layout = ops._texels(texels, B, points, where)
+    decoder_image = ops._decoder_image(decoder_image, viewdir is not None, points, where)
     n_out = 1 + n_attention if n_attention > 0 else 4
     n3 = n_attention if n_attention > 0 else 3
     if viewdir is not None:
@@ -49,8 +54,11 @@ def field_query_bwd(points, texels, decoder_image, w1, w2, scene_range, n_attent
         out['g_points'] = torch.zeros((B, P, 3), dtype=torch.float32, device=dev)
     vd_args = {}
     if viewdir is not None:
-        rf = f(viewdir['ray_features'], 'ray_features')
-        vd_args = dict(ray_features=rf, samples_per_ray=int(viewdir['samples_per_ray']), w3=f(viewdir['w3'], 'w3'))
+        spr = int(viewdir['samples_per_ray'])
+        if spr <= 0 or P % spr:
+            raise ValueError('field_query_bwd: %d points per scene are not whole rays of %d samples' % (P, spr))
+        rf = f(viewdir['ray_features'], 'ray_features', B * (P // spr) * ops.RAY_FEATURE_PITCH)
+        vd_args = dict(ray_features=rf, samples_per_ray=spr, w3=f(viewdir['w3'], 'w3', n3 * 32))
         if not points_only:
             out['g_w3'] = torch.zeros((n3, 32), dtype=torch.float32, device=dev)
             out['g_b3'] = torch.zeros((n3,), dtype=torch.float32, device=dev)
@@ -63,13 +71,13 @@ def field_query_bwd(points, texels, decoder_image, w1, w2, scene_range, n_attent
         scatter_mode = 1 if (P >= BINNED_SCATTER_MIN_POINTS and not points_only) else 0
     fields = dict(
             n_scenes=B, points_per_scene=P,
-            points=points, texels=texels, plane_res=ops.texel_res(texels), texel_dtype=ops.texel_dtype_of(texels),
-            texel_layout=ops.texel_layout_of(texels),
-            decoder_image=decoder_image, w1=f(w1, 'w1'), w2=f(w2, 'w2'), n_attention=n_attention,
-            attention_values=f(attention_values, 'attention_values') if n_attention > 0 else None,
-            use_sdf=int(use_sdf), beta=f(beta, 'beta') if use_sdf else None, alpha=f(alpha, 'alpha') if use_sdf else None,
-            scene_range=float(scene_range), g_sigma=f(g_sigma, 'g_sigma'), g_rgb=f(g_rgb, 'g_rgb'),
-            g_sdf=f(g_sdf, 'g_sdf'), g_semantics=f(g_semantics, 'g_semantics'),
+            points=points, texels=texels, plane_res=ops.texel_res(texels), texel_dtype=tdt,
+            texel_layout=layout,
+            decoder_image=decoder_image, w1=f(w1, 'w1', 64 * 32), w2=f(w2, 'w2', n_out * 64), n_attention=n_attention,
+            attention_values=ops._attention(attention_values, n_attention, B, points, where),
+            use_sdf=int(use_sdf), beta=f(beta, 'beta', 1) if use_sdf else None, alpha=f(alpha, 'alpha', 1) if use_sdf else None,
+            scene_range=float(scene_range), g_sigma=f(g_sigma, 'g_sigma', B * P), g_rgb=f(g_rgb, 'g_rgb', 3 * B * P),
+            g_sdf=f(g_sdf, 'g_sdf', B * P), g_semantics=f(g_semantics, 'g_semantics', B * P * n_attention),
             points_only=int(points_only), normalize_g_points=int(normalize_points), scatter_mode=int(scatter_mode),
             **vd_args, **out)
     n_ws = _lib.struct_query('nfi_field_bwd_workspace_bytes', 'nfi_field_bwd_args', **fields)

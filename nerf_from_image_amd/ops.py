@@ -4,6 +4,17 @@ PyTorch is used here for device memory and streams only: every function checks
 its inputs, allocates the outputs as torch tensors, and passes raw device
 pointers plus ``torch.cuda.current_stream()`` to libnfi_hip.so.  Nothing here
 computes on the CPU and nothing falls back to ATen ops.
+
+The argument contract (tests/contract_util.py has a row per wrapper, tests/test_wrapper_contract*.py run them): the C ABI
+sees pointers and a few integers, so this layer is the only one that can know a tensor's strides, dtype, device and
+length.  Every tensor argument is therefore
+  - refused when it is not on the GPU (RuntimeError), has the wrong dtype (TypeError), lives on another device than the
+    tensor whose stream the call uses, or does not hold the element count the kernel indexes (ValueError) - _f32c with
+    `on` / `n`, _need, _texels, _decoder_image, _attention, _u_and_stride;
+  - copied when it is not dense in the layout its shape claims, or when its first byte is not on a multiple of
+    POINTER_ALIGN (a contiguous view at an odd offset into a flat buffer): kernels read texels, planes and the hand-off's
+    activations as 16-byte vectors, and no other alignment is tested for the rest - _dense.
+All of it is attribute reads on the host: a dense, aligned argument costs no launch and no device-to-host read.
 """
 import functools
 import math
@@ -75,14 +86,72 @@ def _call_ordered(entry, struct, on, unsupported, args):
     _lib.call_struct(entry, struct, _stream(on), ws, n_ws, **args)
 
 
-def _f32c(t, name):
+POINTER_ALIGN = 16         # bytes: the widest vector a kernel reads or writes through a caller's pointer
+
+
+def _dense(t, align=POINTER_ALIGN):
+    """t itself if it is contiguous and its first byte sits on a multiple of `align`, else a copy in fresh storage (a
+    contiguous view at an odd offset into a flat buffer is a copy too: kernels read rows as 8- and 16-byte vectors)."""
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % align else t
+
+
+def _dense_channels_last(t, align=POINTER_ALIGN):
+    """_dense for a [B,C,H,W] tensor the kernel reads as [B,H,W,C]."""
+    t = t.contiguous(memory_format=torch.channels_last)
+    return t.clone(memory_format=torch.preserve_format) if t.data_ptr() % align else t
+
+
+def _f32c(t, name, on=None, n=None, where=None, align=POINTER_ALIGN):
+    """t as a dense, `align`-byte aligned float32 tensor on the GPU (copied if it is not; None stays None).  on: the
+    tensor whose device and stream the call uses - another device is refused; n: the element count the kernel indexes -
+    another count is refused.  Attribute reads on the host only: no launch for a dense, aligned argument."""
     if t is None:
         return None
     if not t.is_cuda:
         raise RuntimeError('%s must live on the GPU (no CPU path in nerf_from_image_amd)' % name)
     if t.dtype != torch.float32:
         raise TypeError('%s must be float32, got %s' % (name, t.dtype))
-    return t.contiguous()
+    if on is not None and t.device != on.device:
+        raise ValueError('%s: %s lives on %s, the call runs on %s' % (where or name, name, t.device, on.device))
+    if n is not None and t.numel() != n:
+        raise ValueError('%s: %s must hold %d elements, got %s' % (where or name, name, n, list(t.shape)))
+    return _dense(t, align)
+
+
+def _texels(texels, n_scenes, on, where, fp32_only=False):
+    """(texels, dtype code, layout code) for a kernel: on the device of `on`, float32 / bfloat16 / float16 (fp32_only:
+    float32), at least n_scenes scenes, and DENSE in the layout its shape claims - a view of the right shape over other
+    strides (a permute of the other layout, a slice of a wider buffer) or at an unaligned offset is copied, as every other
+    argument is, never read as if it were dense."""
+    if not texels.is_cuda:
+        raise RuntimeError('texels must live on the GPU (no CPU path in nerf_from_image_amd)')
+    if fp32_only and texels.dtype != torch.float32:
+        raise TypeError('%s: fp32 texels only, got %s' % (where, texels.dtype))
+    tdt = texel_dtype_of(texels)
+    layout = texel_layout_of(texels)
+    if texels.device != on.device:
+        raise ValueError('%s: texels live on %s, the call runs on %s' % (where, texels.device, on.device))
+    if texels.shape[0] < n_scenes:
+        raise ValueError('%s: texels of %d scene(s) where %d are indexed' % (where, texels.shape[0], n_scenes))
+    return _dense(texels), tdt, layout
+
+
+@functools.lru_cache(maxsize=None)
+def _decoder_image_floats(viewdir):
+    lib = _lib.load()
+    return int(lib.nfi_decoder_image_floats_viewdir() if viewdir else lib.nfi_decoder_image_floats())
+
+
+def _decoder_image(image, viewdir, on, where):
+    """The operand image of decoder_pack (viewdir: of decoder_pack_viewdir): dense float32 on the device of `on`, exactly as
+    long as the kernels read it - the image of the other decoder kind is refused, not read past its end."""
+    if image is None:
+        raise ValueError('%s: decoder_image is missing' % where)
+    try:
+        return _f32c(image, 'decoder_image', on, _decoder_image_floats(bool(viewdir)), where)
+    except ValueError as e:
+        raise ValueError('%s (the image of %s is expected)' % (e, 'decoder_pack_viewdir' if viewdir else 'decoder_pack')) from None
 
 
 def _need(t, n, tail, name, where):
@@ -96,6 +165,31 @@ def _need(t, n, tail, name, where):
         raise ValueError('%s: %s must be %d rows of %s, got %s' % (where, name, n, list(tail), list(t.shape)))
 
 
+def _one_device(where, on, *tensors):
+    """Refuse (ValueError) a call whose tensors do not all live on the device of `on`, the tensor whose stream is used."""
+    for t in tensors:
+        if torch.is_tensor(t) and t.device != on.device:
+            raise ValueError('%s: an argument of shape %s lives on %s, the call runs on %s' % (where, list(t.shape), t.device, on.device))
+
+
+def _points(points, where):
+    points = _f32c(points, 'points')
+    if points.dim() != 3 or points.shape[2] != 3:
+        raise ValueError('%s: points must be [B,P,3], got %s' % (where, tuple(points.shape)))
+    return points
+
+
+def _attention(attention_values, n_attention, n_scenes, on, where):
+    """attention_values [>= n_scenes, A, 3] for A = n_attention > 0, else None (the argument is then not looked at)."""
+    if n_attention <= 0:
+        return None
+    att = _f32c(attention_values, 'attention_values', on, where=where)
+    if att is None or att.dim() != 3 or att.shape[0] < n_scenes or tuple(att.shape[1:]) != (n_attention, 3):
+        raise ValueError('%s: attention_values must be [%d or more, %d, 3], got %s' % (
+            where, n_scenes, n_attention, None if att is None else tuple(att.shape)))
+    return att
+
+
 def _need_rays(rd, n, where):
     if rd.shape[-1] != 3 or rd.numel() != 3 * n:
         raise ValueError('%s: ray_directions must hold %d rays of 3 components, got %s' % (where, n, list(rd.shape)))
@@ -105,6 +199,8 @@ def _need_rays(rd, n, where):
 def planes_to_texels(planes, texel_dtype=TEXEL_F32):
     """planes [B,3,32,R,R] fp32 -> texels [B,3,R,R,32] (fp32 or bf16)."""
     planes = _f32c(planes, 'planes')
+    if planes.dim() != 5:
+        raise ValueError('planes must be [B,3,32,R,R], got %s' % (tuple(planes.shape),))
     B, three, C, R, R2 = planes.shape
     if three != 3 or C != 32 or R != R2:
         raise ValueError('planes must be [B,3,32,R,R], got %s' % (tuple(planes.shape),))
@@ -120,6 +216,8 @@ def planes_to_texels(planes, texel_dtype=TEXEL_F32):
 def texels_to_planes(texels):
     """fp32 texels [B,3,R,R,32] -> planes [B,3,32,R,R] (adjoint layout change for gradients)."""
     texels = _f32c(texels, 'texels')
+    if texel_layout_of(texels) != TEXELS_PLANAR:
+        raise ValueError('texels_to_planes: planar texels [B,3,R,R,32] expected, got %s' % (tuple(texels.shape),))
     B, three, R, R2, C = texels.shape
     planes = torch.empty((B, 3, C, R, R), dtype=torch.float32, device=texels.device)
     lib = _lib.load()
@@ -131,7 +229,8 @@ def texels_to_planes(texels):
 
 def decoder_pack(w1, b1, w2, b2, n_attention, texel_dtype=TEXEL_F32):
     """Raw TriplanarDecoder parameters -> lane-ordered MFMA operand image (fp32 [3152])."""
-    w1, b1, w2, b2 = (_f32c(t, n) for t, n in ((w1, 'w1'), (b1, 'b1'), (w2, 'w2'), (b2, 'b2')))
+    w1 = _f32c(w1, 'w1')
+    b1, w2, b2 = (_f32c(t, n, w1, where='decoder_pack') for t, n in ((b1, 'b1'), (w2, 'w2'), (b2, 'b2')))
     n_out = 1 + n_attention if n_attention > 0 else 4
     if tuple(w1.shape) != (64, 32) or tuple(b1.shape) != (64,) or tuple(w2.shape) != (n_out, 64) \
             or tuple(b2.shape) != (n_out,):
@@ -150,7 +249,8 @@ RAY_FEATURE_PITCH = 48
 
 def decoder_pack_viewdir(w1, b1, w2, b2, w3, b3, n_attention, texel_dtype=TEXEL_F32):
     """--use_viewdir decoder (33 outputs) + ViewDirectionMapper.output (w3, b3) -> operand image (fp32 [6016])."""
-    ts = [_f32c(t, n) for t, n in ((w1, 'w1'), (b1, 'b1'), (w2, 'w2'), (b2, 'b2'), (w3, 'w3'), (b3, 'b3'))]
+    w1 = _f32c(w1, 'w1')
+    ts = [w1] + [_f32c(t, n, w1, where='decoder_pack_viewdir') for t, n in ((b1, 'b1'), (w2, 'w2'), (b2, 'b2'), (w3, 'w3'), (b3, 'b3'))]
     n3 = n_attention if n_attention > 0 else 3
     want = [(64, 32), (64,), (33, 64), (33,), (n3, 32), (n3,)]
     if [tuple(t.shape) for t in ts] != want:
@@ -173,10 +273,10 @@ def pad_ray_features(x):
 
 # --------------------------------------------------------------------------- #
 def raygen(height, width, focal, cam2world, bbox=None, center=None, normalize=False):
-    cam2world = _f32c(cam2world, 'tform_cam2world')
+    cam2world = _cameras(cam2world, 'raygen')
     B = cam2world.shape[0]
     dev = cam2world.device
-    focal, bbox, center = _f32c(focal, 'focal_length'), _f32c(bbox, 'bbox'), _f32c(center, 'center')
+    focal, bbox, center = _camera_extras(focal, bbox, center, cam2world, 'raygen')
     ro = torch.empty((B, height, width, 3), dtype=torch.float32, device=dev)
     rd = torch.empty_like(ro)
     with torch.cuda.device(dev):
@@ -190,9 +290,12 @@ def near_far(ray_origins, ray_directions, scene_range, strict=True):
     """Returns near, far (finished planes), hit (bool).  strict: True - raise when no ray hits, as the reference does
     (costs a device->host read of one counter); 'deferred' - no synchronisation, the counter is looked at by the next
     strict call on the device / flush_strict() (as in render_fwd); False - never raises."""
-    ro, rd = _f32c(ray_origins, 'ray_origins'), _f32c(ray_directions, 'ray_directions')
+    ro = _f32c(ray_origins, 'ray_origins')
+    if ro.dim() < 1 or ro.shape[-1] != 3:
+        raise ValueError('near_far: ray_origins must be [...,3], got %s' % (tuple(ro.shape),))
     shape = ro.shape[:-1]
     n = ro.numel() // 3
+    rd = _f32c(ray_directions, 'ray_directions', ro, 3 * n, 'near_far')
     dev = ro.device
     near_raw = torch.empty((n,), dtype=torch.float32, device=dev)
     far_raw = torch.empty_like(near_raw)
@@ -212,10 +315,15 @@ def near_far(ray_origins, ray_directions, scene_range, strict=True):
 
 
 def stratified_points(ray_origins, ray_directions, near, far, num_samples, noise=None, want_points=True):
-    ro, rd = _f32c(ray_origins, 'ray_origins'), _f32c(ray_directions, 'ray_directions')
-    near, far, noise = _f32c(near, 'near'), _f32c(far, 'far'), _f32c(noise, 'noise')
+    where = 'stratified_points'
+    ro = _f32c(ray_origins, 'ray_origins')
+    if ro.dim() < 1 or ro.shape[-1] != 3:
+        raise ValueError('stratified_points: ray_origins must be [...,3], got %s' % (tuple(ro.shape),))
     shape = ro.shape[:-1]
     n = ro.numel() // 3
+    rd = _f32c(ray_directions, 'ray_directions', ro, 3 * n, where)
+    near, far = _f32c(near, 'near', ro, n, where), _f32c(far, 'far', ro, n, where)
+    noise = _f32c(noise, 'noise', ro, n * num_samples, where)
     depth = torch.empty((*shape, num_samples), dtype=torch.float32, device=ro.device)
     points = torch.empty((*shape, num_samples, 3), dtype=torch.float32, device=ro.device) if want_points else None
     with torch.cuda.device(ro.device):
@@ -226,9 +334,11 @@ def stratified_points(ray_origins, ray_directions, near, far, num_samples, noise
 
 
 def points_on_rays(ray_origins, ray_directions, depth):
-    ro, rd, depth = _f32c(ray_origins, 'ray_origins'), _f32c(ray_directions, 'ray_directions'), _f32c(depth, 'depth')
+    depth = _f32c(depth, 'depth')
     S = depth.shape[-1]
     n = depth.numel() // S
+    ro = _f32c(ray_origins, 'ray_origins', depth, 3 * n, 'points_on_rays')
+    rd = _f32c(ray_directions, 'ray_directions', depth, 3 * n, 'points_on_rays')
     points = torch.empty((*depth.shape, 3), dtype=torch.float32, device=depth.device)
     lib = _lib.load()
     with torch.cuda.device(depth.device):
@@ -244,17 +354,20 @@ def field_query(points, texels, decoder_image, scene_range, n_attention, attenti
     """points [B,P,3] -> dict(sigma [B,P], rgb [B,P,3], sdf?, semantics?, outside?).
     mlp_precision: 0 exact fp32 MFMA, 1 split-fp16 operands (the fused renderer's arithmetic; not with ray_features).
     ray_features: padded [B, P/samples_per_ray, 48] (pad_ray_features) with a decoder_pack_viewdir image."""
-    points = _f32c(points, 'points')
+    where = 'field_query'
+    points = _points(points, where)
     B, P = points.shape[0], points.shape[1]
     if ray_features is not None:
-        ray_features = _f32c(ray_features, 'ray_features')
+        ray_features = _f32c(ray_features, 'ray_features', points, where=where)
         if samples_per_ray <= 0 or P % samples_per_ray or \
                 tuple(ray_features.shape) != (B, P // samples_per_ray, RAY_FEATURE_PITCH):
             raise ValueError('ray_features must be [B, P/samples_per_ray, 48]; got %s for P=%d, S=%d' % (
                 tuple(ray_features.shape), P, samples_per_ray))
     dev = points.device
-    tdt = texel_dtype_of(texels)
-    att = _f32c(attention_values, 'attention_values') if n_attention > 0 else None
+    texels, tdt, layout = _texels(texels, B, points, where)
+    decoder_image = _decoder_image(decoder_image, ray_features is not None, points, where)
+    att = _attention(attention_values, n_attention, B, points, where)
+    beta, alpha = _f32c(beta if use_sdf else None, 'beta', points, 1, where), _f32c(alpha if use_sdf else None, 'alpha', points, 1, where)
     out = {'sigma': torch.empty((B, P), dtype=torch.float32, device=dev),
            'rgb': torch.empty((B, P, 3), dtype=torch.float32, device=dev)}
     if want_sdf:
@@ -266,10 +379,9 @@ def field_query(points, texels, decoder_image, scene_range, n_attention, attenti
     with torch.cuda.device(dev):
         _lib.call_struct('nfi_field_query_fwd', 'nfi_field_args', _stream(points), n_scenes=B, points_per_scene=P,
                          points=points, texels=texels, plane_res=texel_res(texels), texel_dtype=tdt,
-                         texel_layout=texel_layout_of(texels),
+                         texel_layout=layout,
                          decoder_image=decoder_image, n_attention=n_attention, attention_values=att,
-                         use_sdf=int(use_sdf), beta=_f32c(beta, 'beta') if use_sdf else None,
-                         alpha=_f32c(alpha, 'alpha') if use_sdf else None, scene_range=float(scene_range),
+                         use_sdf=int(use_sdf), beta=beta, alpha=alpha, scene_range=float(scene_range),
                          sigma=out['sigma'], rgb=out['rgb'], sdf=out.get('sdf'), semantics=out.get('semantics'),
                          outside=out.get('outside'), ray_features=ray_features, samples_per_ray=int(samples_per_ray),
                          mlp_precision=int(mlp_precision))
@@ -279,7 +391,8 @@ def field_query(points, texels, decoder_image, scene_range, n_attention, attenti
 def bbox_overlay(points, sigma, scene_range):
     """sigma + 100 on the wire frame of the scene cube (generator.py:645-659)."""
     import numpy as np
-    points, sigma = _f32c(points, 'points'), _f32c(sigma, 'sigma')
+    sigma = _f32c(sigma, 'sigma')
+    points = _f32c(points, 'points', sigma, where='bbox_overlay')
     n = sigma.numel()
     if points.numel() != 3 * n:
         raise ValueError('bbox_overlay: points %s do not match sigma %s' % (tuple(points.shape), tuple(sigma.shape)))
@@ -293,7 +406,8 @@ def bbox_overlay(points, sigma, scene_range):
 
 # --------------------------------------------------------------------------- #
 def ray_weights(sigma, ray_directions, depth):
-    sigma, rd, depth = _f32c(sigma, 'sigma'), _f32c(ray_directions, 'ray_directions'), _f32c(depth, 'depth')
+    depth = _f32c(depth, 'depth')
+    sigma, rd = _f32c(sigma, 'sigma', depth, where='ray_weights'), _f32c(ray_directions, 'ray_directions', depth, where='ray_weights')
     S = depth.shape[-1]
     n = depth.numel() // S
     _need(sigma, n, (S,), 'sigma', 'ray_weights')
@@ -305,27 +419,33 @@ def ray_weights(sigma, ray_directions, depth):
     return w
 
 
-def _u_and_stride(u, n, k, where='sample_pdf'):
-    """u: [n,k] dense, or a stride-0 broadcast of one row."""
+def _u_and_stride(u, n, k, where='sample_pdf', on=None):
+    """u: [n,k] dense, or a stride-0 broadcast of one row; float32 on the GPU (the call's device is checked by the caller)."""
+    if not u.is_cuda:
+        raise RuntimeError('%s: u must live on the GPU (no CPU path in nerf_from_image_amd)' % where)
+    if u.dtype != torch.float32:
+        raise TypeError('%s: u must be float32, got %s' % (where, u.dtype))
+    if on is not None and u.device != on.device:
+        raise ValueError('%s: u lives on %s, the call runs on %s' % (where, u.device, on.device))
     if u.shape[-1] != k:
         raise ValueError('%s: u must have %d entries per ray, got %s' % (where, k, list(u.shape)))
-    if u.dim() == 2 and u.stride(0) == 0 and u.stride(1) == 1:
+    if u.dim() == 2 and u.stride(0) == 0 and u.stride(1) == 1 and u.data_ptr() % POINTER_ALIGN == 0:
         return u, 0
     if u.numel() != n * k:
         raise ValueError('%s: u must hold one row per ray ([%d,%d]) or broadcast one row with stride 0, got %s' % (
             where, n, k, list(u.shape)))
-    u = u.contiguous()
-    return u, k
+    return _dense(u), k
 
 
 def sample_pdf(bins, weights, u, want_inds=False, want_cdf=False):
-    bins, weights = _f32c(bins, 'bins'), _f32c(weights, 'weights')
+    bins = _f32c(bins, 'bins')
+    weights = _f32c(weights, 'weights', bins, where='sample_pdf')
     if bins.dim() != 2:
         raise ValueError('sample_pdf: bins must be [n,M], got %s' % (list(bins.shape),))
     n, M = bins.shape
     _need(weights, n, (M - 1,), 'weights', 'sample_pdf')
     K = u.shape[-1]
-    u, stride = _u_and_stride(u, n, K)
+    u, stride = _u_and_stride(u, n, K, on=bins)
     dev = bins.device
     samples = torch.empty((n, K), dtype=torch.float32, device=dev)
     inds = torch.empty((n, K), dtype=torch.int64, device=dev) if want_inds else None
@@ -337,14 +457,15 @@ def sample_pdf(bins, weights, u, want_inds=False, want_cdf=False):
 
 
 def resample(sigma, ray_directions, depth, u, want_taps=False):
-    sigma, rd, depth = _f32c(sigma, 'sigma'), _f32c(ray_directions, 'ray_directions'), _f32c(depth, 'depth')
+    depth = _f32c(depth, 'depth')
+    sigma, rd = _f32c(sigma, 'sigma', depth, where='resample'), _f32c(ray_directions, 'ray_directions', depth, where='resample')
     S = depth.shape[-1]
     n = depth.numel() // S
     _need(sigma, n, (S,), 'sigma', 'resample')
     _need_rays(rd, n, 'resample')
     if u.shape[-1] != S:
         raise ValueError('resample: u must have %d entries per ray, got %s' % (S, list(u.shape)))
-    u, stride = _u_and_stride(u.reshape(-1, S) if u.stride(0) != 0 else u, n, S, 'resample')
+    u, stride = _u_and_stride(u.reshape(-1, S) if u.stride(0) != 0 else u, n, S, 'resample', on=depth)
     dev = depth.device
     fine = torch.empty((n, S), dtype=torch.float32, device=dev)
     taps = {}
@@ -364,6 +485,7 @@ def _check_lists(where, rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, ex
     depth list, both lists and the directions hold the same rays, an extra attribute comes for every list."""
     na = depth_a.shape[-1]
     n = depth_a.numel() // na
+    _one_device(where, rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a, extra_b)
     _need_rays(rd, n, where)
     _need(sigma_a, n, (na,), 'sigma_a', where)
     _need(rgb_a, n, (na, 3), 'rgb_a', where)
@@ -419,6 +541,20 @@ def composite(ray_directions, depth_a, sigma_a, rgb_a, depth_b=None, sigma_b=Non
 
 
 # --------------------------------------------------------------------------- #
+def _cameras(cam2world, where):
+    cam2world = _f32c(cam2world, 'tform_cam2world')
+    if cam2world.dim() != 3 or tuple(cam2world.shape[1:]) != (4, 4):
+        raise ValueError('%s: tform_cam2world must be [B,4,4], got %s' % (where, tuple(cam2world.shape)))
+    return cam2world
+
+
+def _camera_extras(focal, bbox, center, cam2world, where):
+    """focal [B], bbox [B,2,2], center [B,2] (each may be None) on the cameras' device."""
+    B = cam2world.shape[0]
+    return (_f32c(focal, 'focal_length', cam2world, B, where), _f32c(bbox, 'bbox', cam2world, 4 * B, where),
+            _f32c(center, 'center', cam2world, 2 * B, where))
+
+
 TAP_NAMES = ('ray_origins', 'ray_directions', 'near_plane', 'far_plane', 'hit', 't_coarse', 'sigma_coarse',
              'rgb_coarse', 't_fine', 'sigma_fine', 'rgb_fine', 't_sorted', 'weights', 'perm')
 
@@ -429,17 +565,19 @@ def render_setup(cam2world, focal, height, width, scene_range, bbox=None, center
     the render kernel only - e.g. with the set-up of the next batch running on another stream meanwhile.  (Not for calls
     that ask for the ray_origins / ray_directions taps or the training stash: those write rays to their own tensors.)"""
     lib = _lib.load()
-    cam2world = _f32c(cam2world, 'tform_cam2world')
+    cam2world = _cameras(cam2world, 'render_setup')
     dev = cam2world.device
     B = cam2world.shape[0]
     n = B * height * width
+    focal, bbox, center = _camera_extras(focal, bbox, center, cam2world, 'render_setup')
     ws_bytes = lib.nfi_render_workspace_bytes(n)
     if workspace is None or workspace.numel() < ws_bytes:
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    _one_device('render_setup', cam2world, workspace)
     with torch.cuda.device(dev):
         _lib.call_struct('nfi_render_setup', 'nfi_render_args', _stream(cam2world), n_scenes=B, height=height, width=width,
-                         scene_range=float(scene_range), cam2world=cam2world, focal=_f32c(focal, 'focal_length'),
-                         bbox=_f32c(bbox, 'bbox'), center=_f32c(center, 'center'), workspace=workspace,
+                         scene_range=float(scene_range), cam2world=cam2world, focal=focal,
+                         bbox=bbox, center=center, workspace=workspace,
                          workspace_bytes=workspace.numel(), row_offset=0 if row_window is None else int(row_window[0]),
                          full_height=0 if row_window is None else int(row_window[1]))
     return workspace
@@ -483,7 +621,8 @@ def render_fwd(cam2world, focal, height, width, num_samples, texels, decoder_ima
     64 < num_samples <= 128 kernel parks them as unorm16 (|error| <= 2^-17 = 7.7e-6 per sample, values below that become
     0) and scales the composited map to sum to the mask, so its map is within 1e-5 of the reference's instead of 1e-6
     (tests/test_hip_parity.py, test_wide_kernel_semantics_table_precision; tests/test_kernel_matrix.py for A = 14)."""
-    cam2world = _f32c(cam2world, 'tform_cam2world')
+    where = 'render_fwd'
+    cam2world = _cameras(cam2world, where)
     B = cam2world.shape[0]
     dev = cam2world.device
     n = B * height * width
@@ -498,7 +637,12 @@ def render_fwd(cam2world, focal, height, width, num_samples, texels, decoder_ima
         raise ValueError('render_fwd: attention_values of %d scene(s) x views_per_scene %d do not cover %d cameras' % (
             0 if attention_values is None else attention_values.shape[0], V, B))
     lib = _lib.load()
-    tdt = texel_dtype_of(texels)
+    texels, tdt, layout = _texels(texels, B // V, cam2world, where)
+    decoder_image = _decoder_image(decoder_image, ray_features is not None, cam2world, where)
+    att = _attention(attention_values, n_attention, B // V, cam2world, where)
+    focal, bbox, center = _camera_extras(focal, bbox, center, cam2world, where)
+    beta, alpha = _f32c(beta if use_sdf else None, 'beta', cam2world, 1, where), _f32c(alpha if use_sdf else None, 'alpha', cam2world, 1, where)
+    noise_coarse = _f32c(noise_coarse, 'noise_coarse', cam2world, n * S, where)
     out = {'rgb': torch.empty((B, height, width, 3), dtype=torch.float32, device=dev),
            'depth': torch.empty((B, height, width), dtype=torch.float32, device=dev),
            'mask': torch.empty((B, height, width), dtype=torch.float32, device=dev)}
@@ -565,23 +709,22 @@ def render_fwd(cam2world, focal, height, width, num_samples, texels, decoder_ima
     if fine_sampling:
         if noise_fine is None:
             noise_fine = torch.linspace(0.0, 1.0, steps=S, dtype=torch.float32, device=dev).expand(n, S)
-        u, ustride = _u_and_stride(noise_fine if noise_fine.dim() == 2 else noise_fine.reshape(-1, S), n, S, 'render_fwd')
+        u, ustride = _u_and_stride(noise_fine if noise_fine.dim() == 2 else noise_fine.reshape(-1, S), n, S, where, on=cam2world)
     else:
         u, ustride = None, 0
     if ray_features is not None:
-        ray_features = _f32c(ray_features, 'ray_features')
+        ray_features = _f32c(ray_features, 'ray_features', cam2world, where=where)
         if ray_features.numel() != n * RAY_FEATURE_PITCH:
             raise ValueError('ray_features must be [B,H,W,48], got %s' % (tuple(ray_features.shape),))
+    _one_device(where, cam2world, workspace, profile_cycles, clock_probe)
     with torch.cuda.device(dev):
         _lib.call_struct(
             'nfi_render_fwd', 'nfi_render_args', _stream(cam2world), n_scenes=B, height=height, width=width,
             n_samples=S, fine_sampling=int(fine_sampling), white_background=int(white_background),
-            scene_range=float(scene_range), views_per_scene=V, cam2world=cam2world, focal=_f32c(focal, 'focal_length'),
-            bbox=_f32c(bbox, 'bbox'), center=_f32c(center, 'center'), texels=texels, plane_res=texel_res(texels),
-            texel_layout=texel_layout_of(texels), texel_dtype=tdt, decoder_image=decoder_image, n_attention=n_attention,
-            attention_values=_f32c(attention_values, 'attention_values') if n_attention > 0 else None,
-            use_sdf=int(use_sdf), beta=_f32c(beta, 'beta') if use_sdf else None,
-            alpha=_f32c(alpha, 'alpha') if use_sdf else None, noise_coarse=_f32c(noise_coarse, 'noise_coarse'),
+            scene_range=float(scene_range), views_per_scene=V, cam2world=cam2world, focal=focal,
+            bbox=bbox, center=center, texels=texels, plane_res=texel_res(texels),
+            texel_layout=layout, texel_dtype=tdt, decoder_image=decoder_image, n_attention=n_attention,
+            attention_values=att, use_sdf=int(use_sdf), beta=beta, alpha=alpha, noise_coarse=noise_coarse,
             noise_fine=u, noise_fine_row_stride=ustride, rgb=out['rgb'], depth=out['depth'], mask=out['mask'],
             workspace=workspace, workspace_bytes=workspace.numel(), skip_missed_rays=int(skip_missed_rays),
             event_start=None if events is None else events[0], event_stop=None if events is None else events[1],
@@ -654,19 +797,27 @@ def flush_strict(device=None):
 # --------------------------------------------------------------------------- #
 def sdf_gradient_fwd(points, texels, w1, b1, w2, b2, scene_range):
     """points [B,P,3] (inside the cube) -> (sdf [B,P], d sdf / d points [B,P,3])."""
-    points = _f32c(points, 'points')
-    if texels.dtype != torch.float32:
-        raise TypeError('sdf_gradient: fp32 texels only')
+    where = 'sdf_gradient_fwd'
+    points = _points(points, where)
     B, P = points.shape[0], points.shape[1]
+    texels, _, layout = _texels(texels, B, points, where, fp32_only=True)
+    w1, b1, w2, b2 = _distance_head(w1, b1, w2, b2, points, where)
     sdf = torch.empty((B, P), dtype=torch.float32, device=points.device)
     grad = torch.empty((B, P, 3), dtype=torch.float32, device=points.device)
     with torch.cuda.device(points.device):
         _lib.call_struct('nfi_sdf_gradient_fwd', 'nfi_sdf_gradient_args', _stream(points), n_scenes=B, points_per_scene=P,
-                         points=points, texels=texels, plane_res=texel_res(texels), texel_layout=texel_layout_of(texels),
-                         scene_range=float(scene_range),
-                         w1=_f32c(w1, 'w1'), b1=_f32c(b1, 'b1'), w2=_f32c(w2, 'w2'), b2=_f32c(b2, 'b2'), sdf=sdf,
-                         gradient=grad)
+                         points=points, texels=texels, plane_res=texel_res(texels), texel_layout=layout,
+                         scene_range=float(scene_range), w1=w1, b1=b1, w2=w2, b2=b2, sdf=sdf, gradient=grad)
     return sdf, grad
+
+
+def _distance_head(w1, b1, w2, b2, on, where):
+    """Raw decoder parameters of the regulariser: w1 [64,32], b1 [64], w2 [n_out,64], b2 [n_out] (row 0 is the distance)."""
+    w1, b1 = _f32c(w1, 'w1', on, 64 * 32, where), _f32c(b1, 'b1', on, 64, where)
+    w2, b2 = _f32c(w2, 'w2', on, where=where), _f32c(b2, 'b2', on, where=where)
+    if w2.dim() != 2 or w2.shape[0] < 1 or w2.shape[1] != 64 or b2.numel() != w2.shape[0]:
+        raise ValueError('%s: w2 must be [n_out,64] and b2 [n_out], got %s and %s' % (where, tuple(w2.shape), tuple(b2.shape)))
+    return w1, b1, w2, b2
 
 
 def sdf_gradient_bwd(points, texels, w1, b1, w2, b2, scene_range, g_sdf, g_gradient, ordered=False):
@@ -674,17 +825,21 @@ def sdf_gradient_bwd(points, texels, w1, b1, w2, b2, scene_range, g_sdf, g_gradi
     [n_out,64] with row 0 filled, g_b2 [n_out] with entry 0 filled).  ordered=True: nfi_sdf_gradient_bwd_ordered - the same
     contributions summed in a fixed order, every output bit-identical from launch to launch (a workspace is allocated
     per call)."""
-    points = _f32c(points, 'points')
+    where = 'sdf_gradient_bwd'
+    points = _points(points, where)
     B, P = points.shape[0], points.shape[1]
     dev = points.device
-    w2, b2 = _f32c(w2, 'w2'), _f32c(b2, 'b2')
-    out = {'g_texels': torch.zeros_like(texels), 'g_w1': torch.zeros((64, 32), dtype=torch.float32, device=dev),
+    texels, _, layout = _texels(texels, B, points, where, fp32_only=True)
+    w1, b1, w2, b2 = _distance_head(w1, b1, w2, b2, points, where)
+    # the gradient image is dense in the texels' layout whatever strides the caller's texels came with
+    out = {'g_texels': torch.zeros(texels.shape, dtype=torch.float32, device=dev),
+           'g_w1': torch.zeros((64, 32), dtype=torch.float32, device=dev),
            'g_b1': torch.zeros((64,), dtype=torch.float32, device=dev), 'g_w2': torch.zeros_like(w2),
            'g_b2': torch.zeros_like(b2)}
     args = dict(n_scenes=B, points_per_scene=P, points=points, texels=texels, plane_res=texel_res(texels),
-                texel_layout=texel_layout_of(texels), scene_range=float(scene_range),
-                w1=_f32c(w1, 'w1'), b1=_f32c(b1, 'b1'), w2=w2, b2=b2, g_sdf=_f32c(g_sdf, 'g_sdf'),
-                g_gradient=_f32c(g_gradient, 'g_gradient'), **out)
+                texel_layout=layout, scene_range=float(scene_range),
+                w1=w1, b1=b1, w2=w2, b2=b2, g_sdf=_f32c(g_sdf, 'g_sdf', points, B * P, where),
+                g_gradient=_f32c(g_gradient, 'g_gradient', points, 3 * B * P, where), **out)
     with torch.cuda.device(dev):
         if ordered:
             _call_ordered('nfi_sdf_gradient_bwd_ordered', 'nfi_sdf_gradient_args', points, 'sdf_gradient_bwd(ordered=True): shape '
@@ -713,6 +868,14 @@ def composite_bwd_stash(ray_directions, stash_t, stash_sigma, stash_rgb, g_rgb_m
             out['g_ray_directions'] = g['g_ray_directions']
         return out
     S = S2 // 2
+    where = 'composite_bwd_stash'
+    if S2 % 2:
+        raise ValueError('%s: stash rows hold coarse | fine samples, an even count; got %d' % (where, S2))
+    _one_device(where, rd, t, sg, col)
+    _need_rays(rd, n, where)
+    _need(sg, n, (S2,), 'stash_sigma', where)
+    _need(col, n, (S2, 3), 'stash_rgb', where)
+    g_rgb_map, g_mask = _f32c(g_rgb_map, 'g_rgb_map', rd, 3 * n, where), _f32c(g_mask, 'g_mask', rd, n, where)
     out = dict(g_sigma=torch.empty_like(sg), g_rgb=torch.empty_like(col))
     if want_rd:
         out['g_ray_directions'] = torch.empty_like(rd)
@@ -743,6 +906,8 @@ def composite_bwd(ray_directions, depth_a, sigma_a, rgb_a, g_rgb_map, g_mask=Non
         n_extra = extra_a.shape[-1]
     n = _check_lists('composite_bwd', rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a if n_extra else None,
                      extra_b if n_extra and nb else None)
+    g_rgb_map, g_mask = _f32c(g_rgb_map, 'g_rgb_map', rd, where='composite_bwd'), _f32c(g_mask, 'g_mask', rd, where='composite_bwd')
+    g_extra_map = _f32c(g_extra_map, 'g_extra_map', rd, where='composite_bwd') if n_extra else None
     _need(g_rgb_map, n, (3,), 'g_rgb_map', 'composite_bwd')
     if g_mask is not None:
         _need(g_mask, n, (), 'g_mask', 'composite_bwd')
@@ -768,9 +933,10 @@ def composite_bwd(ray_directions, depth_a, sigma_a, rgb_a, g_rgb_map, g_mask=Non
 
 
 def points_bwd(g_points, depth, want_ro=True, want_rd=True):
-    g_points, depth = _f32c(g_points, 'g_points'), _f32c(depth, 'depth')
+    depth = _f32c(depth, 'depth')
     S = depth.shape[-1]
     n = depth.numel() // S
+    g_points = _f32c(g_points, 'g_points', depth, 3 * n * S, 'points_bwd')
     shape = depth.shape[:-1]
     g_ro = torch.empty((*shape, 3), dtype=torch.float32, device=depth.device) if want_ro else None
     g_rd = torch.empty((*shape, 3), dtype=torch.float32, device=depth.device) if want_rd else None
@@ -783,9 +949,11 @@ def points_bwd(g_points, depth, want_ro=True, want_rd=True):
 
 def raygen_bwd(height, width, focal, cam2world, bbox, center, normalize, g_ro, g_rd, ordered=False):
     """g_cam2world [B,4,4], g_focal [B] or None.  ordered: nfi_raygen_bwd_ordered - the same bits on every launch."""
-    cam2world = _f32c(cam2world, 'tform_cam2world')
+    cam2world = _cameras(cam2world, 'raygen_bwd')
     B = cam2world.shape[0]
-    focal, bbox, center = _f32c(focal, 'focal_length'), _f32c(bbox, 'bbox'), _f32c(center, 'center')
+    focal, bbox, center = _camera_extras(focal, bbox, center, cam2world, 'raygen_bwd')
+    n3 = 3 * B * height * width
+    g_ro, g_rd = _f32c(g_ro, 'g_ro', cam2world, n3, 'raygen_bwd'), _f32c(g_rd, 'g_rd', cam2world, n3, 'raygen_bwd')
     g_cam = torch.empty((B, 4, 4), dtype=torch.float32, device=cam2world.device)
     g_focal = torch.empty((B,), dtype=torch.float32, device=cam2world.device) if focal is not None else None
     lib = _lib.load()
@@ -794,7 +962,7 @@ def raygen_bwd(height, width, focal, cam2world, bbox, center, normalize, g_ro, g
     import ctypes
     with torch.cuda.device(cam2world.device):
         name = 'nfi_raygen_bwd_ordered' if ordered else 'nfi_raygen_bwd'
-        _lib.check(getattr(lib, name)(ctypes.byref(a), _lib.ptr(_f32c(g_ro, 'g_ro')), _lib.ptr(_f32c(g_rd, 'g_rd')),
+        _lib.check(getattr(lib, name)(ctypes.byref(a), _lib.ptr(g_ro), _lib.ptr(g_rd),
                                       _lib.ptr(g_cam), _lib.ptr(g_focal), _stream(cam2world)), name)
     return g_cam, g_focal
 
@@ -802,10 +970,10 @@ def raygen_bwd(height, width, focal, cam2world, bbox, center, normalize, g_ro, g
 # --------------------------------------------------------------------------- #
 # neighbours of the renderer in the inversion loop
 # --------------------------------------------------------------------------- #
-def _warp_args(img_shape, rot, scale, translation, white_background):
-    n, c, h, w = img_shape
-    rot, translation = _f32c(rot, 'rot'), _f32c(translation, 'translation')
-    scale = _f32c(scale, 'scale')
+def _warp_args(img, rot, scale, translation, white_background):
+    n, c, h, w = img.shape
+    rot, translation = _f32c(rot, 'rot', img, where='affine_warp'), _f32c(translation, 'translation', img, where='affine_warp')
+    scale = _f32c(scale, 'scale', img, where='affine_warp')
     if rot.numel() != n or translation.numel() != 2 * n or (scale is not None and scale.numel() != n):
         raise ValueError('affine_warp: rot [N], scale [N] or None, translation [N,2] expected for N=%d images' % n)
     return dict(n_images=n, channels=c, height=h, width=w, rot=rot, scale=scale, translation=translation,
@@ -820,7 +988,7 @@ def affine_warp(img, rot, scale, translation, white_background=False):
     out = torch.empty_like(img)
     with torch.cuda.device(img.device):
         _lib.call_struct('nfi_affine_warp_fwd', 'nfi_warp_args', _stream(img), image=img, warped=out,
-                         **_warp_args(img.shape, rot, scale, translation, white_background))
+                         **_warp_args(img, rot, scale, translation, white_background))
     return out
 
 
@@ -829,10 +997,12 @@ def affine_warp_bwd(g_out, rot, scale, translation, white_background=False, orde
     nfi_affine_warp_bwd_ordered - a gather per source pixel instead of a scatter of atomics, bit-identical from launch to
     launch."""
     g_out = _f32c(g_out, 'g_out')
+    if g_out.dim() != 4:
+        raise ValueError('affine_warp_bwd: g_out must be [N,C,H,W]')
     g_img = torch.empty_like(g_out)
     with torch.cuda.device(g_out.device):
         _lib.call_struct('nfi_affine_warp_bwd_ordered' if ordered else 'nfi_affine_warp_bwd', 'nfi_warp_args', _stream(g_out), g_warped=g_out, g_image=g_img,
-                         **_warp_args(g_out.shape, rot, scale, translation, white_background))
+                         **_warp_args(g_out, rot, scale, translation, white_background))
     return g_img
 
 
@@ -859,13 +1029,14 @@ def image_metrics(pred=None, target=None, mask_pred=None, mask_real=None, check_
     kw = dict(n_images=b)
     psnr = iou = flag = None
     if pred is not None:
-        pred, target = _f32c(pred, 'pred'), _f32c(target, 'target')
+        pred, target = _f32c(pred, 'pred', first, where='image_metrics'), _f32c(target, 'target', first, where='image_metrics')
         if pred.shape != target.shape:
             raise ValueError('image_metrics: pred %s vs target %s' % (tuple(pred.shape), tuple(target.shape)))
         psnr = torch.empty((b,), dtype=torch.float32, device=dev)
         kw.update(pred=pred, target=target, elements_per_image=pred.numel() // b, psnr=psnr)
     if mask_pred is not None:
-        mask_pred, mask_real = _f32c(mask_pred, 'mask_pred'), _f32c(mask_real, 'mask_real')
+        mask_pred, mask_real = (_f32c(mask_pred, 'mask_pred', first, where='image_metrics'),
+                                _f32c(mask_real, 'mask_real', first, where='image_metrics'))
         if mask_pred.shape != mask_real.shape or mask_pred.shape[0] != b:
             raise ValueError('image_metrics: mask shapes %s vs %s' % (tuple(mask_pred.shape), tuple(mask_real.shape)))
         iou = torch.empty((b,), dtype=torch.float32, device=dev)
@@ -1138,7 +1309,7 @@ def synth_tail_bwd_launch(kw, g_out, out, need_y, need_dcoefs, need_bias, need_n
 # --------------------------------------------------------------------------- #
 def _pose_rows(t, tail, name, b=None):
     """t as dense float32 [B, *tail] on the GPU (B = its own, or the given one)."""
-    t = _f32c(t, name)
+    t = _f32c(t, name, align=4)              # (nfi_pose.inc: one thread per image, float loads and stores only)
     if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or t.shape[0] < 1 or (b is not None and t.shape[0] != b):
         raise ValueError('%s must be [%s], got %s' % (name, ', '.join(['B' if b is None else str(b)] + [str(v) for v in tail]),
                                                       tuple(t.shape)))
@@ -1244,8 +1415,12 @@ def torgb_texels(x, styles, weight, bias, previous_image=None):
     """Tail of the last synthesis block (stylegan.py:383-435) written as texels: x [B,Cin,R,R], styles [B,Cin],
     weight [96,Cin], bias [96], previous_image [B,96,R/2,R/2] or None -> a [B,96,R,R] tensor in channels-last memory
     format (its storage IS the interleaved texel image [B,R,R,3,32])."""
-    x, styles, weight, bias = _f32c(x, 'x'), _f32c(styles, 'styles'), _f32c(weight, 'weight'), _f32c(bias, 'bias')
-    prev = _f32c(previous_image, 'previous_image')
+    where = 'torgb_texels'
+    x = _f32c(x, 'x')
+    styles, weight, bias = _f32c(styles, 'styles', x, where=where), _f32c(weight, 'weight', x, where=where), _f32c(bias, 'bias', x, where=where)
+    prev = _f32c(previous_image, 'previous_image', x, where=where)
+    if x.dim() != 4:
+        raise ValueError('torgb_texels: x must be [B,Cin,R,R], got %s' % (tuple(x.shape),))
     B, Cin, R, R2 = x.shape
     if R != R2 or tuple(styles.shape) != (B, Cin) or tuple(weight.shape) != (96, Cin) or tuple(bias.shape) != (96,) or \
             (prev is not None and tuple(prev.shape) != (B, 96, R // 2, R // 2)):
@@ -1263,12 +1438,19 @@ def torgb_texels_bwd(g_out, x, styles, weight, previous_image=None, want_weight=
     """Backward of torgb_texels.  g_out: [B,96,R,R] (any strides; brought to channels-last).  Returns dict(g_x, g_styles,
     g_weight?, g_bias?, g_previous_image?).  ordered=True: nfi_torgb_texels_bwd_ordered - the style, weight and bias sums
     in a fixed order, every output bit-identical from launch to launch (a workspace is allocated per call)."""
-    x, styles, weight = _f32c(x, 'x'), _f32c(styles, 'styles'), _f32c(weight, 'weight')
-    prev = _f32c(previous_image, 'previous_image')
+    where = 'torgb_texels_bwd'
+    x = _f32c(x, 'x')
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise ValueError('torgb_texels_bwd: x must be [B,Cin,R,R], got %s' % (tuple(x.shape),))
     B, Cin, R, _ = x.shape
+    styles, weight = _f32c(styles, 'styles', x, B * Cin, where), _f32c(weight, 'weight', x, 96 * Cin, where)
+    prev = _f32c(previous_image, 'previous_image', x, B * 96 * (R // 2) * (R // 2), where)
     if not g_out.is_cuda or g_out.dtype != torch.float32:
         raise TypeError('torgb_texels_bwd: g_out must be a float32 GPU tensor')
-    g = g_out.contiguous(memory_format=torch.channels_last)
+    if tuple(g_out.shape) != (B, 96, R, R) or g_out.device != x.device:
+        raise ValueError('torgb_texels_bwd: g_out must be [%d,96,%d,%d] on %s, got %s on %s' % (
+            B, R, R, x.device, tuple(g_out.shape), g_out.device))
+    g = _dense_channels_last(g_out)
     dev = x.device
     out = {'g_x': torch.empty_like(x), 'g_styles': torch.empty((B, Cin), dtype=torch.float32, device=dev)}
     if want_weight:

@@ -11,6 +11,8 @@ import math
 import numpy as np
 import torch
 
+from contract_util import strided  # noqa: F401  (the one copy of the view helpers; pu.strided as before)
+
 EPS32 = 2.0 ** -23
 
 
@@ -160,18 +162,6 @@ def case(b, perspective, unit=True, seed=0, turns=False):
     s = 0.5 + 1.5 * torch.rand(b, generator=g)
     z0 = torch.rand(b, generator=g) * 8 - 4 if perspective else None
     return dict(q=q.float(), t2=t2, s=s, z0=z0)
-
-
-def strided(t):
-    """The same values behind a non-contiguous view (every other element of the last axis of a wider buffer; a 1-D tensor:
-    every other element)."""
-    if t is None:
-        return None
-    wide = torch.zeros(t.shape[:-1] + (2 * t.shape[-1],), dtype=t.dtype, device=t.device)
-    view = wide[..., ::2]
-    view.copy_(t)
-    assert not view.is_contiguous() or t.numel() <= 1
-    return view
 
 
 def rotations(n, g):
