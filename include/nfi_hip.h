@@ -885,6 +885,72 @@ size_t nfi_synth_tail_bwd_workspace_bytes(const nfi_synth_tail_args* a);
 int nfi_synth_tail_fwd(const nfi_synth_tail_args* a, nfi_stream_t stream);
 int nfi_synth_tail_bwd(const nfi_synth_tail_args* a, nfi_stream_t stream);
 
+/* The head of a synthesis layer: everything SynthesisLayer.forward (models/stylegan.py:325-356) and OutputLayer.forward
+ * (372-380) do BEFORE their convolution - the affine, EqualizedLinear.forward (stylegan.py:173-177), the demodulation
+ * coefficients of conv_modulated2d (127-130) and the modulation of the input (132) - and what autograd records for those
+ * lines.  All tensors float32; B = batch, D = latent_dim, I = in_channels, O = out_channels, K = taps (kh * kw).
+ *   styles[b,i] = (sum_d latent[b,d] affine_weight[i,d] weight_gain + affine_bias[i] bias_gain) style_gain          [B,I]
+ *   dcoefs[b,o] = rsqrt(sum_i styles[b,i]^2 Q[o,i] + 1e-8),  Q[o,i] = sum_k weight[o,i,k]^2      [B,O], with demodulate
+ * style_gain: 1 for a synthesis layer, OutputLayer.weight_gain for toRGB (373).  The reference's [B,O,I,kh,kw] product
+ * weight[None] * styles[:, None, :, None, None] (127-128) is never formed: Q is computed from weight inside the kernel, and
+ * weight is read once per call for up to 8 images (once per 8 beyond that).  Every sum is added in float64 in a fixed order and
+ * rounded to float32 once: no atomics, the same bits on every launch.  dcoefs and the gradients use the rounded styles / dcoefs.
+ *   latent: rows of D floats, latent_stride floats apart (>= D: a layer's ws.unbind(1)[k] is read in place); affine_weight
+ *   dense [I,D]; affine_bias [I] or NULL; weight dense [O,I,K] (may be NULL without demodulate; O and K are then only checked).
+ *   fwd (stylegan.py:173-177, 127-130, 373): writes styles and, with demodulate, dcoefs.  TWO launches, one without demodulate.
+ *   bwd: upstream g_styles [B,I] (the modulation's, and toRGB's) and g_dcoefs [B,O] (the tail's), either may be NULL, not both;
+ *     styles and dcoefs are the forward's results.  With c[b,o] = g_dcoefs d^3 (0 without g_dcoefs):
+ *       g_s[b,i]             = (g_styles[b,i] - styles[b,i] sum_o c[b,o] Q[o,i]) style_gain        (internal, float64)
+ *       g_latent[b,d]        = weight_gain sum_i g_s[b,i] affine_weight[i,d]                        dense [B,D]
+ *       g_affine_weight[i,d] = weight_gain sum_b g_s[b,i] latent[b,d]                               [I,D]
+ *       g_affine_bias[i]     = bias_gain sum_b g_s[b,i]                                             [I]
+ *       g_weight[o,i,k]      = -weight[o,i,k] sum_b c[b,o] styles[b,i]^2                            [O,I,K]
+ *     g_weight is the demodulation's share only (the convolution's stays with the caller).  Each may be NULL (skipped), not
+ *     all four.  At most FOUR launches: one pass over weight (only with g_dcoefs; it writes g_weight too, so weight is read
+ *     once with or without it), g_s, g_latent, g_affine_weight with g_affine_bias.  No second order.
+ *   workspace (bwd): device memory, 8-byte aligned, need not be zeroed; nfi_synth_head_bwd_workspace_bytes reads batch,
+ *   latent_dim, latent_stride, in_channels, out_channels, taps and demodulate and returns 0 for a shape the calls refuse.
+ * Refused before any launch (-1, nfi_last_error() names the argument): a null argument struct / latent / affine_weight /
+ * styles; batch, latent_dim, in_channels, out_channels or taps under 1; latent_stride under latent_dim; demodulate without
+ * weight or without dcoefs; a NaN weight_gain, bias_gain or style_gain; (bwd) no upstream gradient, no gradient pointer,
+ * g_dcoefs without dcoefs (or without demodulate / weight), g_weight without g_dcoefs, a missing, misaligned or too small
+ * workspace; an element count the index arithmetic cannot hold: batch * latent_stride, batch * in_channels, batch *
+ * out_channels, in_channels * latent_dim and out_channels * in_channels * taps must be below 2^31, batch at most 8 * 65535 and
+ * out_channels at most 8 * 65535. */
+typedef struct nfi_synth_head_args {
+  int batch, latent_dim, in_channels, out_channels, taps;      /* B, D, I, O, K */
+  int latent_stride;                             /* floats between the rows of latent */
+  int demodulate;
+  float weight_gain, bias_gain, style_gain;
+  const float* latent; const float* affine_weight; const float* affine_bias; const float* weight;
+  float* styles; float* dcoefs;                  /* written by fwd, read by bwd */
+  const float* g_styles; const float* g_dcoefs;  /* backward: upstream */
+  float* g_latent; float* g_affine_weight; float* g_affine_bias; float* g_weight;    /* backward */
+  void* workspace; size_t workspace_bytes;       /* backward */
+} nfi_synth_head_args;
+size_t nfi_synth_head_bwd_workspace_bytes(const nfi_synth_head_args* a);
+int nfi_synth_head_fwd(const nfi_synth_head_args* a, nfi_stream_t stream);
+int nfi_synth_head_bwd(const nfi_synth_head_args* a, nfi_stream_t stream);
+
+/* The modulation of a layer's input, x * styles.reshape(bs, -1, 1, 1) (stylegan.py:132): x dense [B,C,n] (n = plane = H * W),
+ * styles [B,C].
+ *   fwd: out[b,c,:] = x[b,c,:] styles[b,c].  ONE launch, flat over the tensor.
+ *   bwd: g_x = g_out styles;  g_styles[b,c] = sum_n g_out x, added in float64 in a fixed order (no atomics: the same bits on
+ *     every launch).  Either may be NULL (skipped), not both; x is read only for g_styles.  ONE launch: g_x alone is the flat
+ *     kernel; with g_styles 16 lanes own a plane up to 256 elements, a wave up to 2048, a block of 1024 threads above.
+ *   16-byte accesses where plane % 4 == 0 and x / out / g_out / g_x are 16-byte aligned; a scalar path otherwise.
+ * Refused before any launch (-1, nfi_last_error() names the argument): a null argument struct / styles; null x or out (fwd);
+ * null g_out, g_x and g_styles both null, g_styles without x (bwd); batch, channels or plane under 1; an element count the
+ * index arithmetic cannot hold: batch * channels * plane must be below 2^31. */
+typedef struct nfi_synth_modulate_args {
+  int batch, channels, plane;                    /* B, C, n */
+  const float* x; const float* styles;
+  float* out;                                    /* forward */
+  const float* g_out; float* g_x; float* g_styles;    /* backward */
+} nfi_synth_modulate_args;
+int nfi_synth_modulate_fwd(const nfi_synth_modulate_args* a, nfi_stream_t stream);
+int nfi_synth_modulate_bwd(const nfi_synth_modulate_args* a, nfi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * View-direction mapper, the per-ray trunk.  Replaces ViewDirectionMapper.__init__'s layers as forward runs them
  * (models/generator.py:194-241: fc0 .. fc6, norm1 .. norm4, two residual joins scaled by sqrt(2)/2, LeakyReLU(0.2);

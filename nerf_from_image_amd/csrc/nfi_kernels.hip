@@ -18,7 +18,7 @@ using namespace nfi;
 // error plumbing, argument checks and the LDS staging helpers shared with the other units: nfi_host.hpp
 thread_local char nfi_err_buf[256] = "";
 extern "C" const char* nfi_last_error(void) { return nfi_err_buf; }
-extern "C" int nfi_version(void) { return 106; }
+extern "C" int nfi_version(void) { return 107; }
 
 #include "nfi_layout.inc"           // planes <-> texels, the decoder image packers
 #include "nfi_rays.inc"             // ray generation, near / far planes, stratified query points

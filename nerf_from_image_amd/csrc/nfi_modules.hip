@@ -1,5 +1,5 @@
 // The kernel families around the renderer - regulariser, neighbour / metric kernels, hand-off, PnP, pose algebra, blur,
-// LPIPS head, view-direction mapper, synthesis-layer tail - as their own translation unit.
+// LPIPS head, view-direction mapper, synthesis-layer tail and head - as their own translation unit.
 //
 // None of them uses anything of nfi_kernels.hip, and nothing there uses them: with a code object of their own, adding or
 // editing a family leaves the benchmarked render, stage and field kernels where they are in theirs.  Built with the
@@ -21,3 +21,4 @@ using namespace nfi;
 #include "nfi_lpips.inc"
 #include "nfi_viewdir_mapper.inc"
 #include "nfi_synth_tail.inc"
+#include "nfi_synth_head.inc"

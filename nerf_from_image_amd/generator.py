@@ -548,7 +548,7 @@ def bake(model, model_input, model_inputs={}):
 
 
 def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_handoff=False, hip_viewdir_mapper=False,
-           deterministic_backward=False, fused_synthesis_tail=False):
+           deterministic_backward=False, fused_synthesis_head=False, fused_synthesis_tail=False):
     """Gives a reference-style Generator the HIP sampler.  Returns the same module.
 
     deterministic_backward: the sampler closure's backward (the staged path) runs the field backward in its ordered mode
@@ -576,6 +576,14 @@ def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_hando
     deterministic_backward.  First-order only: a forward that asks for path_length runs the layers' own forwards.  Layers
     fused by an earlier call stay fused (synthesis.unfuse_layers undoes it).
 
+    fused_synthesis_head (off by default; implies fused_synthesis_tail): everything each synthesis layer and each output
+    (toRGB) layer does before its convolution - the affine, the demodulation coefficients, x * styles; stylegan.py:173-177,
+    127-130, 132, 373 - runs as two HIP nodes per layer (synthesis.layer_styles and synthesis.modulate;
+    synthesis.fuse_layers(net, head=True)): the [B,O,I,3,3] product of the reference is never formed, and every sum runs in a
+    fixed order.  With fused_handoff the last block takes its toRGB styles from the same node.  First-order only, like the
+    tail: a forward that asks for path_length runs the layers' and the output layers' own forwards.  Stays on through a
+    later attach() without the option.
+
     hip_regularisers: also serve sdf_eikonal / sdf_distance / total_variation / entropy losses of a module that has
     its own forward from the HIP kernels (bare containers always do).
 
@@ -600,9 +608,9 @@ def attach(model, texel_dtype=ops.TEXEL_F32, hip_regularisers=False, fused_hando
     from . import handoff
     if fused_handoff or handoff.fused_block(model.synthesis_network) is not None:    # fused earlier: stays fused, follows the switch
         handoff.fuse_last_block(model.synthesis_network, deterministic_backward=deterministic_backward)
-    if fused_synthesis_tail:
+    if fused_synthesis_tail or fused_synthesis_head:
         from . import synthesis
-        synthesis.fuse_layers(model.synthesis_network)
+        synthesis.fuse_layers(model.synthesis_network, head=bool(fused_synthesis_head) or synthesis.head_fused(model.synthesis_network))
     if type(model).forward is not torch.nn.Module.forward and not hasattr(model, '_nfi_original_forward'):
         model._nfi_original_forward = model.forward          # bound method of the reference class
         model.forward = types.MethodType(wrapped_forward, model)

@@ -23,7 +23,7 @@ import types
 
 import torch
 
-from . import ops
+from . import ops, synthesis
 from .autograd import differentiable
 
 
@@ -60,7 +60,10 @@ def fused_block_forward(self, x, img, ws, **layer_kwargs):
         x = self.conv0(x, next(w_iter), **layer_kwargs)
     x = self.conv1(x, next(w_iter), **layer_kwargs)
     torgb = self.torgb
-    styles = torgb.affine(next(w_iter)) * torgb.weight_gain               # OutputLayer.forward, stylegan.py:365
+    if getattr(torgb, '_nfi_fused_head', False):                          # synthesis.fuse_layers(net, head=True): the HIP head node
+        styles, _ = synthesis.layer_styles(next(w_iter), torgb.affine, torgb.weight, demodulate=False, style_gain=torgb.weight_gain)
+    else:
+        styles = torgb.affine(next(w_iter)) * torgb.weight_gain           # OutputLayer.forward, stylegan.py:365
     ordered = {'deterministic_backward': True} if getattr(self, 'nfi_deterministic_backward', False) else {}
     img = torgb_upsample_add(x, styles, torgb.weight, torgb.bias, img, **ordered)
     return x, img

@@ -1305,6 +1305,166 @@ def synth_tail_bwd_launch(kw, g_out, out, need_y, need_dcoefs, need_bias, need_n
 
 
 # --------------------------------------------------------------------------- #
+# head of a synthesis layer (models/stylegan.py:173-177, 127-130, 132, 373; csrc/nfi_synth_head.inc).  The kernels read
+# single floats through every pointer but the modulation's planes, and those they test themselves (16-byte accesses where
+# the pointers allow it): nothing here is copied for its alignment.  The functions that hand pointers to the library are
+# private (_synth_head_launch ...): they take what synth_head_args / synth_modulate_args have checked.
+# --------------------------------------------------------------------------- #
+def _latent_rows(latent, where):
+    """latent as float32 [B,D] on the GPU whose rows the kernel can read in place: unit stride along d and rows at least D
+    apart (a layer's ws.unbind(1)[k]); any other view is copied."""
+    if not latent.is_cuda:
+        raise RuntimeError('%s: latent must live on the GPU (no CPU path in nerf_from_image_amd)' % where)
+    if latent.dtype != torch.float32:
+        raise TypeError('%s: latent must be float32, got %s' % (where, latent.dtype))
+    if latent.dim() != 2 or latent.numel() == 0:
+        raise ValueError('%s: latent must be a non-empty [B,D], got %s' % (where, tuple(latent.shape)))
+    b, d = latent.shape
+    in_place = (d == 1 or latent.stride(1) == 1) and (b == 1 or latent.stride(0) >= d)
+    return latent if in_place else latent.contiguous()
+
+
+def synth_head_args(latent, affine_weight, affine_bias, weight_gain, bias_gain, conv_weight, demodulate=True, style_gain=1.0,
+                    where='synth_head'):
+    """The checked arguments of nfi_synth_head_args shared by the forward and the backward, as a dict: latent [B,D] (a view
+    with unit stride along d is read in place), affine_weight [I,D], affine_bias [I] or None, conv_weight [O,I,kh,kw]."""
+    latent = _latent_rows(latent, where)
+    b, d = latent.shape
+    if affine_weight.dim() != 2 or affine_weight.shape[1] != d or affine_weight.shape[0] < 1:
+        raise ValueError('%s: affine_weight must be [I,%d], got %s' % (where, d, tuple(affine_weight.shape)))
+    i = affine_weight.shape[0]
+    if conv_weight.dim() < 2 or conv_weight.shape[1] != i or conv_weight.numel() == 0:
+        raise ValueError('%s: conv_weight must be a non-empty [O,%d,...], got %s' % (where, i, tuple(conv_weight.shape)))
+    o = conv_weight.shape[0]
+    k = conv_weight.numel() // (o * i)
+    affine_weight = _f32c(affine_weight, 'affine_weight', latent, i * d, where, align=4)
+    affine_bias = _f32c(affine_bias, 'affine_bias', latent, i, where, align=4)
+    conv_weight = _f32c(conv_weight, 'conv_weight', latent, o * i * k, where, align=4)
+    for name, g in (('weight_gain', weight_gain), ('bias_gain', bias_gain), ('style_gain', style_gain)):
+        if not math.isfinite(g):
+            raise ValueError('%s: %s must be finite, got %r' % (where, name, g))
+    return dict(batch=b, latent_dim=d, in_channels=i, out_channels=o, taps=k, latent_stride=latent.stride(0) if b > 1 else d,
+                demodulate=int(bool(demodulate)), weight_gain=float(weight_gain), bias_gain=float(bias_gain), style_gain=float(style_gain),
+                latent=latent, affine_weight=affine_weight, affine_bias=affine_bias, weight=conv_weight)
+
+
+@functools.lru_cache(maxsize=None)
+def _synth_head_workspace_bytes(b, d, stride, i, o, k, demodulate):
+    return _lib.struct_query('nfi_synth_head_bwd_workspace_bytes', 'nfi_synth_head_args', batch=b, latent_dim=d, latent_stride=stride,
+                             in_channels=i, out_channels=o, taps=k, demodulate=demodulate)
+
+
+def _synth_head_launch(kw):
+    dev = kw['latent'].device
+    styles = torch.empty((kw['batch'], kw['in_channels']), dtype=torch.float32, device=dev)
+    dcoefs = torch.empty((kw['batch'], kw['out_channels']), dtype=torch.float32, device=dev) if kw['demodulate'] else None
+    with torch.cuda.device(dev):
+        _lib.call_struct('nfi_synth_head_fwd', 'nfi_synth_head_args', _stream(styles), styles=styles, dcoefs=dcoefs, **kw)
+    return styles, dcoefs
+
+
+def _synth_head_bwd_launch(kw, g_styles, g_dcoefs, styles, dcoefs, need_latent, need_affine_weight, need_affine_bias, need_weight):
+    """g_styles / g_dcoefs / styles / dcoefs: dense float32 [B,I] / [B,O] on the device of kw['latent'], or None."""
+    b, d, i, o, k = (kw[n] for n in ('batch', 'latent_dim', 'in_channels', 'out_channels', 'taps'))
+    dev = kw['latent'].device
+    res = {}
+    if need_latent:
+        res['g_latent'] = torch.empty((b, d), dtype=torch.float32, device=dev)
+    if need_affine_weight:
+        res['g_affine_weight'] = torch.empty((i, d), dtype=torch.float32, device=dev)
+    if need_affine_bias:
+        res['g_affine_bias'] = torch.empty((i,), dtype=torch.float32, device=dev)
+    if need_weight:
+        res['g_weight'] = torch.empty((o, i, k), dtype=torch.float32, device=dev)
+    n_ws = _synth_head_workspace_bytes(b, d, kw['latent_stride'], i, o, k, kw['demodulate'])
+    if n_ws == 0:
+        raise RuntimeError('synth_head_bwd: shape not supported: B %d, D %d, I %d, O %d, K %d' % (b, d, i, o, k))
+    ws = torch.empty((n_ws // 8,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call_struct('nfi_synth_head_bwd', 'nfi_synth_head_args', _stream(ws), styles=styles, dcoefs=dcoefs, g_styles=g_styles,
+                         g_dcoefs=g_dcoefs, workspace=ws, workspace_bytes=n_ws, **dict(kw, **res))
+    return res
+
+
+def synth_head(latent, affine_weight, affine_bias, weight_gain, bias_gain, conv_weight, demodulate=True, style_gain=1.0):
+    """What a synthesis layer does before its convolution, up to the modulation (models/stylegan.py:173-177, 127-130; 373 for
+    toRGB): (styles [B,I], dcoefs [B,O] or None without demodulate).  Two launches, one without demodulate; the [B,O,I,kh,kw]
+    product of the reference is never formed."""
+    return _synth_head_launch(synth_head_args(latent, affine_weight, affine_bias, weight_gain, bias_gain, conv_weight, demodulate, style_gain))
+
+
+def synth_head_bwd(g_styles, g_dcoefs, styles, dcoefs, latent, affine_weight, affine_bias, weight_gain, bias_gain, conv_weight,
+                   demodulate=True, style_gain=1.0, need_latent=True, need_affine_weight=True, need_affine_bias=True, need_weight=True):
+    """Gradients of synth_head for the upstream g_styles [B,I] and g_dcoefs [B,O] (either may be None); styles and dcoefs are
+    the forward's results.  Returns a dict with whichever of g_latent [B,D], g_affine_weight [I,D], g_affine_bias [I] and
+    g_weight [O,I,K] (the demodulation's share only; needs g_dcoefs) were asked for.  At most four launches, every sum in
+    a fixed order: the same bits on every call."""
+    where = 'synth_head_bwd'
+    kw = synth_head_args(latent, affine_weight, affine_bias, weight_gain, bias_gain, conv_weight, demodulate, style_gain, where)
+    on, b, i, o = kw['latent'], kw['batch'], kw['in_channels'], kw['out_channels']
+    styles, g_styles = _f32c(styles, 'styles', on, b * i, where, align=4), _f32c(g_styles, 'g_styles', on, b * i, where, align=4)
+    dcoefs, g_dcoefs = _f32c(dcoefs, 'dcoefs', on, b * o, where, align=4), _f32c(g_dcoefs, 'g_dcoefs', on, b * o, where, align=4)
+    if styles is None:
+        raise ValueError('%s: styles (the forward\'s result) is needed' % where)
+    if g_styles is None and g_dcoefs is None:
+        raise ValueError('%s: no upstream gradient (g_styles and g_dcoefs both None)' % where)
+    if g_dcoefs is not None and (dcoefs is None or not demodulate):
+        raise ValueError('%s: g_dcoefs without dcoefs (the forward\'s result, with demodulate)' % where)
+    need_affine_bias = bool(need_affine_bias) and kw['affine_bias'] is not None
+    if need_weight and g_dcoefs is None:
+        raise ValueError('%s: need_weight without g_dcoefs (g_weight is the demodulation\'s share only)' % where)
+    if not (need_latent or need_affine_weight or need_affine_bias or need_weight):
+        raise ValueError('%s: no gradient is wanted' % where)
+    return _synth_head_bwd_launch(kw, g_styles, g_dcoefs, styles, dcoefs, bool(need_latent), bool(need_affine_weight), need_affine_bias,
+                                  bool(need_weight))
+
+
+def synth_modulate_args(x, styles, where='synth_modulate'):
+    """The checked arguments of nfi_synth_modulate_args: x [B,C,...] dense (copied if not), styles [B,C]."""
+    x = _f32c(x, 'x', align=4)
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError('%s: x must be a non-empty [B,C,...], got %s' % (where, tuple(x.shape)))
+    b, c = x.shape[0], x.shape[1]
+    styles = _f32c(styles, 'styles', x, b * c, where, align=4)
+    return dict(batch=b, channels=c, plane=x.numel() // (b * c), x=x, styles=styles)
+
+
+def _synth_modulate_launch(kw):
+    out = torch.empty_like(kw['x'])
+    with torch.cuda.device(out.device):
+        _lib.call_struct('nfi_synth_modulate_fwd', 'nfi_synth_modulate_args', _stream(out), out=out, **kw)
+    return out
+
+
+def _synth_modulate_bwd_launch(kw, g_out, need_x, need_styles):
+    """g_out: dense float32, x's shape and device."""
+    g_x = torch.empty_like(kw['x']) if need_x else None
+    g_styles = torch.empty((kw['batch'], kw['channels']), dtype=torch.float32, device=g_out.device) if need_styles else None
+    with torch.cuda.device(g_out.device):
+        _lib.call_struct('nfi_synth_modulate_bwd', 'nfi_synth_modulate_args', _stream(g_out), g_out=g_out, g_x=g_x, g_styles=g_styles, **kw)
+    return g_x, g_styles
+
+
+def synth_modulate(x, styles):
+    """x * styles.reshape(B, -1, 1, 1) (models/stylegan.py:132): x [B,C,H,W] (any trailing shape), styles [B,C] -> x's shape,
+    dense.  One launch."""
+    return _synth_modulate_launch(synth_modulate_args(x, styles))
+
+
+def synth_modulate_bwd(g_out, x, styles, need_x=True, need_styles=True):
+    """(g_x = g_out * styles or None, g_styles [B,C] = sum over the plane of g_out * x or None).  One launch; the sums run
+    in a fixed order: the same bits on every call."""
+    where = 'synth_modulate_bwd'
+    kw = synth_modulate_args(x, styles, where)
+    g_out = _f32c(g_out, 'g_out', kw['x'], kw['x'].numel(), where, align=4)
+    if tuple(g_out.shape) != tuple(kw['x'].shape):
+        raise ValueError('%s: g_out must have x\'s shape %s, got %s' % (where, tuple(kw['x'].shape), tuple(g_out.shape)))
+    if not (need_x or need_styles):
+        raise ValueError('%s: no gradient is wanted' % where)
+    return _synth_modulate_bwd_launch(kw, g_out, bool(need_x), bool(need_styles))
+
+
+# --------------------------------------------------------------------------- #
 # pose algebra of the inversion loop (lib/pose_utils.py; csrc/nfi_pose.inc): thread = image, one launch per call
 # --------------------------------------------------------------------------- #
 def _pose_rows(t, tail, name, b=None):

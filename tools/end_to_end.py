@@ -101,7 +101,7 @@ def _time_steps(step, iters, warmup):
 
 
 def _scene(geometry, batch, dev, impl, texels, fused_handoff=False, hip_regularisers=False, channels_last=False,
-           fused_synthesis_tail=False):
+           fused_synthesis_tail=False, fused_synthesis_head=False):
     import copy
     import reference_cases as rc
     import nerf_from_image_amd.generator as nfi_gen
@@ -110,7 +110,8 @@ def _scene(geometry, batch, dev, impl, texels, fused_handoff=False, hip_regulari
     sc = rc.build_scene(geometry, batch, dev)
     if impl == 'hip':
         model = nfi_gen.attach(copy.deepcopy(sc.gen), texel_dtype=rc.texel_code(texels), hip_regularisers=hip_regularisers,
-                               fused_handoff=fused_handoff, fused_synthesis_tail=fused_synthesis_tail)
+                               fused_handoff=fused_handoff, fused_synthesis_tail=fused_synthesis_tail,
+                               fused_synthesis_head=fused_synthesis_head)
         ren = nfi_render.make_render(sc.args, sc.dcfg)
     else:
         model = sc.gen
@@ -161,9 +162,9 @@ def leg_render(dev, impl, batch=8, texels='fp32', iters=20, warmup=3, markers=Fa
 
 
 def leg_inversion(dev, impl, batch=4, texels='fp32', iters=12, warmup=3, markers=False, res=128, samples=64,
-                  fused_synthesis_tail=False):
+                  fused_synthesis_tail=False, fused_synthesis_head=False):
     import reference_cases as rc
-    sc, model, ren = _scene('p3d', batch, dev, impl, texels, fused_synthesis_tail=fused_synthesis_tail)
+    sc, model, ren = _scene('p3d', batch, dev, impl, texels, fused_synthesis_tail=fused_synthesis_tail, fused_synthesis_head=fused_synthesis_head)
     model.requires_grad_(False)
     with torch.no_grad():
         tgt = rc.reference_render(sc, res, samples, None)
@@ -195,9 +196,9 @@ def leg_inversion(dev, impl, batch=4, texels='fp32', iters=12, warmup=3, markers
 
 
 def leg_gstep(dev, impl, batch=4, texels='fp32', iters=12, warmup=3, markers=False, res=128, samples=64, fused_handoff=False,
-              path_length=False, hip_regularisers=True, fused_synthesis_tail=False):
+              path_length=False, hip_regularisers=True, fused_synthesis_tail=False, fused_synthesis_head=False):
     sc, model, ren = _scene('cub', batch, dev, impl, texels, fused_handoff=fused_handoff, hip_regularisers=hip_regularisers,
-                            fused_synthesis_tail=fused_synthesis_tail)
+                            fused_synthesis_tail=fused_synthesis_tail, fused_synthesis_head=fused_synthesis_head)
     model.train().requires_grad_(True)
     g = torch.Generator().manual_seed(77)
     t_img = torch.cat([torch.rand(batch, res, res, 3, generator=g) * 2 - 1, (torch.rand(batch, res, res, 1, generator=g) > 0.5).float()],
@@ -285,6 +286,8 @@ def main():
     ap.add_argument('--path-length', action='store_true')
     ap.add_argument('--fused-synthesis-tail', action='store_true',
                     help='inversion and gstep legs, hip: attach(fused_synthesis_tail=True), every synthesis layer\'s tail as one HIP node')
+    ap.add_argument('--fused-synthesis-head', action='store_true',
+                    help='inversion and gstep legs, hip: attach(fused_synthesis_head=True), every layer\'s head as HIP nodes too (implies the tail)')
     ap.add_argument('--reference-regularisers', action='store_true', help='hip: leave the regulariser branch to the original forward')
     ap.add_argument('--sidecar', help='JSON written for tools/phase_split.py (marker table, steps, warm-up)')
     ap.add_argument('--quick', action='store_true')
@@ -306,6 +309,9 @@ def main():
     if a.fused_synthesis_tail:                                      # the key appears in the result only with the flag
         assert a.leg in ('inversion', 'gstep') and a.impl == 'hip', '--fused-synthesis-tail is an option of the drop-in\'s producer legs'
         kw['fused_synthesis_tail'] = True
+    if a.fused_synthesis_head:
+        assert a.leg in ('inversion', 'gstep') and a.impl == 'hip', '--fused-synthesis-head is an option of the drop-in\'s producer legs'
+        kw['fused_synthesis_head'] = True
     r = LEGS[a.leg](dev, a.impl, **kw)
     r.update(leg=a.leg, impl=a.impl, **{k: v for k, v in kw.items() if k not in ('iters', 'warmup')})
     if a.sidecar:
