@@ -36,7 +36,6 @@ def field_query_bwd(points, texels, decoder_image, w1, w2, scene_range, n_attent
     n3 = n_attention if n_attention > 0 else 3
     if viewdir is not None:
         n_out = 33
-    lib = _lib.load()
     out = {}
     if not points_only:
         # fp32 gradient image in the texels' layout (16-bit texel storage: the gradient w.r.t. the rounded planes)
@@ -80,11 +79,9 @@ def field_query_bwd(points, texels, decoder_image, w1, w2, scene_range, n_attent
             g_sdf=f(g_sdf, 'g_sdf', B * P), g_semantics=f(g_semantics, 'g_semantics', B * P * n_attention),
             points_only=int(points_only), normalize_g_points=int(normalize_points), scatter_mode=int(scatter_mode),
             **vd_args, **out)
-    n_ws = _lib.struct_query('nfi_field_bwd_workspace_bytes', 'nfi_field_bwd_args', **fields)
-    ws = torch.empty(((n_ws + 3) // 4,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_field_query_bwd', 'nfi_field_bwd_args', ops._stream(points), workspace=ws,
-                         workspace_bytes=ws.numel() * 4, **fields)
+    ws = ops._workspace(_lib.struct_query('nfi_field_bwd_workspace_bytes', 'nfi_field_bwd_args', **fields), points, where,
+                        (B, P, ops.texel_res(texels)), torch.float32)
+    ops._launch('nfi_field_query_bwd', 'nfi_field_bwd_args', points, workspace=ws, workspace_bytes=ws.numel() * 4, **fields)
     if 'g_ray_features' in vd_args:
         out['g_ray_features'] = vd_args['g_ray_features'][..., 1:33]
     return out

@@ -9,12 +9,18 @@ The argument contract (tests/contract_util.py has a row per wrapper, tests/test_
 sees pointers and a few integers, so this layer is the only one that can know a tensor's strides, dtype, device and
 length.  Every tensor argument is therefore
   - refused when it is not on the GPU (RuntimeError), has the wrong dtype (TypeError), lives on another device than the
-    tensor whose stream the call uses, or does not hold the element count the kernel indexes (ValueError) - _f32c with
-    `on` / `n`, _need, _texels, _decoder_image, _attention, _u_and_stride;
+    tensor whose stream the call uses, or does not hold the element count the kernel indexes (ValueError) - _refuse, the
+    one place that says so; _f32c (with `on` / `n`) is its common front, and _texels, _u_and_stride, _latent_rows,
+    _range_flag and the tensors a caller hands in to be written rest on it too; _need checks shapes by rows;
   - copied when it is not dense in the layout its shape claims, or when its first byte is not on a multiple of
     POINTER_ALIGN (a contiguous view at an odd offset into a flat buffer): kernels read texels, planes and the hand-off's
-    activations as 16-byte vectors, and no other alignment is tested for the rest - _dense.
+    activations as 16-byte vectors, and no other alignment is tested for the rest - _dense, _dense_channels_last, and
+    _nchw_or_nhwc for the images that are read in place in either layout.
 All of it is attribute reads on the host: a dense, aligned argument costs no launch and no device-to-host read.
+
+Every launch goes through _launch (the entries that take a struct) or _launch_positional (the rest): they enter the device
+of the tensor whose stream the call uses and pass that device's current stream.  _workspace allocates a call's scratch
+buffer, or raises for a shape the library reports as unsupported (a size of 0).
 """
 import functools
 import math
@@ -77,13 +83,39 @@ def _stream(t):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
-def _call_ordered(entry, struct, on, unsupported, args):
-    """An ordered entry with a workspace: the size from `entry`_workspace_bytes (0: RuntimeError(unsupported)), allocated per call."""
-    n_ws = _lib.struct_query(entry + '_workspace_bytes', struct, **args)
-    if n_ws == 0:
-        raise RuntimeError(unsupported)
-    ws = torch.empty((n_ws,), dtype=torch.uint8, device=on.device)
-    _lib.call_struct(entry, struct, _stream(on), ws, n_ws, **args)
+def _launch(entry, struct, on, *extra, **fields):
+    """One entry that takes a struct, on the current stream of the device of `on`, with that device entered for the call.
+    extra: the entry's arguments between the struct and the stream (a tensor stands for its device pointer).  (The device
+    goes to torch as its index: that spares both calls the parsing of a torch.device, on a path a host-bound layer runs
+    several times.)"""
+    index = on.get_device()
+    with torch.cuda.device(index):
+        _lib.call_struct(entry, struct, torch.cuda.current_stream(index).cuda_stream, *extra, **fields)
+
+
+def _launch_positional(entry, on, *args):
+    """The same for an entry that takes its arguments one by one; args: all of them but the stream (a tensor stands for
+    its device pointer, None for a null pointer)."""
+    fn = getattr(_lib.load(), entry)
+    index = on.get_device()
+    with torch.cuda.device(index):
+        _lib.check(fn(*[_lib.ptr(a) if torch.is_tensor(a) else a for a in args], torch.cuda.current_stream(index).cuda_stream), entry)
+
+
+def _workspace(n_bytes, on, where, shape, dtype=torch.uint8):
+    """A call's scratch buffer of at least n_bytes on the device of `on`, as whole elements of `dtype` (the type whose
+    alignment the kernel counts on).  A size of 0 is the library's answer for a shape it does not support: RuntimeError
+    naming `where` and `shape`."""
+    if n_bytes == 0:
+        raise RuntimeError('%s: shape not supported: %s' % (where, shape))
+    size = dtype.itemsize
+    return torch.empty(((n_bytes + size - 1) // size,), dtype=dtype, device=on.device)
+
+
+def _call_ordered(entry, struct, on, where, shape, args):
+    """An ordered entry with a workspace: the size from `entry`_workspace_bytes, allocated per call."""
+    ws = _workspace(_lib.struct_query(entry + '_workspace_bytes', struct, **args), on, where, shape)
+    _launch(entry, struct, on, ws, ws.numel(), **args)
 
 
 POINTER_ALIGN = 16         # bytes: the widest vector a kernel reads or writes through a caller's pointer
@@ -102,21 +134,40 @@ def _dense_channels_last(t, align=POINTER_ALIGN):
     return t.clone(memory_format=torch.preserve_format) if t.data_ptr() % align else t
 
 
-def _f32c(t, name, on=None, n=None, where=None, align=POINTER_ALIGN):
-    """t as a dense, `align`-byte aligned float32 tensor on the GPU (copied if it is not; None stays None).  on: the
-    tensor whose device and stream the call uses - another device is refused; n: the element count the kernel indexes -
-    another count is refused.  Attribute reads on the host only: no launch for a dense, aligned argument."""
-    if t is None:
-        return None
+def _refuse(t, name, on=None, n=None, where=None, dtypes=(torch.float32,)):
+    """The refusal rule of every tensor argument, in one place; returns t itself (whether it is copied is the caller's
+    business).  Not on the GPU: RuntimeError; a dtype outside `dtypes` (None: any): TypeError; on another device than `on`,
+    the tensor whose device and stream the call uses, or another element count than n, the one the kernel indexes:
+    ValueError.  Attribute reads on the host only."""
     if not t.is_cuda:
         raise RuntimeError('%s must live on the GPU (no CPU path in nerf_from_image_amd)' % name)
-    if t.dtype != torch.float32:
-        raise TypeError('%s must be float32, got %s' % (name, t.dtype))
+    if dtypes is not None and t.dtype not in dtypes:
+        raise TypeError('%s must be %s, got %s' % (name, ' / '.join(str(d)[len('torch.'):] for d in dtypes), t.dtype))
     if on is not None and t.device != on.device:
         raise ValueError('%s: %s lives on %s, the call runs on %s' % (where or name, name, t.device, on.device))
     if n is not None and t.numel() != n:
         raise ValueError('%s: %s must hold %d elements, got %s' % (where or name, name, n, list(t.shape)))
-    return _dense(t, align)
+    return t
+
+
+def _f32c(t, name, on=None, n=None, where=None, align=POINTER_ALIGN):
+    """t as a dense, `align`-byte aligned float32 tensor on the GPU (refused by _refuse's rule, copied if it is not dense
+    and aligned; None stays None).  No launch for a dense, aligned argument."""
+    if t is None:
+        return None
+    t = _refuse(t, name, on, n, where).contiguous()            # (_dense, written out: a call comes through here per argument)
+    return t.clone() if t.data_ptr() % align else t
+
+
+def _nchw_or_nhwc(t):
+    """(the tensor a kernel reads, its layout code) for an image [B,C,H,W] that is read in place in either layout: t
+    itself and 0 (SSIM_BCHW, FILTER_BCHW) if it is dense, t itself and 1 (SSIM_BHWC, FILTER_BHWC) if it is dense as
+    [B,H,W,C] behind a permute, else a contiguous copy and 0."""
+    if t.is_contiguous():
+        return t, 0
+    if t.permute(0, 2, 3, 1).is_contiguous():
+        return t, 1
+    return t.contiguous(), 0
 
 
 def _texels(texels, n_scenes, on, where, fp32_only=False):
@@ -124,14 +175,9 @@ def _texels(texels, n_scenes, on, where, fp32_only=False):
     float32), at least n_scenes scenes, and DENSE in the layout its shape claims - a view of the right shape over other
     strides (a permute of the other layout, a slice of a wider buffer) or at an unaligned offset is copied, as every other
     argument is, never read as if it were dense."""
-    if not texels.is_cuda:
-        raise RuntimeError('texels must live on the GPU (no CPU path in nerf_from_image_amd)')
-    if fp32_only and texels.dtype != torch.float32:
-        raise TypeError('%s: fp32 texels only, got %s' % (where, texels.dtype))
+    _refuse(texels, 'texels', on, where=where, dtypes=(torch.float32,) if fp32_only else tuple(_TEXEL_TORCH.values()))
     tdt = texel_dtype_of(texels)
     layout = texel_layout_of(texels)
-    if texels.device != on.device:
-        raise ValueError('%s: texels live on %s, the call runs on %s' % (where, texels.device, on.device))
     if texels.shape[0] < n_scenes:
         raise ValueError('%s: texels of %d scene(s) where %d are indexed' % (where, texels.shape[0], n_scenes))
     return _dense(texels), tdt, layout
@@ -168,8 +214,8 @@ def _need(t, n, tail, name, where):
 def _one_device(where, on, *tensors):
     """Refuse (ValueError) a call whose tensors do not all live on the device of `on`, the tensor whose stream is used."""
     for t in tensors:
-        if torch.is_tensor(t) and t.device != on.device:
-            raise ValueError('%s: an argument of shape %s lives on %s, the call runs on %s' % (where, list(t.shape), t.device, on.device))
+        if torch.is_tensor(t) and t.device != on.device:        # (the name is put together for a refusal only)
+            _refuse(t, 'an argument of shape %s' % list(t.shape), on, where=where, dtypes=None)
 
 
 def _points(points, where):
@@ -206,10 +252,7 @@ def planes_to_texels(planes, texel_dtype=TEXEL_F32):
         raise ValueError('planes must be [B,3,32,R,R], got %s' % (tuple(planes.shape),))
     dt = _TEXEL_TORCH[texel_dtype]
     texels = torch.empty((B, 3, R, R, 32), dtype=dt, device=planes.device)
-    lib = _lib.load()
-    with torch.cuda.device(planes.device):
-        _lib.check(lib.nfi_planes_to_texels(_lib.ptr(planes), _lib.ptr(texels), B, R, texel_dtype, _stream(planes)),
-                   'nfi_planes_to_texels')
+    _launch_positional('nfi_planes_to_texels', planes, planes, texels, B, R, texel_dtype)
     return texels
 
 
@@ -220,10 +263,7 @@ def texels_to_planes(texels):
         raise ValueError('texels_to_planes: planar texels [B,3,R,R,32] expected, got %s' % (tuple(texels.shape),))
     B, three, R, R2, C = texels.shape
     planes = torch.empty((B, 3, C, R, R), dtype=torch.float32, device=texels.device)
-    lib = _lib.load()
-    with torch.cuda.device(texels.device):
-        _lib.check(lib.nfi_texels_to_planes(_lib.ptr(texels), _lib.ptr(planes), B, R, _stream(texels)),
-                   'nfi_texels_to_planes')
+    _launch_positional('nfi_texels_to_planes', texels, texels, planes, B, R)
     return planes
 
 
@@ -236,11 +276,8 @@ def decoder_pack(w1, b1, w2, b2, n_attention, texel_dtype=TEXEL_F32):
             or tuple(b2.shape) != (n_out,):
         raise ValueError('decoder shapes must be [64,32],[64],[%d,64],[%d]; got %s %s %s %s' % (
             n_out, n_out, tuple(w1.shape), tuple(b1.shape), tuple(w2.shape), tuple(b2.shape)))
-    lib = _lib.load()
-    image = torch.empty((lib.nfi_decoder_image_floats(),), dtype=torch.float32, device=w1.device)
-    with torch.cuda.device(w1.device):
-        _lib.check(lib.nfi_decoder_pack(_lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), n_attention,
-                                        texel_dtype, _lib.ptr(image), _stream(w1)), 'nfi_decoder_pack')
+    image = torch.empty((_decoder_image_floats(False),), dtype=torch.float32, device=w1.device)
+    _launch_positional('nfi_decoder_pack', w1, w1, b1, w2, b2, n_attention, texel_dtype, image)
     return image
 
 
@@ -255,11 +292,8 @@ def decoder_pack_viewdir(w1, b1, w2, b2, w3, b3, n_attention, texel_dtype=TEXEL_
     want = [(64, 32), (64,), (33, 64), (33,), (n3, 32), (n3,)]
     if [tuple(t.shape) for t in ts] != want:
         raise ValueError('view-direction decoder shapes must be %s; got %s' % (want, [tuple(t.shape) for t in ts]))
-    lib = _lib.load()
-    image = torch.empty((lib.nfi_decoder_image_floats_viewdir(),), dtype=torch.float32, device=ts[0].device)
-    with torch.cuda.device(ts[0].device):
-        _lib.check(lib.nfi_decoder_pack_viewdir(*[_lib.ptr(t) for t in ts], n_attention, texel_dtype, _lib.ptr(image),
-                                                _stream(ts[0])), 'nfi_decoder_pack_viewdir')
+    image = torch.empty((_decoder_image_floats(True),), dtype=torch.float32, device=w1.device)
+    _launch_positional('nfi_decoder_pack_viewdir', w1, *ts, n_attention, texel_dtype, image)
     return image
 
 
@@ -279,10 +313,8 @@ def raygen(height, width, focal, cam2world, bbox=None, center=None, normalize=Fa
     focal, bbox, center = _camera_extras(focal, bbox, center, cam2world, 'raygen')
     ro = torch.empty((B, height, width, 3), dtype=torch.float32, device=dev)
     rd = torch.empty_like(ro)
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_raygen', 'nfi_raygen_args', _stream(cam2world), n_scenes=B, height=height, width=width,
-                         cam2world=cam2world, focal=focal, bbox=bbox, center=center, normalize=int(normalize),
-                         ray_origins=ro, ray_directions=rd)
+    _launch('nfi_raygen', 'nfi_raygen_args', cam2world, n_scenes=B, height=height, width=width, cam2world=cam2world,
+            focal=focal, bbox=bbox, center=center, normalize=int(normalize), ray_origins=ro, ray_directions=rd)
     return ro, rd
 
 
@@ -302,10 +334,9 @@ def near_far(ray_origins, ray_directions, scene_range, strict=True):
     near, far = torch.empty_like(near_raw), torch.empty_like(near_raw)
     hit = torch.empty((n,), dtype=torch.uint8, device=dev)
     red = torch.empty((4,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_near_far', 'nfi_near_far_args', _stream(ro), n_rays=n, ray_origins=ro,
-                         ray_directions=rd, scene_range=float(scene_range), near_raw=near_raw, far_raw=far_raw,
-                         hit=hit, reduce=red, near_plane=near, far_plane=far)
+    _launch('nfi_near_far', 'nfi_near_far_args', ro, n_rays=n, ray_origins=ro, ray_directions=rd,
+            scene_range=float(scene_range), near_raw=near_raw, far_raw=far_raw, hit=hit, reduce=red, near_plane=near,
+            far_plane=far)
     if strict == 'deferred':
         _raise_pending(dev)
         _defer_hit_count(red[2:3], dev)
@@ -326,10 +357,8 @@ def stratified_points(ray_origins, ray_directions, near, far, num_samples, noise
     noise = _f32c(noise, 'noise', ro, n * num_samples, where)
     depth = torch.empty((*shape, num_samples), dtype=torch.float32, device=ro.device)
     points = torch.empty((*shape, num_samples, 3), dtype=torch.float32, device=ro.device) if want_points else None
-    with torch.cuda.device(ro.device):
-        _lib.call_struct('nfi_stratified_points', 'nfi_stratified_args', _stream(ro), n_rays=n,
-                         n_samples=num_samples, ray_origins=ro, ray_directions=rd, near_plane=near, far_plane=far,
-                         noise=noise, depth=depth, points=points)
+    _launch('nfi_stratified_points', 'nfi_stratified_args', ro, n_rays=n, n_samples=num_samples, ray_origins=ro,
+            ray_directions=rd, near_plane=near, far_plane=far, noise=noise, depth=depth, points=points)
     return points, depth
 
 
@@ -340,10 +369,7 @@ def points_on_rays(ray_origins, ray_directions, depth):
     ro = _f32c(ray_origins, 'ray_origins', depth, 3 * n, 'points_on_rays')
     rd = _f32c(ray_directions, 'ray_directions', depth, 3 * n, 'points_on_rays')
     points = torch.empty((*depth.shape, 3), dtype=torch.float32, device=depth.device)
-    lib = _lib.load()
-    with torch.cuda.device(depth.device):
-        _lib.check(lib.nfi_points_on_rays(_lib.ptr(ro), _lib.ptr(rd), _lib.ptr(depth), n, S, _lib.ptr(points),
-                                          _stream(depth)), 'nfi_points_on_rays')
+    _launch_positional('nfi_points_on_rays', depth, ro, rd, depth, n, S, points)
     return points
 
 
@@ -376,15 +402,12 @@ def field_query(points, texels, decoder_image, scene_range, n_attention, attenti
         out['semantics'] = torch.empty((B, P, n_attention), dtype=torch.float32, device=dev)
     if want_outside:
         out['outside'] = torch.empty((B, P), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_field_query_fwd', 'nfi_field_args', _stream(points), n_scenes=B, points_per_scene=P,
-                         points=points, texels=texels, plane_res=texel_res(texels), texel_dtype=tdt,
-                         texel_layout=layout,
-                         decoder_image=decoder_image, n_attention=n_attention, attention_values=att,
-                         use_sdf=int(use_sdf), beta=beta, alpha=alpha, scene_range=float(scene_range),
-                         sigma=out['sigma'], rgb=out['rgb'], sdf=out.get('sdf'), semantics=out.get('semantics'),
-                         outside=out.get('outside'), ray_features=ray_features, samples_per_ray=int(samples_per_ray),
-                         mlp_precision=int(mlp_precision))
+    _launch('nfi_field_query_fwd', 'nfi_field_args', points, n_scenes=B, points_per_scene=P, points=points, texels=texels,
+            plane_res=texel_res(texels), texel_dtype=tdt, texel_layout=layout, decoder_image=decoder_image,
+            n_attention=n_attention, attention_values=att, use_sdf=int(use_sdf), beta=beta, alpha=alpha,
+            scene_range=float(scene_range), sigma=out['sigma'], rgb=out['rgb'], sdf=out.get('sdf'),
+            semantics=out.get('semantics'), outside=out.get('outside'), ray_features=ray_features,
+            samples_per_ray=int(samples_per_ray), mlp_precision=int(mlp_precision))
     return out
 
 
@@ -398,9 +421,7 @@ def bbox_overlay(points, sigma, scene_range):
         raise ValueError('bbox_overlay: points %s do not match sigma %s' % (tuple(points.shape), tuple(sigma.shape)))
     out = torch.empty_like(sigma)
     thr = float(np.float32(scene_range - 5e-2))          # `x < scene_range - eps` against an fp32 tensor
-    with torch.cuda.device(sigma.device):
-        _lib.check(_lib.load().nfi_bbox_overlay(_lib.ptr(points), n, float(scene_range), thr, _lib.ptr(sigma),
-                                                _lib.ptr(out), _stream(sigma)), 'nfi_bbox_overlay')
+    _launch_positional('nfi_bbox_overlay', sigma, points, n, float(scene_range), thr, sigma, out)
     return out
 
 
@@ -413,20 +434,15 @@ def ray_weights(sigma, ray_directions, depth):
     _need(sigma, n, (S,), 'sigma', 'ray_weights')
     _need_rays(rd, n, 'ray_weights')
     w = torch.empty_like(depth)
-    with torch.cuda.device(depth.device):
-        _lib.call_struct('nfi_ray_weights', 'nfi_weights_args', _stream(depth), n_rays=n, n_samples=S, sigma=sigma,
-                         ray_directions=rd, depth=depth, weights=w)
+    _launch('nfi_ray_weights', 'nfi_weights_args', depth, n_rays=n, n_samples=S, sigma=sigma, ray_directions=rd,
+            depth=depth, weights=w)
     return w
 
 
-def _u_and_stride(u, n, k, where='sample_pdf', on=None):
-    """u: [n,k] dense, or a stride-0 broadcast of one row; float32 on the GPU (the call's device is checked by the caller)."""
-    if not u.is_cuda:
-        raise RuntimeError('%s: u must live on the GPU (no CPU path in nerf_from_image_amd)' % where)
-    if u.dtype != torch.float32:
-        raise TypeError('%s: u must be float32, got %s' % (where, u.dtype))
-    if on is not None and u.device != on.device:
-        raise ValueError('%s: u lives on %s, the call runs on %s' % (where, u.device, on.device))
+def _u_and_stride(u, n, k, where, on):
+    """(u, its row stride) for u [n,k] dense (copied if not), or a stride-0 broadcast of one row, read in place; float32
+    on the device of `on`."""
+    _refuse(u, 'u', on, where=where)
     if u.shape[-1] != k:
         raise ValueError('%s: u must have %d entries per ray, got %s' % (where, k, list(u.shape)))
     if u.dim() == 2 and u.stride(0) == 0 and u.stride(1) == 1 and u.data_ptr() % POINTER_ALIGN == 0:
@@ -445,14 +461,13 @@ def sample_pdf(bins, weights, u, want_inds=False, want_cdf=False):
     n, M = bins.shape
     _need(weights, n, (M - 1,), 'weights', 'sample_pdf')
     K = u.shape[-1]
-    u, stride = _u_and_stride(u, n, K, on=bins)
+    u, stride = _u_and_stride(u, n, K, 'sample_pdf', bins)
     dev = bins.device
     samples = torch.empty((n, K), dtype=torch.float32, device=dev)
     inds = torch.empty((n, K), dtype=torch.int64, device=dev) if want_inds else None
     cdf = torch.empty((n, M), dtype=torch.float32, device=dev) if want_cdf else None
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_sample_pdf', 'nfi_sample_pdf_args', _stream(bins), n_rays=n, n_bins=M, n_samples=K,
-                         bins=bins, weights=weights, u=u, u_row_stride=stride, samples=samples, inds=inds, cdf=cdf)
+    _launch('nfi_sample_pdf', 'nfi_sample_pdf_args', bins, n_rays=n, n_bins=M, n_samples=K, bins=bins, weights=weights,
+            u=u, u_row_stride=stride, samples=samples, inds=inds, cdf=cdf)
     return samples, inds, cdf
 
 
@@ -465,7 +480,7 @@ def resample(sigma, ray_directions, depth, u, want_taps=False):
     _need_rays(rd, n, 'resample')
     if u.shape[-1] != S:
         raise ValueError('resample: u must have %d entries per ray, got %s' % (S, list(u.shape)))
-    u, stride = _u_and_stride(u.reshape(-1, S) if u.stride(0) != 0 else u, n, S, 'resample', on=depth)
+    u, stride = _u_and_stride(u.reshape(-1, S) if u.stride(0) != 0 else u, n, S, 'resample', depth)
     dev = depth.device
     fine = torch.empty((n, S), dtype=torch.float32, device=dev)
     taps = {}
@@ -474,9 +489,8 @@ def resample(sigma, ray_directions, depth, u, want_taps=False):
                     smooth=torch.empty((n, S), dtype=torch.float32, device=dev),
                     cdf=torch.empty((n, S - 1), dtype=torch.float32, device=dev),
                     inds=torch.empty((n, S), dtype=torch.int64, device=dev))
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_resample', 'nfi_resample_args', _stream(depth), n_rays=n, n_samples=S, sigma=sigma,
-                         ray_directions=rd, depth=depth, u=u, u_row_stride=stride, fine_depth=fine, **taps)
+    _launch('nfi_resample', 'nfi_resample_args', depth, n_rays=n, n_samples=S, sigma=sigma, ray_directions=rd, depth=depth,
+            u=u, u_row_stride=stride, fine_depth=fine, **taps)
     return fine, taps
 
 
@@ -505,21 +519,26 @@ def _check_lists(where, rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, ex
     return n
 
 
-def composite(ray_directions, depth_a, sigma_a, rgb_a, depth_b=None, sigma_b=None, rgb_b=None, extra_a=None,
-              extra_b=None, white_background=True, want_taps=False):
+def _lists(where, ray_directions, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a, extra_b):
+    """The directions and the sample lists of composite / composite_bwd as dense float32, checked by _check_lists:
+    (rays, samples of list a, of list b, extra channels), (ray_directions, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b,
+    extra_a, extra_b).  Without depth_b there is no list b, without extra_a no extras: those come back None."""
     rd = _f32c(ray_directions, 'ray_directions')
     depth_a, sigma_a, rgb_a = _f32c(depth_a, 'depth'), _f32c(sigma_a, 'sigma'), _f32c(rgb_a, 'rgb')
-    na = depth_a.shape[-1]
-    nb = 0
-    if depth_b is not None:
-        depth_b, sigma_b, rgb_b = _f32c(depth_b, 'depth_b'), _f32c(sigma_b, 'sigma_b'), _f32c(rgb_b, 'rgb_b')
-        nb = depth_b.shape[-1]
-    n_extra = 0
-    if extra_a is not None:
-        extra_a = _f32c(extra_a, 'extra_a')
-        n_extra = extra_a.shape[-1]
-        extra_b = _f32c(extra_b, 'extra_b') if nb else None
-    n = _check_lists('composite', rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a, extra_b if nb else None)
+    if depth_b is None:
+        sigma_b = rgb_b = None
+    depth_b, sigma_b, rgb_b = _f32c(depth_b, 'depth_b'), _f32c(sigma_b, 'sigma_b'), _f32c(rgb_b, 'rgb_b')
+    extra_a = _f32c(extra_a, 'extra_a')
+    extra_b = _f32c(extra_b, 'extra_b') if extra_a is not None and depth_b is not None else None
+    tensors = (rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a, extra_b)
+    n = _check_lists(where, *tensors)
+    return (n, depth_a.shape[-1], 0 if depth_b is None else depth_b.shape[-1], 0 if extra_a is None else extra_a.shape[-1]), tensors
+
+
+def composite(ray_directions, depth_a, sigma_a, rgb_a, depth_b=None, sigma_b=None, rgb_b=None, extra_a=None,
+              extra_b=None, white_background=True, want_taps=False):
+    (n, na, nb, n_extra), (rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a, extra_b) = _lists(
+        'composite', ray_directions, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a, extra_b)
     dev = depth_a.device
     shape = depth_a.shape[:-1]
     rgb_map = torch.empty((*shape, 3), dtype=torch.float32, device=dev)
@@ -531,12 +550,10 @@ def composite(ray_directions, depth_a, sigma_a, rgb_a, depth_b=None, sigma_b=Non
         taps = dict(weights=torch.empty((*shape, na + nb), dtype=torch.float32, device=dev),
                     depth_sorted=torch.empty((*shape, na + nb), dtype=torch.float32, device=dev),
                     perm=torch.empty((*shape, na + nb), dtype=torch.int64, device=dev))
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_composite_fwd', 'nfi_composite_args', _stream(depth_a), n_rays=n, n_a=na, n_b=nb,
-                         ray_directions=rd, depth_a=depth_a, sigma_a=sigma_a, rgb_a=rgb_a, depth_b=depth_b,
-                         sigma_b=sigma_b, rgb_b=rgb_b, n_extra=n_extra, extra_a=extra_a, extra_b=extra_b,
-                         white_background=int(white_background), rgb_map=rgb_map, depth_map=depth_map, mask=mask,
-                         extra_map=extra_map, **taps)
+    _launch('nfi_composite_fwd', 'nfi_composite_args', depth_a, n_rays=n, n_a=na, n_b=nb, ray_directions=rd, depth_a=depth_a,
+            sigma_a=sigma_a, rgb_a=rgb_a, depth_b=depth_b, sigma_b=sigma_b, rgb_b=rgb_b, n_extra=n_extra, extra_a=extra_a,
+            extra_b=extra_b, white_background=int(white_background), rgb_map=rgb_map, depth_map=depth_map, mask=mask,
+            extra_map=extra_map, **taps)
     return rgb_map, depth_map, mask, extra_map, taps
 
 
@@ -574,12 +591,10 @@ def render_setup(cam2world, focal, height, width, scene_range, bbox=None, center
     if workspace is None or workspace.numel() < ws_bytes:
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     _one_device('render_setup', cam2world, workspace)
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_render_setup', 'nfi_render_args', _stream(cam2world), n_scenes=B, height=height, width=width,
-                         scene_range=float(scene_range), cam2world=cam2world, focal=focal,
-                         bbox=bbox, center=center, workspace=workspace,
-                         workspace_bytes=workspace.numel(), row_offset=0 if row_window is None else int(row_window[0]),
-                         full_height=0 if row_window is None else int(row_window[1]))
+    _launch('nfi_render_setup', 'nfi_render_args', cam2world, n_scenes=B, height=height, width=width,
+            scene_range=float(scene_range), cam2world=cam2world, focal=focal, bbox=bbox, center=center, workspace=workspace,
+            workspace_bytes=workspace.numel(), row_offset=0 if row_window is None else int(row_window[0]),
+            full_height=0 if row_window is None else int(row_window[1]))
     return workspace
 
 
@@ -709,7 +724,7 @@ def render_fwd(cam2world, focal, height, width, num_samples, texels, decoder_ima
     if fine_sampling:
         if noise_fine is None:
             noise_fine = torch.linspace(0.0, 1.0, steps=S, dtype=torch.float32, device=dev).expand(n, S)
-        u, ustride = _u_and_stride(noise_fine if noise_fine.dim() == 2 else noise_fine.reshape(-1, S), n, S, where, on=cam2world)
+        u, ustride = _u_and_stride(noise_fine if noise_fine.dim() == 2 else noise_fine.reshape(-1, S), n, S, where, cam2world)
     else:
         u, ustride = None, 0
     if ray_features is not None:
@@ -717,9 +732,7 @@ def render_fwd(cam2world, focal, height, width, num_samples, texels, decoder_ima
         if ray_features.numel() != n * RAY_FEATURE_PITCH:
             raise ValueError('ray_features must be [B,H,W,48], got %s' % (tuple(ray_features.shape),))
     _one_device(where, cam2world, workspace, profile_cycles, clock_probe)
-    with torch.cuda.device(dev):
-        _lib.call_struct(
-            'nfi_render_fwd', 'nfi_render_args', _stream(cam2world), n_scenes=B, height=height, width=width,
+    _launch('nfi_render_fwd', 'nfi_render_args', cam2world, n_scenes=B, height=height, width=width,
             n_samples=S, fine_sampling=int(fine_sampling), white_background=int(white_background),
             scene_range=float(scene_range), views_per_scene=V, cam2world=cam2world, focal=focal,
             bbox=bbox, center=center, texels=texels, plane_res=texel_res(texels),
@@ -804,10 +817,9 @@ def sdf_gradient_fwd(points, texels, w1, b1, w2, b2, scene_range):
     w1, b1, w2, b2 = _distance_head(w1, b1, w2, b2, points, where)
     sdf = torch.empty((B, P), dtype=torch.float32, device=points.device)
     grad = torch.empty((B, P, 3), dtype=torch.float32, device=points.device)
-    with torch.cuda.device(points.device):
-        _lib.call_struct('nfi_sdf_gradient_fwd', 'nfi_sdf_gradient_args', _stream(points), n_scenes=B, points_per_scene=P,
-                         points=points, texels=texels, plane_res=texel_res(texels), texel_layout=layout,
-                         scene_range=float(scene_range), w1=w1, b1=b1, w2=w2, b2=b2, sdf=sdf, gradient=grad)
+    _launch('nfi_sdf_gradient_fwd', 'nfi_sdf_gradient_args', points, n_scenes=B, points_per_scene=P, points=points,
+            texels=texels, plane_res=texel_res(texels), texel_layout=layout, scene_range=float(scene_range), w1=w1, b1=b1,
+            w2=w2, b2=b2, sdf=sdf, gradient=grad)
     return sdf, grad
 
 
@@ -840,12 +852,11 @@ def sdf_gradient_bwd(points, texels, w1, b1, w2, b2, scene_range, g_sdf, g_gradi
                 texel_layout=layout, scene_range=float(scene_range),
                 w1=w1, b1=b1, w2=w2, b2=b2, g_sdf=_f32c(g_sdf, 'g_sdf', points, B * P, where),
                 g_gradient=_f32c(g_gradient, 'g_gradient', points, 3 * B * P, where), **out)
-    with torch.cuda.device(dev):
-        if ordered:
-            _call_ordered('nfi_sdf_gradient_bwd_ordered', 'nfi_sdf_gradient_args', points, 'sdf_gradient_bwd(ordered=True): shape '
-                          'not supported (at most 2^25 points per scene): %s' % ((B, P, texel_res(texels)),), args)
-        else:
-            _lib.call_struct('nfi_sdf_gradient_bwd', 'nfi_sdf_gradient_args', _stream(points), **args)
+    if ordered:
+        _call_ordered('nfi_sdf_gradient_bwd_ordered', 'nfi_sdf_gradient_args', points,
+                      'sdf_gradient_bwd(ordered=True, at most 2^25 points per scene)', (B, P, texel_res(texels)), args)
+    else:
+        _launch('nfi_sdf_gradient_bwd', 'nfi_sdf_gradient_args', points, **args)
     return out
 
 
@@ -880,32 +891,21 @@ def composite_bwd_stash(ray_directions, stash_t, stash_sigma, stash_rgb, g_rgb_m
     if want_rd:
         out['g_ray_directions'] = torch.empty_like(rd)
     f4 = 4              # bytes per float: list b starts S entries into every row
-    with torch.cuda.device(rd.device):
-        _lib.call_struct('nfi_composite_bwd', 'nfi_composite_bwd_args', _stream(rd), n_rays=n, n_a=S, n_b=S,
-                         list_row_stride=S2, ray_directions=rd, depth_a=t, sigma_a=sg, rgb_a=col,
-                         depth_b=t.data_ptr() + S * f4, sigma_b=sg.data_ptr() + S * f4, rgb_b=col.data_ptr() + 3 * S * f4,
-                         n_extra=0, white_background=int(white_background), g_rgb_map=_f32c(g_rgb_map, 'g_rgb_map'),
-                         g_mask=_f32c(g_mask, 'g_mask'), g_sigma_a=out['g_sigma'], g_rgb_a=out['g_rgb'],
-                         g_sigma_b=out['g_sigma'].data_ptr() + S * f4, g_rgb_b=out['g_rgb'].data_ptr() + 3 * S * f4,
-                         g_ray_directions=out.get('g_ray_directions'))
+    _launch('nfi_composite_bwd', 'nfi_composite_bwd_args', rd, n_rays=n, n_a=S, n_b=S, list_row_stride=S2,
+            ray_directions=rd, depth_a=t, sigma_a=sg, rgb_a=col, depth_b=t.data_ptr() + S * f4,
+            sigma_b=sg.data_ptr() + S * f4, rgb_b=col.data_ptr() + 3 * S * f4, n_extra=0,
+            white_background=int(white_background), g_rgb_map=g_rgb_map, g_mask=g_mask, g_sigma_a=out['g_sigma'],
+            g_rgb_a=out['g_rgb'], g_sigma_b=out['g_sigma'].data_ptr() + S * f4,
+            g_rgb_b=out['g_rgb'].data_ptr() + 3 * S * f4, g_ray_directions=out.get('g_ray_directions'))
     return out
 
 
 def composite_bwd(ray_directions, depth_a, sigma_a, rgb_a, g_rgb_map, g_mask=None, depth_b=None, sigma_b=None,
                   rgb_b=None, extra_a=None, extra_b=None, g_extra_map=None, white_background=True, want_rd=True):
-    rd = _f32c(ray_directions, 'ray_directions')
-    depth_a, sigma_a, rgb_a = _f32c(depth_a, 'depth'), _f32c(sigma_a, 'sigma'), _f32c(rgb_a, 'rgb')
-    na = depth_a.shape[-1]
-    nb = 0
-    if depth_b is not None:
-        depth_b, sigma_b, rgb_b = _f32c(depth_b, 'depth_b'), _f32c(sigma_b, 'sigma_b'), _f32c(rgb_b, 'rgb_b')
-        nb = depth_b.shape[-1]
-    n_extra = 0
-    if extra_a is not None and g_extra_map is not None:
-        extra_a, extra_b = _f32c(extra_a, 'extra_a'), _f32c(extra_b, 'extra_b') if nb else None
-        n_extra = extra_a.shape[-1]
-    n = _check_lists('composite_bwd', rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a if n_extra else None,
-                     extra_b if n_extra and nb else None)
+    # (the extras count only where their map has a gradient)
+    (n, na, nb, n_extra), (rd, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b, extra_a, extra_b) = _lists(
+        'composite_bwd', ray_directions, depth_a, sigma_a, rgb_a, depth_b, sigma_b, rgb_b,
+        extra_a if g_extra_map is not None else None, extra_b)
     g_rgb_map, g_mask = _f32c(g_rgb_map, 'g_rgb_map', rd, where='composite_bwd'), _f32c(g_mask, 'g_mask', rd, where='composite_bwd')
     g_extra_map = _f32c(g_extra_map, 'g_extra_map', rd, where='composite_bwd') if n_extra else None
     _need(g_rgb_map, n, (3,), 'g_rgb_map', 'composite_bwd')
@@ -922,13 +922,10 @@ def composite_bwd(ray_directions, depth_a, sigma_a, rgb_a, g_rgb_map, g_mask=Non
             out['g_extra_b'] = torch.empty_like(extra_b)
     if want_rd:
         out['g_ray_directions'] = torch.empty_like(rd)
-    with torch.cuda.device(rd.device):
-        _lib.call_struct('nfi_composite_bwd', 'nfi_composite_bwd_args', _stream(rd), n_rays=n, n_a=na, n_b=nb,
-                         ray_directions=rd, depth_a=depth_a, sigma_a=sigma_a, rgb_a=rgb_a, depth_b=depth_b,
-                         sigma_b=sigma_b, rgb_b=rgb_b, n_extra=n_extra, extra_a=extra_a if n_extra else None,
-                         extra_b=extra_b if n_extra else None, white_background=int(white_background),
-                         g_rgb_map=_f32c(g_rgb_map, 'g_rgb_map'), g_mask=_f32c(g_mask, 'g_mask'),
-                         g_extra_map=_f32c(g_extra_map, 'g_extra_map') if n_extra else None, **out)
+    _launch('nfi_composite_bwd', 'nfi_composite_bwd_args', rd, n_rays=n, n_a=na, n_b=nb, ray_directions=rd, depth_a=depth_a,
+            sigma_a=sigma_a, rgb_a=rgb_a, depth_b=depth_b, sigma_b=sigma_b, rgb_b=rgb_b, n_extra=n_extra, extra_a=extra_a,
+            extra_b=extra_b, white_background=int(white_background), g_rgb_map=g_rgb_map, g_mask=g_mask,
+            g_extra_map=g_extra_map, **out)
     return out
 
 
@@ -940,10 +937,7 @@ def points_bwd(g_points, depth, want_ro=True, want_rd=True):
     shape = depth.shape[:-1]
     g_ro = torch.empty((*shape, 3), dtype=torch.float32, device=depth.device) if want_ro else None
     g_rd = torch.empty((*shape, 3), dtype=torch.float32, device=depth.device) if want_rd else None
-    lib = _lib.load()
-    with torch.cuda.device(depth.device):
-        _lib.check(lib.nfi_points_bwd(_lib.ptr(g_points), _lib.ptr(depth), n, S, _lib.ptr(g_ro), _lib.ptr(g_rd),
-                                      _stream(depth)), 'nfi_points_bwd')
+    _launch_positional('nfi_points_bwd', depth, g_points, depth, n, S, g_ro, g_rd)
     return g_ro, g_rd
 
 
@@ -956,14 +950,9 @@ def raygen_bwd(height, width, focal, cam2world, bbox, center, normalize, g_ro, g
     g_ro, g_rd = _f32c(g_ro, 'g_ro', cam2world, n3, 'raygen_bwd'), _f32c(g_rd, 'g_rd', cam2world, n3, 'raygen_bwd')
     g_cam = torch.empty((B, 4, 4), dtype=torch.float32, device=cam2world.device)
     g_focal = torch.empty((B,), dtype=torch.float32, device=cam2world.device) if focal is not None else None
-    lib = _lib.load()
-    a = _lib.make_args('nfi_raygen_args', n_scenes=B, height=height, width=width, cam2world=cam2world, focal=focal,
-                       bbox=bbox, center=center, normalize=int(normalize))
-    import ctypes
-    with torch.cuda.device(cam2world.device):
-        name = 'nfi_raygen_bwd_ordered' if ordered else 'nfi_raygen_bwd'
-        _lib.check(getattr(lib, name)(ctypes.byref(a), _lib.ptr(g_ro), _lib.ptr(g_rd),
-                                      _lib.ptr(g_cam), _lib.ptr(g_focal), _stream(cam2world)), name)
+    _launch('nfi_raygen_bwd_ordered' if ordered else 'nfi_raygen_bwd', 'nfi_raygen_args', cam2world, g_ro, g_rd, g_cam, g_focal,
+            n_scenes=B, height=height, width=width, cam2world=cam2world, focal=focal, bbox=bbox, center=center,
+            normalize=int(normalize))
     return g_cam, g_focal
 
 
@@ -986,9 +975,8 @@ def affine_warp(img, rot, scale, translation, white_background=False):
     if img.dim() != 4:
         raise ValueError('affine_warp: img must be [N,C,H,W]')
     out = torch.empty_like(img)
-    with torch.cuda.device(img.device):
-        _lib.call_struct('nfi_affine_warp_fwd', 'nfi_warp_args', _stream(img), image=img, warped=out,
-                         **_warp_args(img, rot, scale, translation, white_background))
+    _launch('nfi_affine_warp_fwd', 'nfi_warp_args', img, image=img, warped=out,
+            **_warp_args(img, rot, scale, translation, white_background))
     return out
 
 
@@ -1000,22 +988,19 @@ def affine_warp_bwd(g_out, rot, scale, translation, white_background=False, orde
     if g_out.dim() != 4:
         raise ValueError('affine_warp_bwd: g_out must be [N,C,H,W]')
     g_img = torch.empty_like(g_out)
-    with torch.cuda.device(g_out.device):
-        _lib.call_struct('nfi_affine_warp_bwd_ordered' if ordered else 'nfi_affine_warp_bwd', 'nfi_warp_args', _stream(g_out), g_warped=g_out, g_image=g_img,
-                         **_warp_args(g_out, rot, scale, translation, white_background))
+    _launch('nfi_affine_warp_bwd_ordered' if ordered else 'nfi_affine_warp_bwd', 'nfi_warp_args', g_out, g_warped=g_out,
+            g_image=g_img, **_warp_args(g_out, rot, scale, translation, white_background))
     return g_img
 
 
-def _range_flag(check_range, flag, dev):
+def _range_flag(check_range, flag, on, where):
     """The out_of_range word of a metrics call: None, a fresh int32 [1], or the caller's own (one element of a tensor that
-    gathers the flags of several calls, so that they reach the host in one read)."""
+    gathers the flags of several calls, so that they reach the host in one read) - written where it is, never copied."""
     if not check_range:
         return None
     if flag is None:
-        return torch.empty((1,), dtype=torch.int32, device=dev)
-    if not flag.is_cuda or flag.device != dev or flag.dtype != torch.int32 or flag.numel() != 1:
-        raise ValueError('out_of_range must be one int32 element on %s' % (dev,))
-    return flag
+        return torch.empty((1,), dtype=torch.int32, device=on.device)
+    return _refuse(flag, 'out_of_range', on, 1, where, dtypes=(torch.int32,))
 
 
 def image_metrics(pred=None, target=None, mask_pred=None, mask_real=None, check_range=True, out_of_range=None):
@@ -1041,29 +1026,15 @@ def image_metrics(pred=None, target=None, mask_pred=None, mask_real=None, check_
             raise ValueError('image_metrics: mask shapes %s vs %s' % (tuple(mask_pred.shape), tuple(mask_real.shape)))
         iou = torch.empty((b,), dtype=torch.float32, device=dev)
         kw.update(mask_pred=mask_pred, mask_real=mask_real, elements_per_mask=mask_pred.numel() // b, iou=iou)
-    flag = _range_flag(check_range, out_of_range, dev)
+    flag = _range_flag(check_range, out_of_range, first, 'image_metrics')
     if flag is not None:
         kw['out_of_range'] = flag
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_image_metrics', 'nfi_metrics_args', _stream(first), **kw)
+    _launch('nfi_image_metrics', 'nfi_metrics_args', first, **kw)
     return psnr, iou, flag
 
 
 SSIM_BCHW = 0      # dense [B,3,H,W]
 SSIM_BHWC = 1      # dense [B,H,W,3], seen as [B,3,H,W] through permute(0,3,1,2)
-
-
-def _ssim_input(t, name):
-    """(tensor the kernel reads, its layout): t itself if it is dense in either layout, else a contiguous copy."""
-    if not t.is_cuda:
-        raise RuntimeError('%s must live on the GPU (no CPU path in nerf_from_image_amd)' % name)
-    if t.dtype != torch.float32:
-        raise TypeError('%s must be float32, got %s' % (name, t.dtype))
-    if t.is_contiguous():
-        return t, SSIM_BCHW
-    if t.permute(0, 2, 3, 1).is_contiguous():
-        return t, SSIM_BHWC
-    return t.contiguous(), SSIM_BCHW
 
 
 def image_ssim(pred, target, want_map=False, check_range=True, out_of_range=None):
@@ -1075,21 +1046,17 @@ def image_ssim(pred, target, want_map=False, check_range=True, out_of_range=None
     b, _, h, w = pred.shape
     if b < 1 or h < 7 or w < 7:
         raise ValueError('image_ssim: %d images of %d x %d: at least one image and one 7 x 7 window are needed' % (b, h, w))
-    pred, pred_layout = _ssim_input(pred, 'pred')
-    target, target_layout = _ssim_input(target, 'target')
+    pred, pred_layout = _nchw_or_nhwc(_refuse(pred, 'pred'))
+    target, target_layout = _nchw_or_nhwc(_refuse(target, 'target', pred, where='image_ssim'))
     dev = pred.device
     ssim = torch.empty((b,), dtype=torch.float32, device=dev)
     ssim_map = torch.empty((b, 3, h - 6, w - 6), dtype=torch.float32, device=dev) if want_map else None
-    flag = _range_flag(check_range, out_of_range, dev)
+    flag = _range_flag(check_range, out_of_range, pred, 'image_ssim')
     kw = dict(n_images=b, height=h, width=w)
-    n_ws = _lib.struct_query('nfi_image_ssim_workspace_bytes', 'nfi_ssim_args', **kw)
-    if n_ws == 0:
-        raise RuntimeError('image_ssim: shape not supported: %s' % ((b, h, w),))
-    ws = torch.empty((n_ws,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_image_ssim', 'nfi_ssim_args', _stream(pred), pred=pred, pred_layout=pred_layout, target=target,
-                         target_layout=target_layout, ssim=ssim, ssim_map=ssim_map, out_of_range=flag, workspace=ws,
-                         workspace_bytes=n_ws, **kw)
+    ws = _workspace(_lib.struct_query('nfi_image_ssim_workspace_bytes', 'nfi_ssim_args', **kw), pred, 'image_ssim', (b, h, w))
+    _launch('nfi_image_ssim', 'nfi_ssim_args', pred, pred=pred, pred_layout=pred_layout, target=target,
+            target_layout=target_layout, ssim=ssim, ssim_map=ssim_map, out_of_range=flag, workspace=ws,
+            workspace_bytes=ws.numel(), **kw)
     return ssim, ssim_map, flag
 
 
@@ -1105,10 +1072,7 @@ def separable_filter(image, radius, taps=None, sigma=0.0, background=0.0, flip=F
     device, used as given, or None: the kernel computes blur's own from sigma.  flip=True applies the taps reversed (the
     adjoint).  image is read in place if it is dense as [B,C,H,W] or as [B,H,W,C] behind a permute; anything else is
     copied.  One launch on the current stream."""
-    if not image.is_cuda:
-        raise RuntimeError('image must live on the GPU (no CPU path in nerf_from_image_amd)')
-    if image.dtype != torch.float32:
-        raise TypeError('image must be float32, got %s' % image.dtype)
+    _refuse(image, 'image')
     if image.dim() != 4 or image.numel() == 0:
         raise ValueError('separable_filter: image must be a non-empty [B,C,H,W], got %s' % (tuple(image.shape),))
     radius = int(radius)
@@ -1121,18 +1085,12 @@ def separable_filter(image, radius, taps=None, sigma=0.0, background=0.0, flip=F
         taps = _f32c(taps, 'taps')
         if taps.device != image.device or tuple(taps.shape) != (2 * radius + 1,):
             raise ValueError('separable_filter: taps must be [%d] on %s, got %s on %s' % (2 * radius + 1, image.device, tuple(taps.shape), taps.device))
-    if image.is_contiguous():
-        layout = FILTER_BCHW
-    elif image.permute(0, 2, 3, 1).is_contiguous():
-        layout = FILTER_BHWC
-    else:
-        image, layout = image.contiguous(), FILTER_BCHW
+    image, layout = _nchw_or_nhwc(image)
     b, c, h, w = image.shape
     out = torch.empty((b, c, h, w), dtype=torch.float32, device=image.device)
-    with torch.cuda.device(image.device):
-        _lib.call_struct('nfi_separable_filter', 'nfi_filter_args', _stream(image), n_images=b, channels=c, height=h, width=w,
-                         layout=layout, image=image, out=out, radius=radius, taps=taps, sigma=float(sigma),
-                         background=float(background), flip=int(bool(flip)))
+    _launch('nfi_separable_filter', 'nfi_filter_args', image, n_images=b, channels=c, height=h, width=w, layout=layout,
+            image=image, out=out, radius=radius, taps=taps, sigma=float(sigma), background=float(background),
+            flip=int(bool(flip)))
     return out
 
 
@@ -1164,16 +1122,11 @@ def lpips_head(x, y, weight, y_normalized=False, eps=1e-10, out=None, accumulate
         if accumulate:
             raise ValueError('lpips_head: accumulate=True needs the out tensor to add to')
         out = torch.empty((b,), dtype=torch.float32, device=x.device)
-    elif not (out.is_cuda and out.device == x.device and out.dtype == torch.float32 and tuple(out.shape) == (b,) and out.is_contiguous()):
+    elif tuple(_refuse(out, 'out', x, b, 'lpips_head').shape) != (b,) or not out.is_contiguous():      # (written where it is)
         raise ValueError('lpips_head: out must be a dense float32 [%d] on %s' % (b, x.device))
-    n_ws = _lib.struct_query('nfi_lpips_head_workspace_bytes', 'nfi_lpips_head_args', **kw)
-    if n_ws == 0:
-        raise RuntimeError('lpips_head: shape not supported: %s' % (tuple(x.shape),))
-    ws = torch.empty((n_ws,), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.call_struct('nfi_lpips_head_fwd', 'nfi_lpips_head_args', _stream(x), x=x, y=y, y_normalized=int(bool(y_normalized)),
-                         weight=weight, eps=float(eps), out=out, accumulate=int(bool(accumulate)), workspace=ws,
-                         workspace_bytes=n_ws, **kw)
+    ws = _workspace(_lib.struct_query('nfi_lpips_head_workspace_bytes', 'nfi_lpips_head_args', **kw), x, 'lpips_head', tuple(x.shape))
+    _launch('nfi_lpips_head_fwd', 'nfi_lpips_head_args', x, x=x, y=y, y_normalized=int(bool(y_normalized)), weight=weight,
+            eps=float(eps), out=out, accumulate=int(bool(accumulate)), workspace=ws, workspace_bytes=ws.numel(), **kw)
     return out
 
 
@@ -1189,9 +1142,8 @@ def lpips_head_bwd(g_out, x, y, weight, y_normalized=False, eps=1e-10, need_x=Tr
         raise ValueError('lpips_head_bwd: neither gradient is wanted')
     g_x = torch.empty_like(x) if need_x else None
     g_y = torch.empty_like(y) if need_y else None
-    with torch.cuda.device(x.device):
-        _lib.call_struct('nfi_lpips_head_bwd', 'nfi_lpips_head_args', _stream(x), x=x, y=y, y_normalized=int(bool(y_normalized)),
-                         weight=weight, eps=float(eps), g_out=g_out, g_x=g_x, g_y=g_y, **kw)
+    _launch('nfi_lpips_head_bwd', 'nfi_lpips_head_args', x, x=x, y=y, y_normalized=int(bool(y_normalized)), weight=weight,
+            eps=float(eps), g_out=g_out, g_x=g_x, g_y=g_y, **kw)
     return g_x, g_y
 
 
@@ -1202,7 +1154,8 @@ def synth_tail_args(y, dcoefs, noise, bias, taps, act_gain, up, activate=True, s
     """The checked, dense arguments of nfi_synth_tail_args shared by the forward and the backward, as a dict.  A caller that
     runs both on the same tensors (synthesis.layer_tail) checks once and hands the dict to synth_tail_launch /
     synth_tail_bwd_launch."""
-    y, dcoefs, bias = _f32c(y, 'y'), _f32c(dcoefs, 'dcoefs'), _f32c(bias, 'bias')
+    y = _f32c(y, 'y')
+    dcoefs, bias = _f32c(dcoefs, 'dcoefs', y, where=where), _f32c(bias, 'bias', y, where=where)
     if y.dim() != 4 or y.numel() == 0 or y.shape[2] != y.shape[3]:
         raise ValueError('%s: y must be a non-empty square [B,C,N,N], got %s' % (where, tuple(y.shape)))
     b, c, n = y.shape[0], y.shape[1], y.shape[2]
@@ -1217,7 +1170,7 @@ def synth_tail_args(y, dcoefs, noise, bias, taps, act_gain, up, activate=True, s
         raise ValueError('%s: slope must not be negative, got %r' % (where, slope))
     shared = 0
     if noise is not None:
-        noise = _f32c(noise, 'noise')
+        noise = _f32c(noise, 'noise', y, where=where)
         if tuple(noise.shape) == (r, r):
             shared = 1
         elif tuple(noise.shape) != (b, 1, r, r):
@@ -1225,14 +1178,11 @@ def synth_tail_args(y, dcoefs, noise, bias, taps, act_gain, up, activate=True, s
     if up:
         if taps is None:
             raise ValueError('%s: an up layer needs its resample_filter' % where)
-        taps = _f32c(taps, 'resample_filter')
+        taps = _f32c(taps, 'resample_filter', y, where=where)
         if tuple(taps.shape) != (4, 4):
             raise ValueError('%s: resample_filter must be [4,4], got %s' % (where, tuple(taps.shape)))
     else:
         taps = None
-    for t, name in ((dcoefs, 'dcoefs'), (bias, 'bias'), (noise, 'noise'), (taps, 'resample_filter')):
-        if t is not None and t.device != y.device:
-            raise ValueError('%s: %s lives on %s, y on %s' % (where, name, t.device, y.device))
     kw = dict(batch=b, channels=c, resolution=r, in_size=n, up=int(bool(up)), activate=int(bool(activate)), act_gain=float(act_gain),
               slope=float(slope), y=y, dcoefs=dcoefs, bias=bias, taps=taps, noise=noise, noise_shared=shared)
     return kw
@@ -1256,8 +1206,7 @@ def synth_tail_launch(kw):
     """synth_tail on arguments synth_tail_args has checked."""
     r = kw['resolution']
     out = torch.empty((kw['batch'], kw['channels'], r, r), dtype=torch.float32, device=kw['y'].device)
-    with torch.cuda.device(out.device):
-        _lib.call_struct('nfi_synth_tail_fwd', 'nfi_synth_tail_args', _stream(out), out=out, **kw)
+    _launch('nfi_synth_tail_fwd', 'nfi_synth_tail_args', out, out=out, **kw)
     return out
 
 
@@ -1268,10 +1217,10 @@ def synth_tail_bwd(g_out, out, y, dcoefs, noise, bias, resample_filter, act_gain
     g_noise (noise's shape) were asked for.  Every sum runs in a fixed order (no atomics): the same bits on every call."""
     kw = synth_tail_args(y, dcoefs, noise, bias, resample_filter, act_gain, up, activate, slope, 'synth_tail_bwd')
     b, c, r = kw['batch'], kw['channels'], kw['resolution']
-    g_out, out = _f32c(g_out, 'g_out'), _f32c(out, 'out')
-    if tuple(g_out.shape) != (b, c, r, r) or tuple(out.shape) != (b, c, r, r) or g_out.device != out.device or out.device != kw['y'].device:
-        raise ValueError('synth_tail_bwd: g_out and out must be [%d,%d,%d,%d] on %s, got %s and %s' % (
-            b, c, r, r, kw['y'].device, tuple(g_out.shape), tuple(out.shape)))
+    g_out, out = _f32c(g_out, 'g_out', kw['y'], where='synth_tail_bwd'), _f32c(out, 'out', kw['y'], where='synth_tail_bwd')
+    if tuple(g_out.shape) != (b, c, r, r) or tuple(out.shape) != (b, c, r, r):
+        raise ValueError('synth_tail_bwd: g_out and out must be [%d,%d,%d,%d], got %s and %s' % (
+            b, c, r, r, tuple(g_out.shape), tuple(out.shape)))
     if need_noise and noise is None:
         raise ValueError('synth_tail_bwd: need_noise without a noise input')
     if not (need_y or need_dcoefs or need_bias or need_noise):
@@ -1295,28 +1244,21 @@ def synth_tail_bwd_launch(kw, g_out, out, need_y, need_dcoefs, need_bias, need_n
     ws, n_ws = None, 0
     if need_dcoefs or need_bias:
         n_ws = _synth_tail_workspace_bytes(b, c, r, kw['up'])
-        if n_ws == 0:
-            raise RuntimeError('synth_tail_bwd: shape not supported: %s' % (tuple(kw['y'].shape),))
-        ws = torch.empty((n_ws // 8,), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_synth_tail_bwd', 'nfi_synth_tail_args', _stream(out), out=out, g_out=g_out, workspace=ws,
-                         workspace_bytes=n_ws, **dict(kw, **res))
+        ws = _workspace(n_ws, out, 'synth_tail_bwd', kw['y'].shape, torch.float64)
+    _launch('nfi_synth_tail_bwd', 'nfi_synth_tail_args', out, out=out, g_out=g_out, workspace=ws, workspace_bytes=n_ws,
+            **dict(kw, **res))
     return res
 
 
 # --------------------------------------------------------------------------- #
 # head of a synthesis layer (models/stylegan.py:173-177, 127-130, 132, 373; csrc/nfi_synth_head.inc).  The kernels read
 # single floats through every pointer but the modulation's planes, and those they test themselves (16-byte accesses where
-# the pointers allow it): nothing here is copied for its alignment.  The functions that hand pointers to the library are
-# private (_synth_head_launch ...): they take what synth_head_args / synth_modulate_args have checked.
+# the pointers allow it): nothing here is copied for its alignment.
 # --------------------------------------------------------------------------- #
 def _latent_rows(latent, where):
     """latent as float32 [B,D] on the GPU whose rows the kernel can read in place: unit stride along d and rows at least D
     apart (a layer's ws.unbind(1)[k]); any other view is copied."""
-    if not latent.is_cuda:
-        raise RuntimeError('%s: latent must live on the GPU (no CPU path in nerf_from_image_amd)' % where)
-    if latent.dtype != torch.float32:
-        raise TypeError('%s: latent must be float32, got %s' % (where, latent.dtype))
+    _refuse(latent, 'latent')
     if latent.dim() != 2 or latent.numel() == 0:
         raise ValueError('%s: latent must be a non-empty [B,D], got %s' % (where, tuple(latent.shape)))
     b, d = latent.shape
@@ -1354,17 +1296,18 @@ def _synth_head_workspace_bytes(b, d, stride, i, o, k, demodulate):
                              in_channels=i, out_channels=o, taps=k, demodulate=demodulate)
 
 
-def _synth_head_launch(kw):
+def synth_head_launch(kw):
+    """synth_head on arguments synth_head_args has checked."""
     dev = kw['latent'].device
     styles = torch.empty((kw['batch'], kw['in_channels']), dtype=torch.float32, device=dev)
     dcoefs = torch.empty((kw['batch'], kw['out_channels']), dtype=torch.float32, device=dev) if kw['demodulate'] else None
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_synth_head_fwd', 'nfi_synth_head_args', _stream(styles), styles=styles, dcoefs=dcoefs, **kw)
+    _launch('nfi_synth_head_fwd', 'nfi_synth_head_args', styles, styles=styles, dcoefs=dcoefs, **kw)
     return styles, dcoefs
 
 
-def _synth_head_bwd_launch(kw, g_styles, g_dcoefs, styles, dcoefs, need_latent, need_affine_weight, need_affine_bias, need_weight):
-    """g_styles / g_dcoefs / styles / dcoefs: dense float32 [B,I] / [B,O] on the device of kw['latent'], or None."""
+def synth_head_bwd_launch(kw, g_styles, g_dcoefs, styles, dcoefs, need_latent, need_affine_weight, need_affine_bias, need_weight):
+    """synth_head_bwd on arguments synth_head_args has checked; g_styles / g_dcoefs / styles / dcoefs: dense float32 [B,I] /
+    [B,O] on the device of kw['latent'], or None."""
     b, d, i, o, k = (kw[n] for n in ('batch', 'latent_dim', 'in_channels', 'out_channels', 'taps'))
     dev = kw['latent'].device
     res = {}
@@ -1377,12 +1320,9 @@ def _synth_head_bwd_launch(kw, g_styles, g_dcoefs, styles, dcoefs, need_latent, 
     if need_weight:
         res['g_weight'] = torch.empty((o, i, k), dtype=torch.float32, device=dev)
     n_ws = _synth_head_workspace_bytes(b, d, kw['latent_stride'], i, o, k, kw['demodulate'])
-    if n_ws == 0:
-        raise RuntimeError('synth_head_bwd: shape not supported: B %d, D %d, I %d, O %d, K %d' % (b, d, i, o, k))
-    ws = torch.empty((n_ws // 8,), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_synth_head_bwd', 'nfi_synth_head_args', _stream(ws), styles=styles, dcoefs=dcoefs, g_styles=g_styles,
-                         g_dcoefs=g_dcoefs, workspace=ws, workspace_bytes=n_ws, **dict(kw, **res))
+    ws = _workspace(n_ws, kw['latent'], 'synth_head_bwd (B, D, I, O, K)', (b, d, i, o, k), torch.float64)
+    _launch('nfi_synth_head_bwd', 'nfi_synth_head_args', ws, styles=styles, dcoefs=dcoefs, g_styles=g_styles, g_dcoefs=g_dcoefs,
+            workspace=ws, workspace_bytes=n_ws, **dict(kw, **res))
     return res
 
 
@@ -1390,7 +1330,7 @@ def synth_head(latent, affine_weight, affine_bias, weight_gain, bias_gain, conv_
     """What a synthesis layer does before its convolution, up to the modulation (models/stylegan.py:173-177, 127-130; 373 for
     toRGB): (styles [B,I], dcoefs [B,O] or None without demodulate).  Two launches, one without demodulate; the [B,O,I,kh,kw]
     product of the reference is never formed."""
-    return _synth_head_launch(synth_head_args(latent, affine_weight, affine_bias, weight_gain, bias_gain, conv_weight, demodulate, style_gain))
+    return synth_head_launch(synth_head_args(latent, affine_weight, affine_bias, weight_gain, bias_gain, conv_weight, demodulate, style_gain))
 
 
 def synth_head_bwd(g_styles, g_dcoefs, styles, dcoefs, latent, affine_weight, affine_bias, weight_gain, bias_gain, conv_weight,
@@ -1415,8 +1355,8 @@ def synth_head_bwd(g_styles, g_dcoefs, styles, dcoefs, latent, affine_weight, af
         raise ValueError('%s: need_weight without g_dcoefs (g_weight is the demodulation\'s share only)' % where)
     if not (need_latent or need_affine_weight or need_affine_bias or need_weight):
         raise ValueError('%s: no gradient is wanted' % where)
-    return _synth_head_bwd_launch(kw, g_styles, g_dcoefs, styles, dcoefs, bool(need_latent), bool(need_affine_weight), need_affine_bias,
-                                  bool(need_weight))
+    return synth_head_bwd_launch(kw, g_styles, g_dcoefs, styles, dcoefs, bool(need_latent), bool(need_affine_weight), need_affine_bias,
+                                 bool(need_weight))
 
 
 def synth_modulate_args(x, styles, where='synth_modulate'):
@@ -1429,26 +1369,25 @@ def synth_modulate_args(x, styles, where='synth_modulate'):
     return dict(batch=b, channels=c, plane=x.numel() // (b * c), x=x, styles=styles)
 
 
-def _synth_modulate_launch(kw):
+def synth_modulate_launch(kw):
+    """synth_modulate on arguments synth_modulate_args has checked."""
     out = torch.empty_like(kw['x'])
-    with torch.cuda.device(out.device):
-        _lib.call_struct('nfi_synth_modulate_fwd', 'nfi_synth_modulate_args', _stream(out), out=out, **kw)
+    _launch('nfi_synth_modulate_fwd', 'nfi_synth_modulate_args', out, out=out, **kw)
     return out
 
 
-def _synth_modulate_bwd_launch(kw, g_out, need_x, need_styles):
-    """g_out: dense float32, x's shape and device."""
+def synth_modulate_bwd_launch(kw, g_out, need_x, need_styles):
+    """synth_modulate_bwd on arguments synth_modulate_args has checked; g_out: dense float32, x's shape and device."""
     g_x = torch.empty_like(kw['x']) if need_x else None
     g_styles = torch.empty((kw['batch'], kw['channels']), dtype=torch.float32, device=g_out.device) if need_styles else None
-    with torch.cuda.device(g_out.device):
-        _lib.call_struct('nfi_synth_modulate_bwd', 'nfi_synth_modulate_args', _stream(g_out), g_out=g_out, g_x=g_x, g_styles=g_styles, **kw)
+    _launch('nfi_synth_modulate_bwd', 'nfi_synth_modulate_args', g_out, g_out=g_out, g_x=g_x, g_styles=g_styles, **kw)
     return g_x, g_styles
 
 
 def synth_modulate(x, styles):
     """x * styles.reshape(B, -1, 1, 1) (models/stylegan.py:132): x [B,C,H,W] (any trailing shape), styles [B,C] -> x's shape,
     dense.  One launch."""
-    return _synth_modulate_launch(synth_modulate_args(x, styles))
+    return synth_modulate_launch(synth_modulate_args(x, styles))
 
 
 def synth_modulate_bwd(g_out, x, styles, need_x=True, need_styles=True):
@@ -1461,15 +1400,16 @@ def synth_modulate_bwd(g_out, x, styles, need_x=True, need_styles=True):
         raise ValueError('%s: g_out must have x\'s shape %s, got %s' % (where, tuple(kw['x'].shape), tuple(g_out.shape)))
     if not (need_x or need_styles):
         raise ValueError('%s: no gradient is wanted' % where)
-    return _synth_modulate_bwd_launch(kw, g_out, bool(need_x), bool(need_styles))
+    return synth_modulate_bwd_launch(kw, g_out, bool(need_x), bool(need_styles))
 
 
 # --------------------------------------------------------------------------- #
 # pose algebra of the inversion loop (lib/pose_utils.py; csrc/nfi_pose.inc): thread = image, one launch per call
 # --------------------------------------------------------------------------- #
-def _pose_rows(t, tail, name, b=None):
-    """t as dense float32 [B, *tail] on the GPU (B = its own, or the given one)."""
-    t = _f32c(t, name, align=4)              # (nfi_pose.inc: one thread per image, float loads and stores only)
+def _pose_rows(t, tail, name, on=None):
+    """t as dense float32 [B, *tail] on the GPU; on: the call's first tensor - t then has its B and lives on its device."""
+    t = _f32c(t, name, on, align=4)          # (nfi_pose.inc: one thread per image, float loads and stores only)
+    b = None if on is None else on.shape[0]
     if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or t.shape[0] < 1 or (b is not None and t.shape[0] != b):
         raise ValueError('%s must be [%s], got %s' % (name, ', '.join(['B' if b is None else str(b)] + [str(v) for v in tail]),
                                                       tuple(t.shape)))
@@ -1478,8 +1418,7 @@ def _pose_rows(t, tail, name, b=None):
 
 def _pose_params(q, t2, s, z0):
     q = _pose_rows(q, (4,), 'q')
-    b = q.shape[0]
-    return q, _pose_rows(t2, (2,), 't2', b), _pose_rows(s, (), 's', b), None if z0 is None else _pose_rows(z0, (), 'z0', b)
+    return q, _pose_rows(t2, (2,), 't2', q), _pose_rows(s, (), 's', q), None if z0 is None else _pose_rows(z0, (), 'z0', q)
 
 
 def pose_to_matrix(q, t2, s, z0=None, camera_flipped=False, normalize_q=False):
@@ -1489,9 +1428,8 @@ def pose_to_matrix(q, t2, s, z0=None, camera_flipped=False, normalize_q=False):
     b, dev = q.shape[0], q.device
     cam2world = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
     focal = None if z0 is None else torch.empty((b,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_pose_to_matrix_fwd', 'nfi_pose_args', _stream(q), n_images=b, camera_flipped=int(bool(camera_flipped)),
-                         normalize_q=int(bool(normalize_q)), q=q, t2=t2, s=s, z0=z0, cam2world=cam2world, focal=focal)
+    _launch('nfi_pose_to_matrix_fwd', 'nfi_pose_args', q, n_images=b, camera_flipped=int(bool(camera_flipped)),
+            normalize_q=int(bool(normalize_q)), q=q, t2=t2, s=s, z0=z0, cam2world=cam2world, focal=focal)
     return cam2world, focal
 
 
@@ -1500,16 +1438,14 @@ def pose_to_matrix_bwd(g_cam2world, g_focal, q, t2, s, z0=None, camera_flipped=F
     """Gradients (g_q, g_t2, g_s, g_z0) of the above from g_cam2world [B,4,4] and g_focal [B] or None; needs: which of the
     four to compute (the others, and g_z0 without z0, are None)."""
     q, t2, s, z0 = _pose_params(q, t2, s, z0)
-    b, dev = q.shape[0], q.device
-    g_cam2world = _pose_rows(g_cam2world, (4, 4), 'g_cam2world', b)
-    g_focal = None if g_focal is None or z0 is None else _pose_rows(g_focal, (), 'g_focal', b)
+    g_cam2world = _pose_rows(g_cam2world, (4, 4), 'g_cam2world', q)
+    g_focal = None if g_focal is None or z0 is None else _pose_rows(g_focal, (), 'g_focal', q)
     needs = tuple(needs[:3]) + (needs[3] and z0 is not None,)
     outs = [torch.empty_like(t) if need else None for t, need in zip((q, t2, s, z0), needs)]
     if any(needs):
-        with torch.cuda.device(dev):
-            _lib.call_struct('nfi_pose_to_matrix_bwd', 'nfi_pose_args', _stream(q), n_images=b, camera_flipped=int(bool(camera_flipped)),
-                             normalize_q=int(bool(normalize_q)), q=q, t2=t2, s=s, z0=z0, g_cam2world=g_cam2world, g_focal=g_focal,
-                             g_q=outs[0], g_t2=outs[1], g_s=outs[2], g_z0=outs[3])
+        _launch('nfi_pose_to_matrix_bwd', 'nfi_pose_args', q, n_images=q.shape[0], camera_flipped=int(bool(camera_flipped)),
+                normalize_q=int(bool(normalize_q)), q=q, t2=t2, s=s, z0=z0, g_cam2world=g_cam2world, g_focal=g_focal,
+                g_q=outs[0], g_t2=outs[1], g_s=outs[2], g_z0=outs[3])
     return tuple(outs)
 
 
@@ -1518,16 +1454,15 @@ def matrix_to_pose(cam2world, focal=None, camera_flipped=False, want_pose=True, 
     None without want_pose, the last without want_cond."""
     cam2world = _pose_rows(cam2world, (4, 4), 'cam2world')
     b, dev = cam2world.shape[0], cam2world.device
-    focal = None if focal is None else _pose_rows(focal, (), 'focal', b)
+    focal = None if focal is None else _pose_rows(focal, (), 'focal', cam2world)
 
     def new(*shape):
         return torch.empty(shape, dtype=torch.float32, device=dev)
     z0 = new(b) if want_pose and focal is not None else None
     t2, s, q = (new(b, 2), new(b), new(b, 4)) if want_pose else (None, None, None)
     cond = new(b, 13) if want_cond else None
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_matrix_to_pose', 'nfi_matrix_to_pose_args', _stream(cam2world), n_images=b,
-                         camera_flipped=int(bool(camera_flipped)), cam2world=cam2world, focal=focal, z0=z0, t2=t2, s=s, q=q, cond=cond)
+    _launch('nfi_matrix_to_pose', 'nfi_matrix_to_pose_args', cam2world, n_images=b, camera_flipped=int(bool(camera_flipped)),
+            cam2world=cam2world, focal=focal, z0=z0, t2=t2, s=s, q=q, cond=cond)
     return z0, t2, s, q, cond
 
 
@@ -1537,11 +1472,9 @@ def rotation_distance(p, q):
     if dim not in (3, 4):
         raise ValueError('rotation_distance: [B,3,3] or [B,4,4] matrices, got %s' % (tuple(p.shape),))
     p = _pose_rows(p, (dim, dim), 'p')
-    q = _pose_rows(q, (dim, dim), 'q', p.shape[0])
+    q = _pose_rows(q, (dim, dim), 'q', p)
     degrees = torch.empty((p.shape[0],), dtype=torch.float32, device=p.device)
-    with torch.cuda.device(p.device):
-        _lib.call_struct('nfi_rotation_distance', 'nfi_rotation_distance_args', _stream(p), n_images=p.shape[0], dim=dim, p=p, q=q,
-                         degrees=degrees)
+    _launch('nfi_rotation_distance', 'nfi_rotation_distance_args', p, n_images=p.shape[0], dim=dim, p=p, q=q, degrees=degrees)
     return degrees
 
 
@@ -1550,11 +1483,10 @@ def pose_nearest_by_angle(cam2world, target):
     closest to target [N] degrees (the lowest index on a tie)."""
     cam2world = _pose_rows(cam2world, (4, 4), 'cam2world')
     n = cam2world.shape[0]
-    target = _pose_rows(target, (), 'target', n)
+    target = _pose_rows(target, (), 'target', cam2world)
     index = torch.empty((n,), dtype=torch.int32, device=cam2world.device)
-    with torch.cuda.device(cam2world.device):
-        _lib.call_struct('nfi_pose_nearest_by_angle', 'nfi_pose_nearest_args', _stream(cam2world), n_images=n, cam2world=cam2world,
-                         target=target, index=index)
+    _launch('nfi_pose_nearest_by_angle', 'nfi_pose_nearest_args', cam2world, n_images=n, cam2world=cam2world, target=target,
+            index=index)
     return index
 
 
@@ -1562,10 +1494,9 @@ def pose_project_(q, s, z0=None):
     """run.py:2307-2310 in place on dense float32 tensors: q [B,4] normalised, s [B] made non-negative, z0 [B] (if given)
     clamped to [-4, 4]."""
     for t, tail, name in ((q, (4,), 'q'), (s, (), 's'), (z0, (), 'z0')):
-        if t is not None and _pose_rows(t, tail, name, None if t is q else q.shape[0]) is not t:
+        if t is not None and _pose_rows(t, tail, name, None if t is q else q) is not t:
             raise ValueError('pose_project_: %s must be contiguous to be changed in place' % name)
-    with torch.cuda.device(q.device):
-        _lib.call_struct('nfi_pose_project', 'nfi_pose_project_args', _stream(q), n_images=q.shape[0], q=q, s=s, z0=z0)
+    _launch('nfi_pose_project', 'nfi_pose_project_args', q, n_images=q.shape[0], q=q, s=s, z0=z0)
 
 
 # --------------------------------------------------------------------------- #
@@ -1588,9 +1519,8 @@ def torgb_texels(x, styles, weight, bias, previous_image=None):
             tuple(x.shape), tuple(styles.shape), tuple(weight.shape), tuple(bias.shape),
             None if prev is None else tuple(prev.shape)))
     out = torch.empty((B, 96, R, R), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    with torch.cuda.device(x.device):
-        _lib.call_struct('nfi_torgb_texels_fwd', 'nfi_torgb_args', _stream(x), n_scenes=B, in_channels=Cin, resolution=R,
-                         x=x, styles=styles, weight=weight, bias=bias, previous_image=prev, texels=out)
+    _launch('nfi_torgb_texels_fwd', 'nfi_torgb_args', x, n_scenes=B, in_channels=Cin, resolution=R, x=x, styles=styles,
+            weight=weight, bias=bias, previous_image=prev, texels=out)
     return out
 
 
@@ -1605,11 +1535,8 @@ def torgb_texels_bwd(g_out, x, styles, weight, previous_image=None, want_weight=
     B, Cin, R, _ = x.shape
     styles, weight = _f32c(styles, 'styles', x, B * Cin, where), _f32c(weight, 'weight', x, 96 * Cin, where)
     prev = _f32c(previous_image, 'previous_image', x, B * 96 * (R // 2) * (R // 2), where)
-    if not g_out.is_cuda or g_out.dtype != torch.float32:
-        raise TypeError('torgb_texels_bwd: g_out must be a float32 GPU tensor')
-    if tuple(g_out.shape) != (B, 96, R, R) or g_out.device != x.device:
-        raise ValueError('torgb_texels_bwd: g_out must be [%d,96,%d,%d] on %s, got %s on %s' % (
-            B, R, R, x.device, tuple(g_out.shape), g_out.device))
+    if tuple(_refuse(g_out, 'g_out', x, where=where).shape) != (B, 96, R, R):
+        raise ValueError('torgb_texels_bwd: g_out must be [%d,96,%d,%d], got %s' % (B, R, R, tuple(g_out.shape)))
     g = _dense_channels_last(g_out)
     dev = x.device
     out = {'g_x': torch.empty_like(x), 'g_styles': torch.empty((B, Cin), dtype=torch.float32, device=dev)}
@@ -1620,12 +1547,10 @@ def torgb_texels_bwd(g_out, x, styles, weight, previous_image=None, want_weight=
         out['g_previous_image'] = torch.empty_like(prev)
     args = dict(n_scenes=B, in_channels=Cin, resolution=R, x=x, styles=styles, weight=weight, previous_image=prev, g_texels=g,
                 **out)
-    with torch.cuda.device(dev):
-        if ordered:
-            _call_ordered('nfi_torgb_texels_bwd_ordered', 'nfi_torgb_args', x,
-                          'torgb_texels_bwd(ordered=True): shape not supported: %s' % ((B, Cin, R),), args)
-        else:
-            _lib.call_struct('nfi_torgb_texels_bwd', 'nfi_torgb_args', _stream(x), **args)
+    if ordered:
+        _call_ordered('nfi_torgb_texels_bwd_ordered', 'nfi_torgb_args', x, 'torgb_texels_bwd(ordered=True)', (B, Cin, R), args)
+    else:
+        _launch('nfi_torgb_texels_bwd', 'nfi_torgb_args', x, **args)
     return out
 
 
@@ -1650,7 +1575,7 @@ def _viewdir_mapper_inputs(viewdir, params):
             len(VIEWDIR_MAPPER_PARAMS), ', '.join(n for n, _ in VIEWDIR_MAPPER_PARAMS), len(params)))
     kw = {}
     for (name, shape), t in zip(VIEWDIR_MAPPER_PARAMS, params):
-        t = _f32c(t, name)
+        t = _f32c(t, name, viewdir, where='viewdir_mapper')
         if tuple(t.shape) != shape:
             raise ValueError('viewdir_mapper: %s must be %s, got %s' % (name, list(shape), tuple(t.shape)))
         kw[name] = t
@@ -1662,9 +1587,8 @@ def viewdir_mapper_fwd(viewdir, params):
     [...,32], one launch."""
     viewdir, kw = _viewdir_mapper_inputs(viewdir, params)
     feature = torch.empty(viewdir.shape[:-1] + (32,), dtype=torch.float32, device=viewdir.device)
-    with torch.cuda.device(viewdir.device):
-        _lib.call_struct('nfi_viewdir_mapper_fwd', 'nfi_viewdir_mapper_args', _stream(viewdir), n_rays=viewdir.numel() // 3,
-                         viewdir=viewdir, feature=feature, **kw)
+    _launch('nfi_viewdir_mapper_fwd', 'nfi_viewdir_mapper_args', viewdir, n_rays=viewdir.numel() // 3, viewdir=viewdir,
+            feature=feature, **kw)
     return feature
 
 
@@ -1674,26 +1598,17 @@ def viewdir_mapper_bwd(viewdir, params, g_feature, want_viewdir=True, into=None,
     then ADDED to its tensors (the accumulate contract of the C entry); otherwise fresh zeroed tensors are filled.
     want_params=False (a frozen mapper): only g_viewdir is computed, the parameter entries are None."""
     viewdir, kw = _viewdir_mapper_inputs(viewdir, params)
-    g_feature = _f32c(g_feature, 'g_feature')
-    if g_feature.data_ptr() % 16:
-        g_feature = g_feature.clone()              # the kernel reads rows as 16-byte vectors (a view at an odd storage offset)
-    if not want_params:
-        if not want_viewdir or into is not None:
-            raise ValueError('viewdir_mapper_bwd: want_params=False computes g_viewdir only')
-        if tuple(g_feature.shape) != tuple(viewdir.shape[:-1]) + (32,):
-            raise ValueError('g_feature must be %s, got %s' % (tuple(viewdir.shape[:-1]) + (32,), tuple(g_feature.shape)))
-        g_viewdir = torch.empty_like(viewdir)
-        with torch.cuda.device(viewdir.device):
-            _lib.call_struct('nfi_viewdir_mapper_bwd', 'nfi_viewdir_mapper_args', _stream(viewdir), n_rays=viewdir.numel() // 3,
-                             viewdir=viewdir, g_feature=g_feature, g_viewdir=g_viewdir, **kw)
-        out = {'g_' + name: None for name, _ in VIEWDIR_MAPPER_PARAMS}
-        out['g_viewdir'] = g_viewdir
-        return out
+    where = 'viewdir_mapper_bwd'
+    g_feature = _f32c(g_feature, 'g_feature', viewdir, where=where)      # (the kernel reads its rows as 16-byte vectors)
     if tuple(g_feature.shape) != tuple(viewdir.shape[:-1]) + (32,):
         raise ValueError('g_feature must be %s, got %s' % (tuple(viewdir.shape[:-1]) + (32,), tuple(g_feature.shape)))
     dev = viewdir.device
     out = {}
-    if into is None:
+    if not want_params:
+        if not want_viewdir or into is not None:
+            raise ValueError('viewdir_mapper_bwd: want_params=False computes g_viewdir only')
+        out = {'g_' + name: None for name, _ in VIEWDIR_MAPPER_PARAMS}           # (null pointers: not computed)
+    elif into is None:
         # one zero-fill for the 18 buffers: they are views of one flat tensor (23 392 floats)
         sizes = [math.prod(shape) for _, shape in VIEWDIR_MAPPER_PARAMS]
         flat = torch.zeros((sum(sizes),), dtype=torch.float32, device=dev)
@@ -1701,13 +1616,12 @@ def viewdir_mapper_bwd(viewdir, params, g_feature, want_viewdir=True, into=None,
             out['g_' + name] = part.view(shape)
     else:
         for name, shape in VIEWDIR_MAPPER_PARAMS:
-            t = into['g_' + name]
-            if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            t = _refuse(into['g_' + name], 'into[g_%s]' % name, viewdir, where=where)        # (added to where it is)
+            if tuple(t.shape) != shape or not t.is_contiguous():
                 raise ValueError('viewdir_mapper_bwd: into[g_%s] must be a contiguous float32 GPU tensor %s' % (name, list(shape)))
             out['g_' + name] = t
     g_viewdir = torch.empty_like(viewdir) if want_viewdir else None
-    with torch.cuda.device(dev):
-        _lib.call_struct('nfi_viewdir_mapper_bwd', 'nfi_viewdir_mapper_args', _stream(viewdir), n_rays=viewdir.numel() // 3,
-                         viewdir=viewdir, g_feature=g_feature, g_viewdir=g_viewdir, **kw, **out)
+    _launch('nfi_viewdir_mapper_bwd', 'nfi_viewdir_mapper_args', viewdir, n_rays=viewdir.numel() // 3, viewdir=viewdir,
+            g_feature=g_feature, g_viewdir=g_viewdir, **kw, **out)
     out['g_viewdir'] = g_viewdir
     return out

@@ -34,8 +34,6 @@ def compute_pose_pnp(coords, masks, focal_proposals, refine=True):
     """coords [B,H,W,3] canonical coordinates, masks [B,H,W] (bool, or float: foreground where > 0.5), focal_proposals:
     sequence / array / tensor of focal lengths.  Returns (world2cam [B,4,4], focal [B], errors [B]) float32 on the
     device: ``flip @ [R | t]`` per image for the best proposal, the reference's dummy pose where nothing solves."""
-    if not coords.is_cuda:
-        raise RuntimeError('compute_pose_pnp: coords must live on the GPU (no CPU path in nerf_from_image_amd)')
     coords = ops._f32c(coords.float(), 'coords')
     B, H, W, three = coords.shape
     if three != 3 or tuple(masks.shape) != (B, H, W):
@@ -46,16 +44,13 @@ def compute_pose_pnp(coords, masks, focal_proposals, refine=True):
     nf = focals.numel()
     if nf == 0:
         raise ValueError('compute_pose_pnp: no focal proposals')
-    lib = _lib.load()
-    ws = torch.empty((lib.nfi_pnp_workspace_bytes(B, nf) // 8,), dtype=torch.float64, device=coords.device)
+    ws = ops._workspace(_lib.load().nfi_pnp_workspace_bytes(B, nf), coords, 'compute_pose_pnp', (B, nf), torch.float64)
     world2cam = torch.empty((B, 4, 4), dtype=torch.float32, device=coords.device)
     focal = torch.empty((B,), dtype=torch.float32, device=coords.device)
     error = torch.empty((B,), dtype=torch.float32, device=coords.device)
-    with torch.cuda.device(coords.device):
-        _lib.call_struct('nfi_pose_pnp', 'nfi_pnp_args', ops._stream(coords), n_images=B, height=H, width=W, coords=coords,
-                         mask=mask, mask_threshold=0.5, n_focal=nf, focal_proposals=focals,
-                         refine_iterations=REFINE_ITERATIONS if refine else 0, workspace=ws, workspace_bytes=ws.numel() * 8,
-                         world2cam=world2cam, focal=focal, error=error)
+    ops._launch('nfi_pose_pnp', 'nfi_pnp_args', coords, n_images=B, height=H, width=W, coords=coords, mask=mask,
+                mask_threshold=0.5, n_focal=nf, focal_proposals=focals, refine_iterations=REFINE_ITERATIONS if refine else 0,
+                workspace=ws, workspace_bytes=ws.numel() * 8, world2cam=world2cam, focal=focal, error=error)
     return world2cam, focal, error
 
 

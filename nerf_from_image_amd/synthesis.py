@@ -41,9 +41,6 @@ def layer_tail(y, dcoefs, noise, bias, resample_filter, act_gain, up, activate=T
     """Differentiable fused tail: y [B,C,2n+1,2n+1] with up (R = 2n) or [B,C,R,R]; dcoefs [B,C]; noise None, [B,1,R,R] or
     [R,R]; bias [C]; resample_filter [4,4] (a buffer: no gradient) ->
     lrelu_slope(((noise + filter(y) * dcoefs) + bias) * act_gain), [B,C,R,R].  act_gain must be positive."""
-    for t, name in ((y, 'y'), (dcoefs, 'dcoefs'), (noise, 'noise'), (bias, 'bias')):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError('layer_tail: %s must live on the GPU (no CPU path in nerf_from_image_amd)' % name)
     # checked once: the node's forward and backward launch on these very tensors (dense float32 already, or made so here)
     kw = ops.synth_tail_args(y, dcoefs, noise, bias, resample_filter.detach() if up else None, float(act_gain), bool(up), bool(activate),
                              float(slope), 'layer_tail')
@@ -73,9 +70,6 @@ def layer_styles(w, affine, conv_weight, demodulate=True, style_gain=1.0):
     if getattr(affine, 'activate', False):
         raise RuntimeError('layer_styles: an affine with an activation is not supported')
     has_bias = getattr(affine, 'bias', None) is not None
-    for t, name in ((w, 'w'), (affine.weight, 'affine.weight'), (conv_weight, 'conv_weight')):
-        if not t.is_cuda:
-            raise RuntimeError('layer_styles: %s must live on the GPU (no CPU path in nerf_from_image_amd)' % name)
     # checked once: the node's forward and backward launch on these very tensors
     kw = ops.synth_head_args(w, affine.weight, affine.bias if has_bias else None, affine.weight_gain, affine.bias_gain, conv_weight,
                              bool(demodulate), float(style_gain), 'layer_styles')
@@ -85,7 +79,7 @@ def layer_styles(w, affine, conv_weight, demodulate=True, style_gain=1.0):
         return dict(kw, latent=args[0], affine_weight=args[1], weight=args[2], affine_bias=args[3] if has_bias else None)
 
     def fwd(*args):
-        styles, dcoefs = ops._synth_head_launch(packed(args))
+        styles, dcoefs = ops.synth_head_launch(packed(args))
         return (styles, dcoefs) if demodulate else styles
 
     def bwd(inputs, out_meta, grads, needs, kept):
@@ -95,8 +89,8 @@ def layer_styles(w, affine, conv_weight, demodulate=True, style_gain=1.0):
         need_bias = has_bias and bool(needs[3])
         if (g_styles is None and g_dcoefs is None) or not (needs[0] or needs[1] or need_weight or need_bias):
             return (None,) * len(inputs)
-        g = ops._synth_head_bwd_launch(packed(inputs), g_styles, g_dcoefs, kept[0], kept[1] if demodulate else None, bool(needs[0]),
-                                       bool(needs[1]), need_bias, need_weight)
+        g = ops.synth_head_bwd_launch(packed(inputs), g_styles, g_dcoefs, kept[0], kept[1] if demodulate else None, bool(needs[0]),
+                                      bool(needs[1]), need_bias, need_weight)
         g_weight = g.get('g_weight')
         return (g.get('g_latent'), g.get('g_affine_weight'), None if g_weight is None else g_weight.view(shape)) + \
             ((g.get('g_affine_bias'),) if has_bias else ())
@@ -108,18 +102,15 @@ def layer_styles(w, affine, conv_weight, demodulate=True, style_gain=1.0):
 def modulate(x, styles):
     """Differentiable x * styles.reshape(B, -1, 1, 1) (stylegan.py:132): x [B,C,H,W], styles [B,C] -> dense [B,C,H,W].  One launch
     forward, one backward (g_x, and g_styles summed in a fixed order)."""
-    for t, name in ((x, 'x'), (styles, 'styles')):
-        if not t.is_cuda:
-            raise RuntimeError('modulate: %s must live on the GPU (no CPU path in nerf_from_image_amd)' % name)
     kw = ops.synth_modulate_args(x, styles, 'modulate')
 
     def fwd(a_x, a_s):
-        return ops._synth_modulate_launch(dict(kw, x=a_x, styles=a_s))
+        return ops.synth_modulate_launch(dict(kw, x=a_x, styles=a_s))
 
     def bwd(inputs, out_meta, grads, needs):
         if grads[0] is None or not any(needs):
             return (None, None)
-        return ops._synth_modulate_bwd_launch(dict(kw, x=inputs[0], styles=inputs[1]), grads[0].contiguous(), bool(needs[0]), bool(needs[1]))
+        return ops.synth_modulate_bwd_launch(dict(kw, x=inputs[0], styles=inputs[1]), grads[0].contiguous(), bool(needs[0]), bool(needs[1]))
     return differentiable('synth_modulate', fwd, kw['x'], kw['styles'], bwd=bwd)
 
 

@@ -1,5 +1,6 @@
 """The contract between a caller's tensors and the raw pointers a kernel gets, as one table: a row per core wrapper of
-nerf_from_image_amd/ops.py (+ field_backward.field_query_bwd) with the smallest valid arguments, the way to call it, its
+nerf_from_image_amd/ops.py (+ field_backward.field_query_bwd; the synthesis layer's tail, head and modulation) with the
+smallest valid arguments, the way to call it, its
 tensor arguments, the element count the wrapper must insist on for each, and the widest access a kernel makes through each
 pointer.  tests/test_wrapper_contract.py (CPU) and tests/test_wrapper_contract_gpu.py run every row through the same
 cases: views of the same values, refused arguments, unaligned views.
@@ -420,6 +421,71 @@ def _rows():
     add('torgb_texels_bwd', 'torgb_texels_bwd', handoff,
         lambda a: ops.torgb_texels_bwd(a['g_out'], a['x'], a['styles'], a['weight'], a['previous_image'], ordered=True),
         dict(hc, g_out=lambda a: B * 96 * R * R))
+
+    # ---- synthesis layer: tail, head, modulation.  The families' own smallest shapes (tests/test_synth_tail_gpu.py,
+    # tests/synth_head_util.py): the tail at B = 2, C = 3, R = 4, once with `up` (y one wider, the 4x4 filter, noise per image)
+    # and once without (one noise plane for the batch); the head at D = 70 (one wave and a tail), I = 5, O = 3, K = 9 with
+    # demodulation and a bias; the modulation on x [2,5,4,4].  What a backward reads of its forward comes from the forward
+    # (on the CPU, where no row gets as far as reading it: zeros of that shape).
+    TB, TC, TR = 2, 3, 4
+    GAIN = 2.0 ** 0.5
+
+    def tail(dev, up):
+        g = _gen(19 + int(up))
+        n = TR + 1 if up else TR
+        a = dict(y=torch.randn(TB, TC, n, n, generator=g), dcoefs=0.5 + torch.rand(TB, TC, generator=g),
+                 noise=0.1 * (torch.randn(TB, 1, TR, TR, generator=g) if up else torch.randn(TR, TR, generator=g)),
+                 bias=0.3 * torch.randn(TC, generator=g), taps=torch.rand(4, 4, generator=g) / 8 if up else None,
+                 g_out=torch.randn(TB, TC, TR, TR, generator=g))
+        a = {k: v if v is None else v.to(dev) for k, v in a.items()}
+        a['out'] = (ops.synth_tail(a['y'], a['dcoefs'], a['noise'], a['bias'], a['taps'], GAIN, up) if torch.device(dev).type == 'cuda'
+                    else torch.zeros(TB, TC, TR, TR))
+        return a
+    for up in (True, False):
+        tc = {'y': None, 'dcoefs': lambda a: TB * TC, 'noise': lambda a, up=up: (TB if up else 1) * TR * TR, 'bias': lambda a: TC}
+        if up:
+            tc['taps'] = lambda a: 16
+        tag = 'up' if up else 'shared-noise'
+        add('synth_tail[%s]' % tag, 'synth_tail', lambda dev, up=up: tail(dev, up),
+            lambda a, up=up: ops.synth_tail(a['y'], a['dcoefs'], a['noise'], a['bias'], a['taps'], GAIN, up), tc)
+        add('synth_tail_bwd[%s]' % tag, 'synth_tail_bwd', lambda dev, up=up: tail(dev, up),
+            lambda a, up=up: ops.synth_tail_bwd(a['g_out'], a['out'], a['y'], a['dcoefs'], a['noise'], a['bias'], a['taps'], GAIN, up,
+                                                need_noise=True),
+            dict(tc, g_out=lambda a: TB * TC * TR * TR, out=lambda a: TB * TC * TR * TR))
+
+    HB, HD, HI, HO, HK = 2, 70, 5, 3, 9
+
+    def head(dev):
+        g = _gen(21)
+        a = dict(latent=torch.randn(HB, HD, generator=g), affine_weight=torch.randn(HI, HD, generator=g),
+                 affine_bias=1.0 + 0.5 * torch.randn(HI, generator=g), conv_weight=torch.randn(HO, HI, 3, 3, generator=g),
+                 g_styles=torch.randn(HB, HI, generator=g), g_dcoefs=torch.randn(HB, HO, generator=g))
+        a = {k: v.to(dev) for k, v in a.items()}
+        a['styles'], a['dcoefs'] = (head_fwd(a) if torch.device(dev).type == 'cuda' else (torch.zeros(HB, HI), torch.zeros(HB, HO)))
+        return a
+
+    def head_fwd(a):
+        return ops.synth_head(a['latent'], a['affine_weight'], a['affine_bias'], HD ** -0.5, 1.0, a['conv_weight'])
+    # conv_weight sets O for the forward; the backward has dcoefs [B,O] to hold it to
+    add('synth_head', 'synth_head', head, head_fwd,
+        {'latent': None, 'affine_weight': lambda a: HI * HD, 'affine_bias': lambda a: HI, 'conv_weight': None})
+    add('synth_head_bwd', 'synth_head_bwd', head,
+        lambda a: ops.synth_head_bwd(a['g_styles'], a['g_dcoefs'], a['styles'], a['dcoefs'], a['latent'], a['affine_weight'], a['affine_bias'],
+                                     HD ** -0.5, 1.0, a['conv_weight']),
+        {'latent': None, 'affine_weight': lambda a: HI * HD, 'affine_bias': lambda a: HI, 'conv_weight': lambda a: HO * HI * HK,
+         'g_styles': lambda a: HB * HI, 'g_dcoefs': lambda a: HB * HO, 'styles': lambda a: HB * HI, 'dcoefs': lambda a: HB * HO})
+
+    def modulation(dev):
+        g = _gen(22)
+        a = dict(x=torch.randn(2, 5, 4, 4, generator=g), styles=torch.randn(2, 5, generator=g), g_out=torch.randn(2, 5, 4, 4, generator=g))
+        return {k: v.to(dev) for k, v in a.items()}
+    add('synth_modulate', 'synth_modulate', modulation, lambda a: ops.synth_modulate(a['x'], a['styles']),
+        {'x': None, 'styles': lambda a: 10})
+    # a dense x or g_out one float off 16-byte alignment is read in place on the scalar path, which adds a plane's products in
+    # another order than the 16-byte path: g_styles within one unit in the last place of its largest entry, the bound of
+    # tests/test_synth_head_gpu.py test_modulate_views_and_unaligned_planes (which also holds the copied views to the same bits)
+    add('synth_modulate_bwd', 'synth_modulate_bwd', modulation, lambda a: ops.synth_modulate_bwd(a['g_out'], a['x'], a['styles']),
+        {'x': None, 'styles': lambda a: 10, 'g_out': lambda a: 160}, exact=False, tolerance=2.0 ** -23)
     return rows
 
 
@@ -431,8 +497,10 @@ EXEMPT = {
     'texel_grad_to_planes': 'a permute, or texels_to_planes, which has a row',
     'synth_tail_launch': 'takes the dict synth_tail_args has checked: covered through synth_tail',
     'synth_tail_bwd_launch': 'takes the dict synth_tail_args has checked: covered through synth_tail_bwd',
-    'synth_tail': 'views and refusals: tests/test_synth_tail_gpu.py',
-    'synth_tail_bwd': 'views and refusals: tests/test_synth_tail_gpu.py',
+    'synth_head_launch': 'takes the dict synth_head_args has checked: covered through synth_head',
+    'synth_head_bwd_launch': 'takes the dict synth_head_args has checked: covered through synth_head_bwd',
+    'synth_modulate_launch': 'takes the dict synth_modulate_args has checked: covered through synth_modulate',
+    'synth_modulate_bwd_launch': 'takes the dict synth_modulate_args has checked: covered through synth_modulate_bwd',
     'image_ssim': 'dense in either layout, else copied: tests/test_ssim_gpu.py',
     'separable_filter': 'dense in either layout, else copied: tests/test_blur_gpu.py',
     'lpips_head': '_lpips_inputs: tests/test_lpips_gpu.py',
@@ -450,16 +518,16 @@ EXEMPT = {
 
 def wrappers_that_reach_the_library(module=ops):
     """Public functions of `module` whose body hands something to _lib.ptr / call_struct / make_args / struct_query (or to
-    _call_ordered, which does), directly or through another public function of the module."""
-    direct = re.compile(r'_lib\.(ptr|call_struct|make_args|struct_query)\(|_call_ordered\(')
-    public = {n: inspect.getsource(f) for n, f in vars(module).items()
-              if inspect.isfunction(f) and f.__module__ == module.__name__ and not n.startswith('_')}
-    found = {n for n, src in public.items() if direct.search(src)}
+    the module's launch and workspace helpers, which do), directly or through another function of the module - a private
+    one as well: a public wrapper whose only way to the library is `_something(...)` is found."""
+    direct = re.compile(r'_lib\.(ptr|call_struct|make_args|struct_query)\(|\b_(launch|launch_positional|workspace|call_ordered)\(')
+    own = {n: inspect.getsource(f) for n, f in vars(module).items() if inspect.isfunction(f) and f.__module__ == module.__name__}
+    found = {n for n, src in own.items() if direct.search(src)}
     grew = True
     while grew:
         grew = False
-        for n, src in public.items():
+        for n, src in own.items():
             if n not in found and any(re.search(r'\b%s\(' % re.escape(m), src) for m in found):
                 found.add(n)
                 grew = True
-    return found
+    return {n for n in found if not n.startswith('_')}

@@ -28,6 +28,59 @@ def test_a_wrapper_without_a_row_is_noticed(monkeypatch):
     assert 'points_bwd' in cu.wrappers_that_reach_the_library() - {r.fn for r in left} - set(cu.EXEMPT)
 
 
+STAND_IN = '''
+from nerf_from_image_amd import _lib
+
+
+def _hand_over(kw):
+    _lib.call_struct('nfi_x', 'nfi_x_args', 0, **kw)
+
+
+def _twice_removed(kw):
+    return _hand_over(kw)
+
+
+def through_a_private_helper(x):
+    return _hand_over(dict(x=x))
+
+
+def through_two_private_helpers(x):
+    return _twice_removed(dict(x=x))
+
+
+def through_a_public_wrapper(x):
+    return through_a_private_helper(x)
+
+
+def straight(x):
+    _lib.call_struct('nfi_x', 'nfi_x_args', 0, x=x)
+
+
+def checks_only(x):
+    return x
+'''
+
+
+def test_a_wrapper_whose_only_way_to_the_library_is_a_private_helper_is_noticed(tmp_path):
+    """The completeness check follows the module's private helpers: a public function that reaches _lib only through
+    `_something(...)` is found, and without a row or a reason it is reported as missing.  (A stand-in module: ops.py's own
+    names are not restated here.)"""
+    import importlib.util
+    path = tmp_path / 'contract_stand_in.py'
+    path.write_text(STAND_IN)
+    spec = importlib.util.spec_from_file_location('contract_stand_in', str(path))
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    reach = cu.wrappers_that_reach_the_library(module)
+    assert reach == {'through_a_private_helper', 'through_two_private_helpers', 'through_a_public_wrapper', 'straight'}
+    missing = reach - {r.fn for r in cu.ROWS} - set(cu.EXEMPT)
+    assert {'through_a_private_helper', 'through_two_private_helpers'} <= missing
+    # ... and in ops.py itself every launcher that takes a checked dict is public, seen, and exempt through its wrapper
+    launchers = {n for n in cu.wrappers_that_reach_the_library() if n.endswith('_launch')}
+    assert launchers and launchers <= set(cu.EXEMPT)
+    assert all(cu.EXEMPT[n].rsplit(' ', 1)[-1] in {r.fn for r in cu.ROWS} for n in launchers)
+
+
 def test_launching_entries_are_told_from_size_queries():
     launching = cu.stream_entries()
     assert {'nfi_render_fwd', 'nfi_field_query_bwd', 'nfi_points_on_rays', 'nfi_sdf_gradient_bwd_ordered', 'nfi_raygen_bwd'} <= launching
